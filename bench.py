@@ -9,8 +9,12 @@ anything touches a GPU, and rank 0 prints the line.
 --workload snark (default, the headline metric, SURVEY.md 8d config 3): SNARK::prove (src/lib.rs:971-2746)
     on a synthetic 2^20-constraint program (2 block types x 2^9 executions x 2^10 constraints), instances
     encoded and witness resident in HBM before the timed region; every step produces the full bincode(SNARK),
-    compared byte-for-byte with the CPU oracle's. Multi-GPU: independent replicas (weak scaling).
-    At N = 1 the same line also carries every other single-GPU BASELINE config, each measured in this run with its
+    the same bytes in every step. Multi-GPU: independent replicas (weak scaling). A plain run sets up, warms up,
+    times the K steps and prints the headline line (metric, value, ms_per_step, shape, proof hash) and nothing else.
+    --full adds every other measurement and check to that line, each in legs of its own after the timed steps: the
+    proof compared byte-for-byte with the CPU oracle's, the callback-transcript mode, the per-kernel profiling pass
+    with its rooflines, the witness-upload-inclusive time, SNARK::verify, the CPU baselines, and
+    at N = 1 every other single-GPU BASELINE config, each measured in this run with its
     own roofline and CPU baselines (--extras none skips them): config 2 (`config2_msm`: one 2^16-point MSM;
     `config2_rows`: the 1024 x 1024 Hyrax row commit of a 2^20-entry polynomial), config 4 on one GPU
     (`config4_r1cs`: R1CSProof::prove over P = 8 x 2^9 x 2^10 = 2^22 constraints), config 5 (`config5_spark`:
@@ -21,9 +25,12 @@ anything touches a GPU, and rank 0 prints the line.
     executions x 2^10 constraints = 2^22. Sharded modes exchange over libspg's own RCCL transport
     (spg_set_comm_rccl) whenever the backend is nccl; --comm callback selects the torch.distributed callback.
 --workload spark: SURVEY 8d config 5 alone; --workload msm: SURVEY 8d config 2 alone (both strong scaling
-    over the ranks by default).
+    over the ranks by default). These single-config workloads always report in full.
+--dump-outputs DIR: after the timed steps, what the last timed step returned to its caller (the proof bytes, the MSM
+    result, the row commitments) is written as DIR/<name>.npy, one float32 per byte; inputs are seeded, so two
+    builds run with the same arguments can be compared output for output.
 
-Rooflines: `roofline` belongs to the kernel with the most device time that has a work model -- VALU work (curve
+Rooflines (--full): `roofline` belongs to the kernel with the most device time that has a work model -- VALU work (curve
 mixed additions, one per nonzero signed window digit) against the measured whole-GPU ext_madd throughput, or
 algorithmic HBM bytes against 8 TB/s; `roofline_hbm` / `roofline_valu` give the largest kernel of each kind.
 Per-launch times are libspg's HIP events on its context stream (spg_prof_read2) in a profiling pass after the
@@ -112,6 +119,12 @@ def parse():
     ap.add_argument("--comm", default="auto", choices=["auto", "rccl", "callback"],
                     help="sharded modes: libspg's RCCL transport (auto: with the nccl backend) or the torch callback")
     ap.add_argument("--traffic", default=None, help="per-launch HBM bytes from rocprofv3 --pmc (scripts/pmc_traffic.py)")
+    ap.add_argument("--full", action="store_true",
+                    help="snark: after the timed steps also run every other leg (oracle comparison and CPU baselines, "
+                         "callback-transcript mode, profiling pass and rooflines, witness upload, verify, --extras); "
+                         "off by default, so a plain run does only what the headline figure needs")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step returned as DIR/<name>.npy (float32, one value per byte)")
     return ap.parse_args()
 
 
@@ -190,7 +203,7 @@ def install_comm(env, ctx, how="auto"):
 
 def timed(env, step, steps, warmup):
     """warmup untimed steps, then `steps` timed ones bracketed by barrier + synchronize; returns (seconds max over
-    ranks, per-step laps on this rank, set of result hashes)"""
+    ranks, per-step laps on this rank, set of result hashes, the last step's result)"""
     for _ in range(warmup):
         step()
     env.sync()
@@ -203,7 +216,18 @@ def timed(env, step, steps, warmup):
     env.sync()
     dt = time.perf_counter() - t0
     # the determinism check (every step's bytes hashed) is the bench's own bookkeeping: after the timed region
-    return env.max_over_ranks(dt), laps, {hashlib.sha256(r).hexdigest() for r in res}
+    return env.max_over_ranks(dt), laps, {hashlib.sha256(r).hexdigest() for r in res}, res[-1] if res else None
+
+
+def dump_outputs(env, path, **arrays):
+    """--dump-outputs: each named result of the last timed step (bytes, as its caller receives them) as
+    <path>/<name>.npy, one float32 per byte; with several ranks every rank writes its own <name>_rank<r>.npy"""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    for name, raw in arrays.items():
+        f = name if env.world == 1 else f"{name}_rank{env.rank}"
+        np.save(os.path.join(path, f + ".npy"), np.frombuffer(raw, dtype=np.uint8).astype(np.float32))
 
 
 def profile_pass(ctx, step, steps):
@@ -401,7 +425,7 @@ def no_table_leg(env, ctx, step, steps, warmup, outs):
             got.add(r if isinstance(r, bytes) else r.tobytes())
             return r if isinstance(r, bytes) else r.tobytes()
 
-        dt, laps, _ = timed(env, st, steps, warmup)
+        dt, laps, _, _ = timed(env, st, steps, warmup)
     finally:
         ctx.set_comb(True)
     return {"ms_per_step": round(dt / steps * 1e3, 3), "ms_per_step_median": round(sorted(laps)[len(laps) // 2] * 1e3, 3),
@@ -440,9 +464,49 @@ def main_snark(a):
                                spg.RandomTape(b"proof", seed))
 
     comb0 = spg.comb_stats()
-    dt, laps, proofs = timed(env, lambda: prove(wit), a.steps, a.warmup)
+    dt, laps, proofs, last = timed(env, lambda: prove(wit), a.steps, a.warmup)
     assert len(proofs) == 1, "proof bytes changed between steps"
     comb1 = spg.comb_stats()
+    if a.dump_outputs:
+        dump_outputs(env, a.dump_outputs, proof=last)
+    N = wl.total_constraints
+    value = N * env.world * a.steps / dt
+    # every other leg runs on all ranks (the sharded extras are collective); rank 0 prints
+    more = snark_full(a, env, ctx, wl, views, seed, gens, block, pairwise, perm_root, wit, prove, dt, laps,
+                      proofs) if a.full else {}
+    if env.rank == 0:
+        out = {
+            "metric": "R1CS constraints/sec (SNARK::prove) at 2^20 vars; proof bytes bit-exact",
+            "value": round(value, 1), "unit": "constraints/s", "n_gpus": env.world, "steps": a.steps,
+            "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True,
+            "scaling": "weak", "vs_baseline": None, "dtype": "fq252 (8x u32 Montgomery limbs), ristretto255",
+            "data": "synthetic program (2 block types, chain-of-squarings blocks, seeded), random-tape seed fixed",
+            "config": {"workload": "SNARK::prove (src/lib.rs:971-2746)", "block_types": 2,
+                       "constraints_per_block": 1 << a.log_cons, "executions_per_block": 1 << a.log_proofs,
+                       "constraints_per_gpu": N, "num_vars": wl.num_vars, "num_ios": wl.num_ios,
+                       "gens": "R1CSGens(gens_r1cs_sat, 2^24)", "parallelism": f"replicas x{env.world}",
+                       "devices_visible": env.ndev, "ranks_share_a_gpu": env.world > env.ndev,
+                       "launcher": os.environ.get("SPG_BENCH_LAUNCHER") or ("torchrun" if env.world > 1 else None)},
+            "proof_sha256": sorted(proofs)[0][:16],
+            "precomputation": precomputation(
+                comb0, comb1, "fixed-base tables over the public generators, built once per generator set on first use "
+                              "(in the warmup steps here, outside value) and kept in HBM; the reference's SNARK::prove "
+                              "runs vartime MSMs without tables"),
+            "ms_per_step_median": round(sorted(laps)[len(laps) // 2] * 1e3, 3),
+            "ms_per_step_min": round(min(laps) * 1e3, 3),
+            "encode_s": round(t_encode, 3), "host_gen_s": round(t_gen, 3),
+        }
+        out.update(more)
+        print(json.dumps(out))
+    env.close()
+
+
+def snark_full(a, env, ctx, wl, views, seed, gens, block, pairwise, perm_root, wit, prove, dt, laps, proofs):
+    """--full: the legs of the headline workload beside its timed steps, run after them on the same context, and the
+    other BASELINE configs (--extras); returns the fields they add to the line"""
+    import spg
+
+    N = wl.total_constraints
     # the drop-in mode (INTEGRATION.md section 3, item 4): every append / challenge of the prove goes through C callbacks
     # into a caller-owned merlin transcript (libspg_hostcheck's native merlin, as a Rust caller's extern "C" trampolines
     # over &mut Transcript would) instead of libspg's own; same steps, timed the same way, right after the timed region
@@ -450,7 +514,7 @@ def main_snark(a):
         return spg.snark_prove(ctx, block, pairwise, perm_root, w, gens, spg.Transcript.from_native_merlin(b"snark_bench"),
                                spg.RandomTape(b"proof", seed))
 
-    dt_cb, laps_cb, proofs_cb = timed(env, lambda: prove_cb(wit), a.steps, 1)
+    dt_cb, laps_cb, proofs_cb, _ = timed(env, lambda: prove_cb(wit), a.steps, 1)
     # the two modes alternated step by step (box drift cancels): medians of each
     alt = {0: [], 1: []}
     for i in range(2 * a.steps):
@@ -474,8 +538,6 @@ def main_snark(a):
     for _ in range(3):
         spg.snark_verify(ctx, block, pairwise, perm_root, views.inputs, gens, spg.Transcript(b"snark_bench"), proof)
     t_verify = (time.perf_counter() - t1) / 3
-    N = wl.total_constraints
-    value = N * env.world * a.steps / dt
     roof, roof_h, roof_v = rooflines(prof, a.traffic or TRAFFIC["snark"])
     cpu = cpu_all = bitexact = cpu_verify_ms = None
     if env.rank == 0 and env.world == 1 and not a.no_cpu_baseline:
@@ -525,51 +587,32 @@ def main_snark(a):
                                                                  if a.extras_log_nnz == 24 else None))
         if "cpu1" in want and cpu_on:
             extras["config1_cpu"] = guarded(cpu1_core)
-    if env.rank == 0:
-        out = {
-            "metric": "R1CS constraints/sec (SNARK::prove) at 2^20 vars; proof bytes bit-exact",
-            "value": round(value, 1), "unit": "constraints/s", "n_gpus": env.world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "fq252 (8x u32 Montgomery limbs), ristretto255",
-            "data": "synthetic program (2 block types, chain-of-squarings blocks, seeded), random-tape seed fixed",
-            "config": {"workload": "SNARK::prove (src/lib.rs:971-2746)", "block_types": 2,
-                       "constraints_per_block": 1 << a.log_cons, "executions_per_block": 1 << a.log_proofs,
-                       "constraints_per_gpu": N, "num_vars": wl.num_vars, "num_ios": wl.num_ios,
-                       "gens": "R1CSGens(gens_r1cs_sat, 2^24)", "parallelism": f"replicas x{env.world}",
-                       "devices_visible": env.ndev, "ranks_share_a_gpu": env.world > env.ndev,
-                       "launcher": os.environ.get("SPG_BENCH_LAUNCHER") or ("torchrun" if env.world > 1 else None)},
-            "roofline": roof, "roofline_hbm": roof_h, "roofline_valu": roof_v,
-            "roofline_fq": roofline_fq(prof, a.traffic or TRAFFIC["snark"]),
-            "cpu_baseline": cpu, "cpu_baseline_all_cores": cpu_all, "proof_bitexact_vs_cpu": bitexact,
-            "proof_sha256": sorted(proofs)[0][:16],
-            "device_busy_ms_per_step": round(prof.busy_us / a.steps / 1e3, 3),
-            "device_busy_incl_resident_ms_per_step": round(prof.busy_resident_us / a.steps / 1e3, 3),
-            "value_incl_witness_upload": round(N * env.world / t_incl, 1),
-            "ms_per_step_incl_witness_upload": round(t_incl * 1e3, 3),
-            "transcript_mode": {
-                "value": "native (libspg's own merlin transcript)",
-                "callback": {"transcript": "caller-owned merlin behind spg_transcript_new_callbacks (C callbacks, "
-                                           "libspg_hostcheck spgh_merlin_*)",
-                             "value": round(N * env.world * a.steps / dt_cb, 1),
-                             "ms_per_step": round(dt_cb / a.steps * 1e3, 3),
-                             "ms_per_step_median": round(sorted(laps_cb)[len(laps_cb) // 2] * 1e3, 3),
-                             "over_native": round(dt_cb / dt, 4), "same_bytes": proofs_cb == proofs,
-                             "alternated": {"native_ms_median": round(med_native * 1e3, 3),
-                                            "callback_ms_median": round(med_cb * 1e3, 3),
-                                            "over_native": round(med_cb / med_native, 4)}}},
-            "precomputation": precomputation(
-                comb0, comb1, "fixed-base tables over the public generators, built once per generator set on first use "
-                              "(in the warmup steps here, outside value) and kept in HBM; the reference's SNARK::prove "
-                              "runs vartime MSMs without tables"),
-            "ms_per_step_median": round(sorted(laps)[len(laps) // 2] * 1e3, 3),
-            "ms_per_step_min": round(min(laps) * 1e3, 3), "verify_ms": round(t_verify * 1e3, 2),
-            "ms_per_step_laps": [round(x * 1e3, 2) for x in laps],
-            "verify_ok": verify_ok, "cpu_verify_ms_1thread": None if cpu_verify_ms is None else round(cpu_verify_ms, 1),
-            "encode_s": round(t_encode, 3), "host_gen_s": round(t_gen, 3), "kernels": kernel_table(prof, a.steps),
-        }
-        out.update(extras)
-        print(json.dumps(out))
-    env.close()
+    out = {
+        "roofline": roof, "roofline_hbm": roof_h, "roofline_valu": roof_v,
+        "roofline_fq": roofline_fq(prof, a.traffic or TRAFFIC["snark"]),
+        "cpu_baseline": cpu, "cpu_baseline_all_cores": cpu_all, "proof_bitexact_vs_cpu": bitexact,
+        "device_busy_ms_per_step": round(prof.busy_us / a.steps / 1e3, 3),
+        "device_busy_incl_resident_ms_per_step": round(prof.busy_resident_us / a.steps / 1e3, 3),
+        "value_incl_witness_upload": round(N * env.world / t_incl, 1),
+        "ms_per_step_incl_witness_upload": round(t_incl * 1e3, 3),
+        "transcript_mode": {
+            "value": "native (libspg's own merlin transcript)",
+            "callback": {"transcript": "caller-owned merlin behind spg_transcript_new_callbacks (C callbacks, "
+                                       "libspg_hostcheck spgh_merlin_*)",
+                         "value": round(N * env.world * a.steps / dt_cb, 1),
+                         "ms_per_step": round(dt_cb / a.steps * 1e3, 3),
+                         "ms_per_step_median": round(sorted(laps_cb)[len(laps_cb) // 2] * 1e3, 3),
+                         "over_native": round(dt_cb / dt, 4), "same_bytes": proofs_cb == proofs,
+                         "alternated": {"native_ms_median": round(med_native * 1e3, 3),
+                                        "callback_ms_median": round(med_cb * 1e3, 3),
+                                        "over_native": round(med_cb / med_native, 4)}}},
+        "verify_ms": round(t_verify * 1e3, 2),
+        "ms_per_step_laps": [round(x * 1e3, 2) for x in laps],
+        "verify_ok": verify_ok, "cpu_verify_ms_1thread": None if cpu_verify_ms is None else round(cpu_verify_ms, 1),
+        "kernels": kernel_table(prof, a.steps),
+    }
+    out.update(extras)
+    return out
 
 
 def guarded(fn, env=None):
@@ -592,7 +635,7 @@ def guarded(fn, env=None):
 
 
 # ---------------------------------------------------------------- R1CSProof::prove (config 4)
-def r1cs_core(env, ctx, cfg, shard, steps, warmup, cpu_on, traffic_file=None, comm="auto"):
+def r1cs_core(env, ctx, cfg, shard, steps, warmup, cpu_on, traffic_file=None, comm="auto", dump=None):
     """R1CSProof::prove (src/r1csproof.rs:210-685) on the CONFIGS shape `cfg`. shard: ONE proof split over the ranks by
     instance, its per-round (e0, e2, e3) sums and the final gathers over the ranks (RCCL with the nccl
     backend) -> strong scaling; else an independent proof per rank (weak). A step is one whole proof with the witness
@@ -627,7 +670,9 @@ def r1cs_core(env, ctx, cfg, shard, steps, warmup, cpu_on, traffic_file=None, co
                                wl.num_inputs, spg.Transcript(b"r1cs_bench"), spg.RandomTape(b"proof", seed))
         return pf
 
-    dt, laps, proofs = timed(env, step, steps, warmup)
+    dt, laps, proofs, last = timed(env, step, steps, warmup)
+    if dump:
+        dump_outputs(env, dump, proof=last)
     pre = precomputation(c0, spg.comb_stats(), "comb tables over R1CSGens' generators, built in the first (warmup) "
                                                "proof and kept in HBM; the CPU baseline uses no tables")
     if not shard:
@@ -702,7 +747,7 @@ def main_r1cs(a):
     cfg = a.config or ("r1cs_2e22_p8" if shard else "r1cs_2e20")
     ctx = spg.Context(env.gpu)
     out = r1cs_core(env, ctx, cfg, shard, a.steps, a.warmup, not a.no_cpu_baseline,
-                    a.traffic or (TRAFFIC["r1cs22"] if cfg == "r1cs_2e22_p8" else None), a.comm)
+                    a.traffic or (TRAFFIC["r1cs22"] if cfg == "r1cs_2e22_p8" else None), a.comm, a.dump_outputs)
     if env.rank == 0:
         out["vs_baseline"] = None
         print(json.dumps(out))
@@ -710,7 +755,7 @@ def main_r1cs(a):
 
 
 # ---------------------------------------------------------------- Hyrax row commit (config 2's row batch)
-def rows_core(env, ctx, steps, warmup, cpu_on, traffic_file=None, log_rows=10, log_width=10):
+def rows_core(env, ctx, steps, warmup, cpu_on, traffic_file=None, log_rows=10, log_width=10, dump=None):
     """SURVEY 8d config 2, second shape: DensePolynomial::commit_inner (src/dense_mlpoly.rs:184-212) of a
     2^20-entry polynomial as 2^10 row MSMs of 2^10 scalars each (the block-witness commit of every config-3 prove),
     generators MultiCommitGens(1024, spg_bench_rows), scalars resident in HBM. A step is the whole batch ending in
@@ -733,8 +778,10 @@ def rows_core(env, ctx, steps, warmup, cpu_on, traffic_file=None, log_rows=10, l
         return r.tobytes()
 
     c0 = spg.comb_stats()
-    dt, laps, _ = timed(env, step, steps, warmup)
+    dt, laps, _, last = timed(env, step, steps, warmup)
     assert len(outs) == 1, "row commitments changed between steps"
+    if dump:
+        dump_outputs(env, dump, rows=last)
     pre = precomputation(c0, spg.comb_stats(), "comb table of MultiCommitGens(1024, spg_bench_rows), built in the first "
                                                "(warmup) step and kept in HBM; the CPU baseline uses no tables")
     no_tab = no_table_leg(env, ctx, step, steps, warmup, outs)
@@ -810,7 +857,7 @@ def msm_scalars(n):
     return workload.to_mont_limbs(v)
 
 
-def msm_core(env, ctx, log_msm, steps, warmup, cpu_on, traffic_file=None):
+def msm_core(env, ctx, log_msm, steps, warmup, cpu_on, traffic_file=None, dump=None):
     """SURVEY 8d config 2: one 2^k-point MSM (GroupElement::vartime_multiscalar_mul, src/group.rs:98-116) against
     MultiCommitGens::new(2^k, b"spg_bench_msm").G, resident in HBM. With N ranks the MSM is split into contiguous
     chunks: each rank computes an uncompressed partial sum (spg_msm_partial), the 128-byte partials are
@@ -847,7 +894,9 @@ def msm_core(env, ctx, log_msm, steps, warmup, cpu_on, traffic_file=None):
         return r
 
     c0 = spg.comb_stats()
-    dt, laps, _ = timed(env, step_keep, steps, warmup)
+    dt, laps, _, last = timed(env, step_keep, steps, warmup)
+    if dump:
+        dump_outputs(env, dump, result=last)
     pre = precomputation(c0, spg.comb_stats(), "comb table of MultiCommitGens(2^k, spg_bench_msm) (c = 9 windows, "
                                                "128-byte entries), built in the first (warmup) step and kept in HBM; the "
                                                "CPU baseline is the table-free vartime Pippenger")
@@ -858,7 +907,7 @@ def msm_core(env, ctx, log_msm, steps, warmup, cpu_on, traffic_file=None):
         outs_raw.add(r)
         return r
 
-    dt_host, _, _ = timed(env, step_host, steps, warmup)
+    dt_host, _, _, _ = timed(env, step_host, steps, warmup)
     assert len(outs_raw) == 1, "MSM result changed between steps (or between the two entry points)"
     prof = profile_pass(ctx, step, steps)
     roof, roof_h, roof_v = rooflines(prof, traffic_file)
@@ -910,7 +959,7 @@ def main_msm(a):
 
     ctx = spg.Context(env.gpu)
     out = msm_core(env, ctx, a.log_msm, a.steps, a.warmup, not a.no_cpu_baseline,
-                   a.traffic or (TRAFFIC["msm16"] if a.log_msm == 16 else None))
+                   a.traffic or (TRAFFIC["msm16"] if a.log_msm == 16 else None), a.dump_outputs)
     if env.rank == 0:
         out["vs_baseline"] = None
         print(json.dumps(out))
@@ -918,7 +967,7 @@ def main_msm(a):
 
 
 # ---------------------------------------------------------------- SPARK (config 5)
-def spark_core(env, ctx, k, cpu_log_nnz, steps, warmup, mode, cpu_on, traffic_file=None, comm="auto"):
+def spark_core(env, ctx, k, cpu_log_nnz, steps, warmup, mode, cpu_on, traffic_file=None, comm="auto", dump=None):
     """SURVEY 8d config 5: SparseMatPolynomial::multi_evaluate + SparseMatPolyEvalProof::prove over the three
     2^k-nonzero matrices (A, B, C) with num_vars_x = num_vars_y = k. A step is one multi_evaluate at (rx, ry)
     plus one full SPARK evaluation proof (derefs, derefs commit, hash layer, product trees, batched layer
@@ -952,7 +1001,9 @@ def spark_core(env, ctx, k, cpu_log_nnz, steps, warmup, mode, cpu_on, traffic_fi
         evals = spg.r1cs_multi_evaluate(ctx, inst, 1, rx, ry)
         return comm.prove(rx, ry, evals, spg.Transcript(b"spark_bench"), spg.RandomTape(b"proof", seed))
 
-    dt, laps, proofs = timed(env, step, steps, warmup)
+    dt, laps, proofs, last = timed(env, step, steps, warmup)
+    if dump:
+        dump_outputs(env, dump, proof=last)
     pre = precomputation(c0, spg.comb_stats(), "comb tables of the gens_r1cs_eval generator sets (comb_ops / comb_mem "
                                                "rows at the commitment, the derefs rows in the first proof), kept in HBM; "
                                                "the CPU baseline uses no tables")
@@ -1014,7 +1065,7 @@ def main_spark(a):
 
     ctx = spg.Context(env.gpu)
     out = spark_core(env, ctx, a.log_nnz, a.cpu_log_nnz, a.steps, a.warmup, a.mode or "shard", not a.no_cpu_baseline,
-                     a.traffic or (TRAFFIC["spark24"] if a.log_nnz == 24 else None), a.comm)
+                     a.traffic or (TRAFFIC["spark24"] if a.log_nnz == 24 else None), a.comm, a.dump_outputs)
     if env.rank == 0:
         out["vs_baseline"] = None
         print(json.dumps(out))
@@ -1026,7 +1077,8 @@ def main_rows(a):
     import spg
 
     ctx = spg.Context(env.gpu)
-    out = rows_core(env, ctx, a.steps, a.warmup, not a.no_cpu_baseline, a.traffic or TRAFFIC["rows"])
+    out = rows_core(env, ctx, a.steps, a.warmup, not a.no_cpu_baseline, a.traffic or TRAFFIC["rows"],
+                    dump=a.dump_outputs)
     if env.rank == 0:
         out["vs_baseline"] = None
         print(json.dumps(out))

@@ -3,6 +3,7 @@
 #   TESTS=1     pytest -m gpu (PYTEST_K: -k filter; T_TESTS: time limit, default 900 s)
 #   SMOKE=1     __graft_entry__.smoke()
 #   BENCH=1     python bench.py $BENCH_ARGS > gpurun_out/${TAG}bench.json (T_BENCH, default 600 s)
+#               (the summary printed after it reads the rooflines, baselines and extra configs: pass --full in BENCH_ARGS)
 #   PROF=1      rocprofv3 --kernel-trace --stats of bench.py $PROF_ARGS (csv under gpurun_out/${TAG}prof)
 #   PMC=1       two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE) of bench.py $PROF_ARGS -> ${TAG}pmc_traffic.json
 #   TRACE=hipt  kernel + HIP runtime API + memory-copy trace of traced proves (scripts/trace_snark.py), lap events in

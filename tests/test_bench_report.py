@@ -1,6 +1,6 @@
 """bench.py's report helpers on a synthetic profile (no GPU): the roofline objects and the kernel table read the
 per-kernel tuples spg.Context.prof_read(ops=True) returns -- (launches, us, bytes, madds, Fq products) -- whatever
-mix of modelled quantities a kernel carries"""
+mix of modelled quantities a kernel carries; and its timing loop, output dump and option defaults"""
 import importlib.util
 import os
 
@@ -49,6 +49,49 @@ def test_rooflines_on_four_field_tuples(bench):
     roof, h, v = bench.rooflines(prof)
     assert roof is not None and h is not None and v is not None
     assert bench.roofline_fq(prof) is None
+
+
+class OneRank:
+    """what timed() / dump_outputs() use of bench.Env, for one rank without a device"""
+    rank, world = 0, 1
+
+    def sync(self):
+        pass
+
+    def max_over_ranks(self, x):
+        return x
+
+
+def test_timed_runs_the_steps_asked_for_and_returns_the_last_result(bench):
+    calls = []
+
+    def step():
+        calls.append(len(calls))
+        return bytes([calls[-1]])
+
+    dt, laps, hashes, last = bench.timed(OneRank(), step, steps=5, warmup=2)
+    assert len(calls) == 7 and len(laps) == 5 and len(hashes) == 5
+    assert last == bytes([6]) and dt >= sum(laps) > 0
+
+
+def test_dump_outputs_writes_float32_arrays_of_the_bytes(bench, tmp_path):
+    import numpy as np
+
+    raw = bytes(range(256)) * 3
+    bench.dump_outputs(OneRank(), str(tmp_path / "d"), proof=raw, rows=np.frombuffer(raw[:64], dtype=np.uint8))
+    got = np.load(tmp_path / "d" / "proof.npy")
+    assert got.dtype == np.float32 and got.shape == (768,)
+    assert got.astype(np.uint8).tobytes() == raw
+    assert np.load(tmp_path / "d" / "rows.npy").astype(np.uint8).tobytes() == raw[:64]
+
+
+def test_full_is_off_by_default(bench, monkeypatch):
+    monkeypatch.setattr("sys.argv", ["bench.py", "--gpus", "1", "--steps", "4", "--warmup", "1"])
+    a = bench.parse()
+    assert not a.full and a.dump_outputs is None and a.steps == 4
+    monkeypatch.setattr("sys.argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
 
 
 def test_kernel_table(bench):
