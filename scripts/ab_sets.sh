@@ -6,7 +6,6 @@ L=$PWD/spartan-parallel_amd/lib
 export BENCH_ARGS=${BENCH_ARGS:---extras none}
 for set in "$@"; do
   case $set in
-    persist) bash scripts/ab_env.sh SPG_LAYER_PERSIST "0 1" 3 ;;
     fuse) bash scripts/ab_env.sh SPG_SC_FUSE "0 1" 2 ;;
     bcomb) AB_KERNEL=msm_bullet_round bash scripts/ab_env.sh SPG_BULLET_COMB "0 1" 2 ;;
     bshape) AB_KERNEL=msm_bullet_round bash scripts/ab_env.sh SPG_BCOMB_R "4 8 16" 2 &&

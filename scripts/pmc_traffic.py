@@ -21,12 +21,11 @@ NAMES = {
     "k_phase1_pair": "sc_phase1_pair", "k_phase2_pair": "sc_phase2_pair", "k_phase1_fold2x": "sc_fold",
     "k_phase2_fold2x": "sc_fold", "k_pqx_bound_q": "sc_fold_q_all",
     "k_bullet_comb": "msm_bullet_round", "k_comb_msm_parts": "msm_comb_parts", "k_comb_accum": "msm_comb",
-    "k_layer_persist": "spark_layer_persist",
     "k_phase1_eval": "sc_phase1_eval", "k_phase2_eval": "sc_phase2_eval", "k_pqx_fold": "sc_fold",
     "k_spmv": "spmv_block", "k_z_fill": "z_fill", "k_abc": "eval_table_abc", "k_bound_part": "poly_bound",
     "k_fold_top": "fold_dense", "k_eq_table": "eq_table", "k_cubic_eval": "sc_cubic_eval",
     "k_final": "msm_final", "k_segments": "msm_segments", "k_items": "msm_bucket_items",
-    "k_layer_eval": "spark_layer_eval", "k_layer_tiny": "spark_layer_tiny", "k_fold_many": "spark_fold", "k_seg_dot": "spark_evaluate",
+    "k_seg_dot": "spark_evaluate",
     "k_gather": "spark_deref", "k_bound_rows": "spark_bound", "k_dot3": "spark_dotp_eval",
     "k_tree_level": "spark_product_tree", "k_tree_top": "spark_product_tree", "k_hash_ops": "spark_hash_layer",
     "k_layer_pair": "spark_layer_pair", "k_layer_triple": "spark_layer_triple",

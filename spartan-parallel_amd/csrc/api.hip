@@ -329,11 +329,6 @@ int mbox_wait(spg_ctx* ctx, uint32_t seq, Fq* out, int n) {
   return 0;
 }
 
-void down_post(spg_ctx* ctx, uint32_t seq, const Fq& r) {
-  for (int i = 0; i < 8; i++) ctx->down[8 + i] = r.l[i];
-  __atomic_store_n(ctx->down, seq, __ATOMIC_RELEASE);
-}
-
 struct SegArgs {
   const Fq* p[kSegMax];
   uint32_t off[kSegMax + 1];
@@ -564,17 +559,15 @@ extern "C" int spg_init(int device, spg_ctx** out) {
     return SPG_E_HIP;
   }
   void* mb = nullptr;
-  if (hipHostMalloc(&mb, 2 * spg::kMboxBytes + 4096, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
+  if (hipHostMalloc(&mb, 2 * spg::kMboxBytes, hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess ||
       hipHostGetDevicePointer((void**)&c->d_mbox, mb, 0) != hipSuccess) {
     delete c;
     return SPG_E_HIP;
   }
-  memset(mb, 0, 2 * spg::kMboxBytes + 4096);
+  memset(mb, 0, 2 * spg::kMboxBytes);
   c->mbox = (volatile uint32_t*)mb;
   c->res = (spg::Fq*)((uint8_t*)mb + spg::kMboxBytes);
   c->d_res = (spg::Fq*)((uint8_t*)c->d_mbox + spg::kMboxBytes);
-  c->down = (volatile uint32_t*)((uint8_t*)mb + 2 * spg::kMboxBytes);
-  c->d_down = (uint32_t*)((uint8_t*)c->d_mbox + 2 * spg::kMboxBytes);
   *out = c;
   return SPG_OK;
 }
@@ -668,19 +661,14 @@ extern "C" int spg_prof_read3(spg_ctx* c, char* names, long* launches, double* t
   if (!c) return SPG_E_ARG;
   hipStreamSynchronize(c->stream);
   hipStreamSynchronize(c->stream2);
-  // device busy time = the union of the timed intervals (kernels on the second stream overlap the main one's).
-  // A resident launch (scope name ending in "_persist") spans the host's answers between its rounds, so it is left
-  // out of "(device_busy)" and counted only in "(device_busy_resident)", the union over every launch.
+  // device busy time = the union of the timed intervals (kernels on the second stream overlap the main one's)
   if (!c->prof_pending.empty()) {
-    std::vector<std::pair<float, float>> iv, iv_all;
+    std::vector<std::pair<float, float>> iv;
     const hipEvent_t base = c->prof_pending.front().a;
     for (auto& r : c->prof_pending) {
       float s = 0.f, e = 0.f;
-      if (hipEventElapsedTime(&s, base, r.a) == hipSuccess && hipEventElapsedTime(&e, base, r.b) == hipSuccess) {
-        iv_all.push_back({s, e});
-        const size_t n = r.name.size();
-        if (!(n >= 8 && r.name.compare(n - 8, 8, "_persist") == 0)) iv.push_back({s, e});
-      }
+      if (hipEventElapsedTime(&s, base, r.a) == hipSuccess && hipEventElapsedTime(&e, base, r.b) == hipSuccess)
+        iv.push_back({s, e});
     }
     auto union_ms = [](std::vector<std::pair<float, float>>& v) {
       std::sort(v.begin(), v.end());
@@ -700,7 +688,6 @@ extern "C" int spg_prof_read3(spg_ctx* c, char* names, long* launches, double* t
       return busy;
     };
     c->prof_acc["(device_busy)"].us += union_ms(iv) * 1000.0;
-    c->prof_acc["(device_busy_resident)"].us += union_ms(iv_all) * 1000.0;
   }
   for (auto& r : c->prof_pending) {
     float ms = 0.f;

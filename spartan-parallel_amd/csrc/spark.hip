@@ -5,7 +5,7 @@
 //     AddrTimestamps::deref, Derefs::commit      :255-270, :51-67                        k_gather, Hyrax rows
 //     Layers::build_hash_layer, ProductCircuit   :612-736, src/product_tree.rs:36-58    k_hash_*, k_tree_level
 //     ProductLayerProof::prove                   :1118-1263                              batched_prove
-//     ProductCircuitEvalProofBatched::prove      src/product_tree.rs:271-396             k_layer_eval, k_fold_many
+//     ProductCircuitEvalProofBatched::prove      src/product_tree.rs:271-396             k_layer_* (layer.hpp)
 //     SumcheckInstanceProof::prove_cubic_batched src/sumcheck.rs:264-434
 //     HashLayerProof::prove                      :805-918                                k_seg_dot, PolyEvalProofs
 //
@@ -141,111 +141,6 @@ __global__ void k_tops(const Fq* __restrict__ tree, size_t nc, size_t stride, si
   if (c < nc) out[c] = fq_mul(tree[c * stride + off], tree[c * stride + off + 1]);
 }
 
-// A whole round of a small layer in one workgroup of 1024 threads (nt * len up to a few thousand): first the previous
-// round's bound_poly_var_top of every layer vector (when do_fold; vectors of 2 flen -> flen, one pass,
-// __syncthreads), then the round's (e0, e2, e3) with each triple's coefficient applied per element, a block
-// reduction and the mailbox post. No grid-wide ticket and one launch instead of fold + eval.
-__global__ void __launch_bounds__(1024) k_layer_tiny(const Triple* __restrict__ tr, const Fq* __restrict__ coeff,
-                                                     int nt, int log_len, Fq* const* __restrict__ fv, int nv,
-                                                     int do_fold, Fq r, uint32_t* __restrict__ mb, uint32_t seq) {
-  const int t = threadIdx.x;
-  const int len = 1 << log_len;
-  if (do_fold) {
-    const int flen = 2 * len;  // folded length
-    for (int k = t; k < nv * flen; k += 1024) {
-      Fq* p = fv[k / flen];
-      const int i = k % flen;
-      const Fq lo = p[i];
-      p[i] = fq_add(lo, fq_mul(r, fq_sub(p[i + flen], lo)));
-    }
-    __syncthreads();
-  }
-  Fq e0 = fq_zero(), e2 = fq_zero(), e3 = fq_zero();
-  for (int u = t; u < nt * len; u += 1024) {
-    const Triple x = tr[u >> log_len];
-    const Fq k = coeff[u >> log_len];
-    const int i = u & (len - 1);
-    // the coefficient scales the A factor (k A is linear in X), 8 multiplications per element instead of 9
-    const Fq al = fq_mul(k, x.A[i]), ah = fq_mul(k, x.A[i + len]);
-    const Fq bl = x.B[i], bh = x.B[i + len], cl = x.C[i], ch = x.C[i + len];
-    Fq da = fq_sub(ah, al), db = fq_sub(bh, bl), dc = fq_sub(ch, cl);
-    Fq a2 = fq_add(ah, da), b2 = fq_add(bh, db), c2 = fq_add(ch, dc);
-    e0 = fq_add(e0, fq_mul(fq_mul(al, bl), cl));
-    e2 = fq_add(e2, fq_mul(fq_mul(a2, b2), c2));
-    e3 = fq_add(e3, fq_mul(fq_mul(fq_add(a2, da), fq_add(b2, db)), fq_add(c2, dc)));
-  }
-  block_sum3_t0<1024>(e0, e2, e3);
-  if (t == 0) {
-    mbox_post3(mb, seq, e0, e2, e3);
-  }
-}
-// one batched cubic sumcheck round over nt triples (A_c, B_c, C_c) of length 2 * len:
-// sum_c coeff_c * sum_i A*B*C at X = 0, 2, 3 (sumcheck.rs:300-367). blockIdx.y = triple, so the coefficient
-// multiplies the block's sums once; the last block to finish (ticket on `counter`) adds every block's
-// partials and posts the round's three scalars to the host mailbox (one launch per round).
-__global__ void __launch_bounds__(256) k_layer_eval(const Triple* __restrict__ tr, const Fq* __restrict__ coeff,
-                                                    size_t len, Fq* __restrict__ partials,
-                                                    unsigned* __restrict__ counter, uint32_t* __restrict__ mb,
-                                                    uint32_t seq) {
-  const Triple x = tr[blockIdx.y];
-  Fq e0 = fq_zero(), e2 = fq_zero(), e3 = fq_zero();
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < len; i += (size_t)gridDim.x * 256) {
-    Fq al = x.A[i], ah = x.A[i + len], bl = x.B[i], bh = x.B[i + len], cl = x.C[i], ch = x.C[i + len];
-    Fq da = fq_sub(ah, al), db = fq_sub(bh, bl), dc = fq_sub(ch, cl);
-    Fq a2 = fq_add(ah, da), b2 = fq_add(bh, db), c2 = fq_add(ch, dc);
-    e0 = fq_add(e0, fq_mul(fq_mul(al, bl), cl));
-    e2 = fq_add(e2, fq_mul(fq_mul(a2, b2), c2));
-    e3 = fq_add(e3, fq_mul(fq_mul(fq_add(a2, da), fq_add(b2, db)), fq_add(c2, dc)));
-  }
-  block_sum3_sp(e0, e2, e3);
-  __shared__ bool last;
-  const unsigned nblocks = gridDim.x * gridDim.y, bid = blockIdx.y * gridDim.x + blockIdx.x;
-  if (threadIdx.x == 0) {
-    const Fq k = coeff[blockIdx.y];
-    partials[3 * bid] = fq_mul(k, e0);
-    partials[3 * bid + 1] = fq_mul(k, e2);
-    partials[3 * bid + 2] = fq_mul(k, e3);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    last = __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == nblocks - 1;
-    if (last) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-  }
-  __syncthreads();
-  if (!last) return;
-  Fq a = fq_zero(), b = fq_zero(), c = fq_zero();
-  for (unsigned i = threadIdx.x; i < nblocks; i += 256) {
-    a = fq_add(a, partials[3 * i]);
-    b = fq_add(b, partials[3 * i + 1]);
-    c = fq_add(c, partials[3 * i + 2]);
-  }
-  block_sum3_sp(a, b, c);
-  if (threadIdx.x == 0) {
-    mbox_post3(mb, seq, a, b, c);
-    __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-// DensePolynomial::bound_poly_var_top on nv distinct vectors of length 2 * len (in place)
-__global__ void k_fold_many(Fq* const* __restrict__ v, size_t nv, int log_len, Fq r) {
-  const size_t len = (size_t)1 << log_len;
-  size_t t = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (t >= nv * len) return;
-  Fq* p = v[t >> log_len];
-  size_t i = t & (len - 1);
-  Fq lo = p[i];
-  p[i] = fq_add(lo, fq_mul(r, fq_sub(p[i + len], lo)));
-}
-// A[0], B[0], C[0] of every triple (the final claims of a layer)
-__global__ void k_finals(const Triple* __restrict__ tr, size_t nt, Fq* __restrict__ out) {
-  size_t c = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (c >= nt) return;
-  out[3 * c] = tr[c].A[0];
-  out[3 * c + 1] = tr[c].B[0];
-  out[3 * c + 2] = tr[c].C[0];
-}
 // DotProductCircuit::evaluate per triple: sum_i A*B*C over n entries (blockIdx.y = triple)
 __global__ void __launch_bounds__(256) k_dot3(const Triple* __restrict__ tr, size_t n, Fq* __restrict__ partials) {
   const Triple x = tr[blockIdx.y];
@@ -317,10 +212,9 @@ static const size_t kSmallRowMax = 256;
 static const size_t kHostFinalRows = 64;  // latency-path commits of at most this many rows finish on the host
 // workspace slots of this file
 enum : size_t {
-  kWsCommit = 60, kWsL, kWsBoundPart, kWsBound, kWsSegPart, kWsSeg, kWsC, kWsTriples, kWsCoeff, kWsFoldPtr,
-  kWsPart, kWs3, kWsMemRx, kWsMemRy, kWsDerefs, kWsTreeOps, kWsTreeMem, kWsDotp, kWsFinals, kWsEqOps, kWsEqMem,
-  kWsTops, kWsCommitBk, kWsC2, kWsGather, kWsTopOps, kWsTopMem, kWsStage, kWsTsKeys, kWsTsTemp,  // 60 .. 89
-  kWsRelay = 94,
+  kWsCommit = 60, kWsL, kWsBoundPart, kWsBound, kWsSegPart, kWsSeg, kWsC, kWsTriples, kWsPart, kWsMemRx, kWsMemRy,
+  kWsDerefs, kWsTreeOps, kWsTreeMem, kWsDotp, kWsEqOps, kWsEqMem, kWsTops, kWsCommitBk, kWsC2, kWsGather, kWsTopOps,
+  kWsTopMem, kWsTsKeys, kWsTsTemp,  // 60 .. 84
   kWsMultiExt = 120, kWsMultiOut, kWsCommitExt  // (snark.hip uses 91 .. 93 and 95, verify.hip 96, msm_big.hip
                                                 // 100 .. 108, sumcheck.hip 110 .. 111)
 };
@@ -719,41 +613,579 @@ struct TreeSh {
   int W = 1, r = 0;
 };
 
-// ProductCircuitEvalProofBatched::prove with fused layer rounds (k_layer_round / k_layer_close above); same
-// transcript and proof as batched_prove below.
+// ------------------------------------------------------------------------------------ the layer prover
+// ProductCircuitEvalProofBatched::prove (product_tree.rs:271-396): batched_prove below walks the layers; per layer
+// layer_setup uploads the descriptors, run_rounds asks plan_step for the next launch form (round_single, round_pair,
+// round_triple, then layer_close when no launch posted the final entries) and layer_finals appends the claims.
+
+// the cubic Lagrange basis on 0..3 at r
+static void lagrange4(const Fq& r, Fq L[4]) {
+  static const Fq inv2 = fq_inv(fq_from_u64(2)), inv6 = fq_inv(fq_from_u64(6));
+  const Fq a0 = r, a1 = fq_sub(r, fq_one()), a2 = fq_sub(a1, fq_one()), a3 = fq_sub(a2, fq_one());
+  const Fq a01 = fq_mul(a0, a1), a23 = fq_mul(a2, a3);
+  L[0] = fq_neg(fq_mul(fq_mul(a1, a23), inv6));
+  L[1] = fq_mul(fq_mul(a0, a23), inv2);
+  L[2] = fq_neg(fq_mul(fq_mul(a01, a3), inv2));
+  L[3] = fq_mul(fq_mul(a01, a2), inv6);
+}
+
+// the launch forms' switches and limits (environment, read once)
+struct LayerKnobs {
+  bool quad, ends_on, pair_on, triple_on;
+  size_t wide_min;    // thread-elements from which a round takes the throughput form
+  size_t pair_max;    // elements (16 lanes each) of a paired launch
+  size_t triple_max;  // elements (a wave each, four per workgroup) of a tripled launch: 64 partials per workgroup
+  int pair_bs;        // 64: paired launches over 64-thread workgroups (more of them)
+  int step_cost[3];   // relative wall of a launched single / paired / tripled round trip, for the launch plan
+};
+static const LayerKnobs& layer_knobs() {
+  static const LayerKnobs kn = [] {
+    auto on = [](const char* name) { return !getenv(name) || atoi(getenv(name)) != 0; };
+    auto num = [](const char* name, size_t dflt) { return getenv(name) ? (size_t)atol(getenv(name)) : dflt; };
+    LayerKnobs k;
+    k.quad = on("SPG_LAYER_QUAD");
+    k.ends_on = on("SPG_LAYER_ENDS");
+    k.pair_on = on("SPG_LAYER_PAIR");
+    k.triple_on = on("SPG_LAYER_TRIPLE");
+    k.wide_min = num("SPG_WIDE_MIN", (size_t)1 << 19);
+    k.pair_bs = getenv("SPG_PAIR_BS") ? atoi(getenv("SPG_PAIR_BS")) : 0;
+    // a paired launch of E elements stores 16 partials per workgroup of BSp / 16 elements into `part` (3 x 2048
+    // scalars): 16 E / BSp * 16 <= 6144, so E <= 6144 with 256-thread workgroups and E <= 1536 with 64-thread ones
+    k.pair_max = std::min<size_t>(num("SPG_PAIR_MAX", 4096), k.pair_bs == 64 ? 1536 : 6144);
+    k.triple_max = std::min<size_t>(num("SPG_TRIPLE_MAX", 384), 384);
+    k.step_cost[0] = 18, k.step_cost[1] = 25, k.step_cost[2] = 30;
+    if (const char* e = getenv("SPG_STEP_COSTS"))
+      sscanf(e, "%d,%d,%d", &k.step_cost[0], &k.step_cost[1], &k.step_cost[2]);
+    return k;
+  }();
+  return kn;
+}
+
+// The launch plan. Two rounds in one launch (k_layer_pair): small rounds of an unsharded layer (`multi`), every
+// element's 16 lanes within pair_max elements, the last pair's corners within the mailbox; three (k_layer_triple): a
+// wave per element within triple_max elements, the last triple's corners within the mailbox. nt triples in ngroups
+// thread groups; k rounds left.
+static bool pair_ok(const LayerKnobs& kn, size_t nt, size_t ngroups, bool multi, size_t k) {
+  return kn.pair_on && multi && k >= 2 && (nt << (k - 2)) <= kn.pair_max && 15 + 12 * nt <= kMboxScalars &&
+         ngroups * ((size_t)1 << (k - 1)) < kn.wide_min;
+}
+static bool triple_ok(const LayerKnobs& kn, size_t nt, size_t ngroups, bool multi, size_t k) {
+  return kn.triple_on && multi && k >= 3 && (nt << (k - 3)) <= kn.triple_max && 64 + 24 * nt <= kMboxScalars &&
+         ngroups * ((size_t)1 << (k - 1)) < kn.wide_min;
+}
+// Single rounds first, then pairs, then triples (a pair leaves two pending folds, which only a pair or a triple
+// applies; a triple three, which only a triple applies), the cheapest by step_cost. Returns the rounds of the first
+// launch from k rounds left with `npend` folds pending, 0 when no plan finishes the layer.
+static int plan_step(const LayerKnobs& kn, size_t nt, size_t ngroups, bool multi, size_t k, int npend) {
+  const int inf = 1 << 28, mode = npend >= 3 ? 2 : (npend == 2 ? 1 : 0);  // 0: free, 1: after a pair, 2: after a triple
+  std::vector<std::array<int, 3>> best(k + 1), first(k + 1);
+  for (size_t j = 0; j <= k; j++)
+    for (int md = 0; md < 3; md++) {
+      int b = j == 0 ? 0 : inf, f = 0;
+      if (j >= 1 && md == 0 && best[j - 1][0] < inf && kn.step_cost[0] + best[j - 1][0] < b)
+        b = kn.step_cost[0] + best[j - 1][0], f = 1;
+      if (md <= 1 && pair_ok(kn, nt, ngroups, multi, j) && best[j - 2][1] < inf && kn.step_cost[1] + best[j - 2][1] < b)
+        b = kn.step_cost[1] + best[j - 2][1], f = 2;
+      if (triple_ok(kn, nt, ngroups, multi, j) && best[j - 3][2] < inf && kn.step_cost[2] + best[j - 3][2] < b)
+        b = kn.step_cost[2] + best[j - 3][2], f = 3;
+      best[j][md] = b;
+      first[j][md] = f;
+    }
+  return first[k][mode];
+}
+
+// what stays fixed over a prove's layers
+struct LayerEnv {
+  spg_ctx* ctx;
+  Tr& t;
+  const Shard& sh;
+  Laps& lp;
+  size_t nc;         // product circuits: triples 0 .. nc-1 share the eq vector
+  Fq* cbuf[2];       // the shared eq vector's ping-pong pair
+  uint8_t* ddesc;    // the layer's triples, then (at tr_bytes) their coefficients
+  size_t tr_bytes;
+  Fq* part;          // the ticketed reductions' partials (3 x 2048 scalars)
+  Fq* gbuf;          // sharded: the gathered entries
+  size_t W;          // ranks the trees are sharded over
+  int rank;
+  const Triple* dtr() const { return (const Triple*)ddesc; }
+  const Fq* dcoef() const { return (const Fq*)(ddesc + tr_bytes); }
+};
+// a layer's sumcheck as it goes
+struct LayerState {
+  size_t nt = 0, ngroups = 0;  // triples; thread groups (the product circuits share one thread per index)
+  int cur = 0;                 // the buffer holding the shared eq vector C
+  // bound_poly_var_top's not yet applied, with r[0], then r[1], then r[2]: one after a single round, two after a
+  // paired launch (which only a pair or a triple applies), three after a tripled one (which only a triple applies)
+  int npend = 0;
+  Fq r[3] = {fq_zero(), fq_zero(), fq_zero()};
+  Fq e = fq_zero();  // the running claim
+  FqV r_prod;        // the layer's challenges
+  LayerProofP proof;
+  bool shared = false;  // a failure returned from an exchange: every rank has it
+};
+
+// the host half of a round: UniPoly from (e0, e2, e3), transcript, r_j
+static Fq host_round(const LayerEnv& E, LayerState& S, const Fq ev[3]) {
+  Fq evals[4] = {ev[0], fq_sub(S.e, ev[0]), ev[1], ev[2]};
+  FqV poly = uni_from_evals3(evals);
+  append_unipoly(E.t, poly);
+  Fq r_j = E.t.challenge("challenge_nextround");
+  S.r_prod.push_back(r_j);
+  S.e = uni_eval(poly, r_j);
+  S.proof.polys.push_back({poly[0], poly[2], poly[3]});
+  return r_j;
+}
+
+// A[0], B[0], C[0] of every triple (after the pending fold, if any), by mailbox
+static int layer_close(const LayerEnv& E, LayerState& S, FqV& fin) {
+  spg_ctx* ctx = E.ctx;
+  if (S.npend > 1) return set_err(ctx, SPG_E_ARG, "layer close after a paired round");  // (the last pair posts its ends)
+  fin.resize(3 * S.nt);
+  KScope ks(ctx, "spark_layer_close");
+  const uint32_t seq = ++ctx->mbox_seq;
+  hipLaunchKernelGGL(k_layer_close, dim3(1), dim3(256), 0, ctx->stream, E.dtr(), (int)S.nt, S.npend, S.r[0],
+                     E.cbuf[S.cur], ctx->d_mbox, seq);
+  SPG_HIP(ctx, hipGetLastError());
+  S.npend = 0;
+  return mbox_wait(ctx, seq, fin.data(), (int)fin.size());
+}
+
+// One round in one launch, 2^log_len entries per vector. `local`: the round's sums are added over the ranks. *done:
+// the layer's last round in one workgroup also posted every vector's two entries and `fin` holds the final claims.
+static int round_single(const LayerEnv& E, LayerState& S, size_t log_len, bool local, bool close_after, FqV* fin,
+                        bool* done) {
+  spg_ctx* ctx = E.ctx;
+  hipStream_t s = ctx->stream;
+  const LayerKnobs& kn = layer_knobs();
+  if (S.npend > 1) return set_err(ctx, SPG_E_ARG, "single layer round after a paired one");
+  log_len--;
+  const size_t len = (size_t)1 << log_len, nt = S.nt, ngroups = S.ngroups, nc = E.nc;
+  const bool pending = S.npend == 1, wide = ngroups * len >= kn.wide_min;
+  const Triple* dtr = E.dtr();
+  const Fq* dcoef = E.dcoef();
+  Fq *cin = E.cbuf[S.cur], *cout = E.cbuf[S.cur ^ 1];
+  unsigned K;
+  int BS;
+  // algorithmic HBM bytes of the round: per distinct vector (A, B of every triple; the shared C once; each
+  // dot-product circuit's own C) and index, 2 entries read, or with the pending fold 4 read + 2 written
+  const double layer_bytes = (pending ? 192.0 : 64.0) * (double)len * (double)(2 * nt + ngroups);
+  if (wide) {  // throughput form for rounds that fill the chip
+    K = (unsigned)std::min<size_t>((ngroups * len + 255) / 256, 2048);
+    // Fq products per index: per product circuit k A B at 3 points from the folded A, B (3 + 2 + 4 folds), the
+    // shared C folded once (2) and multiplied in (3); a dot-product circuit 14 (its own C folded too)
+    const double fqm_w = (double)len * ((pending ? 2.0 : 0.0) + 3.0 + (double)nc * (pending ? 9.0 : 5.0) +
+                                        (double)(nt - nc) * (pending ? 14.0 : 8.0));
+    KScope ks(ctx, "spark_layer_round", layer_bytes, 0.0, fqm_w);
+    hipLaunchKernelGGL(k_layer_round_wide<256>, dim3(K), dim3(256), 0, s, dtr, dcoef, (int)nc, (int)nt, (int)log_len,
+                       pending ? 1 : 0, S.r[0], cin, cout, E.part, ctx->d_counter, ctx->d_mbox, ++ctx->mbox_seq);
+  } else if (kn.quad) {  // a quad per element, about one element per quad
+    const size_t Wd = nt * len;
+    BS = Wd <= 16 ? 64 : 256;
+    K = (unsigned)std::min<size_t>((Wd * 4 + BS - 1) / BS, 2048);
+  } else {
+    layer_grid(nt * len, &K, &BS);
+  }
+  // the layer's last round in one workgroup also posts every vector's two entries: the host then folds the
+  // final claims with the round's challenge, and no close launch (another round trip) follows
+  const bool ends =
+      close_after && log_len == 0 && kn.quad && K == 1 && 3 + 6 * nt <= kMboxScalars && !wide && kn.ends_on;
+  if (!wide) {
+    // Fq products per element: lanes 0..2 fold their vector's two entries (6) and form k A B C at their point (9)
+    KScope ks(ctx, "spark_layer_round", layer_bytes, 0.0, (double)nt * (double)len * (pending ? 15.0 : 9.0));
+    const int lg = (int)log_len, df = pending ? 1 : 0;
+    const uint32_t seq = ++ctx->mbox_seq;
+    if (kn.quad && BS == 64)
+      hipLaunchKernelGGL(k_layer_round_q<64>, dim3(K), dim3(64), 0, s, dtr, dcoef, (int)nt, lg, df, S.r[0], cin, cout,
+                         E.part, ctx->d_counter, ctx->d_mbox, seq, nullptr, ends ? 1 : 0);
+    else if (kn.quad)
+      hipLaunchKernelGGL(k_layer_round_q<256>, dim3(K), dim3(256), 0, s, dtr, dcoef, (int)nt, lg, df, S.r[0], cin, cout,
+                         E.part, ctx->d_counter, ctx->d_mbox, seq, nullptr, ends ? 1 : 0);
+    else if (BS == 64)
+      hipLaunchKernelGGL(k_layer_round<64>, dim3(K), dim3(64), 0, s, dtr, dcoef, (int)nt, lg, df, S.r[0], cin, cout,
+                         E.part, ctx->d_counter, ctx->d_mbox, seq, nullptr);
+    else
+      hipLaunchKernelGGL(k_layer_round<256>, dim3(K), dim3(256), 0, s, dtr, dcoef, (int)nt, lg, df, S.r[0], cin, cout,
+                         E.part, ctx->d_counter, ctx->d_mbox, seq, nullptr);
+  }
+  if (pending) S.cur ^= 1;
+  FqV ev(ends ? 3 + 6 * nt : 3);
+  const hipError_t le = hipGetLastError();
+  int rc = le != hipSuccess ? set_err(ctx, SPG_E_HIP, std::string("layer round: ") + hipGetErrorString(le))
+                            : mbox_wait(ctx, ctx->mbox_seq, ev.data(), (int)ev.size());
+  if (local) {
+    rc = comm_sum_fq(ctx, E.sh, rc, ev.data(), 3);
+    if (rc) S.shared = true;
+  }
+  if (rc) return rc;
+  E.lp.lap("round_eval_wait");
+  S.r[0] = host_round(E, S, ev.data());
+  S.npend = 1;
+  E.lp.lap("round_host");
+  if (ends) {  // bound_poly_var_top of the length-2 vectors, on the host
+    fin->resize(3 * nt);
+    for (size_t c = 0; c < 3 * nt; c++) {
+      const Fq lo = ev[3 + 2 * c], hi = ev[4 + 2 * c];
+      (*fin)[c] = fq_add(lo, fq_mul(S.r[0], fq_sub(hi, lo)));
+    }
+    S.npend = 0;
+    *done = true;
+  }
+  return 0;
+}
+
+// Two rounds in one launch (k_layer_pair), from 2^log_len entries per vector. *done: these were the layer's last
+// rounds, the launch posted every vector's 2 x 2 corners and `fin` holds the final claims.
+static int round_pair(const LayerEnv& E, LayerState& S, size_t log_len, FqV* fin, bool* done) {
+  spg_ctx* ctx = E.ctx;
+  if (S.npend > 2) return set_err(ctx, SPG_E_ARG, "paired layer round after a tripled one");
+  const int lgj = (int)log_len - 1;  // round j's half length 2^lgj; round j + 1's 2^(lgj - 1)
+  const size_t nt = S.nt, h = (size_t)1 << (lgj - 1), lanes = 16 * nt * h;
+  const int BSp = lanes <= 64 || layer_knobs().pair_bs == 64 ? 64 : 256;
+  const unsigned Kp = (unsigned)((lanes + BSp - 1) / BSp);
+  const bool ends = log_len == 2;  // the layer's last pair posts every vector's 2 x 2 corners
+  const int nf = S.npend;
+  PairArgs P;
+  P.tr = E.dtr();
+  P.coeff = E.dcoef();
+  P.nt = (int)nt;
+  P.log_len = lgj;
+  P.nf = nf;
+  P.r1 = S.r[0];
+  P.r2 = S.r[1];
+  P.r12 = fq_mul(S.r[0], S.r[1]);
+  P.cin = E.cbuf[S.cur];
+  P.cout = E.cbuf[S.cur ^ 1];
+  P.partials = E.part;
+  P.counter = ctx->d_counter;
+  P.mb = ctx->d_mbox;
+  P.seq = ++ctx->mbox_seq;
+  P.ends = ends ? 1 : 0;
+  P.probe = nullptr;
+  {
+    // algorithmic bytes: per distinct vector and element, 4 corners from 4 2^nf entries, written back when folded
+    const double per = 32.0 * (4.0 * (double)(1 << nf) + (nf ? 4.0 : 0.0));
+    // Fq products per element: the corners folded (12 x 3 with two pending folds, 12 with one), 15 points x 3
+    KScope ks(ctx, "spark_layer_pair", per * (double)h * (double)(2 * nt + S.ngroups), 0.0,
+              (double)nt * (double)h * (45.0 + (nf == 2 ? 36.0 : nf == 1 ? 12.0 : 0.0)));
+    if (BSp == 64)
+      hipLaunchKernelGGL(k_layer_pair<64>, dim3(Kp), dim3(64), 0, ctx->stream, P);
+    else
+      hipLaunchKernelGGL(k_layer_pair<256>, dim3(Kp), dim3(256), 0, ctx->stream, P);
+  }
+  if (nf) S.cur ^= 1;
+  FqV ev(15 + (ends ? 12 * nt : 0));
+  const hipError_t le = hipGetLastError();
+  E.lp.lap(ends ? "pair_launch_end" : "pair_launch");
+  const int rc = le != hipSuccess ? set_err(ctx, SPG_E_HIP, std::string("layer pair: ") + hipGetErrorString(le))
+                                  : mbox_wait(ctx, P.seq, ev.data(), (int)ev.size());
+  if (rc) return rc;
+  E.lp.lap(ends ? "pair_wait_end" : "pair_wait");
+  // round j: F(X, 0) + F(X, 1) at X = 0, 2, 3
+  const Fq ej[3] = {fq_add(ev[0], ev[12]), fq_add(ev[2], ev[13]), fq_add(ev[3], ev[14])};
+  const Fq rj = host_round(E, S, ej);
+  // round j + 1: the cubics t -> F(t, Y) through t = 0..3 (lines Y = 0, 2, 3) at t = r_j
+  Fq L[4];
+  lagrange4(rj, L);
+  Fq ej1[3];
+  for (int y = 0; y < 3; y++) {
+    Fq acc = fq_zero();
+    for (int k = 0; k < 4; k++) acc = fq_add(acc, fq_mul(L[k], ev[4 * y + k]));
+    ej1[y] = acc;
+  }
+  const Fq rj1 = host_round(E, S, ej1);
+  E.lp.lap("pair_host");
+  if (ends) {  // the 2 x 2 cube of every vector folded at (r_j, r_j+1): the layer's final claims
+    fin->resize(3 * nt);
+    for (size_t c = 0; c < 3 * nt; c++) {
+      const Fq* w = &ev[15 + 4 * c];  // p00, p01, p10, p11 of vector c % 3 of triple c / 3
+      const Fq q0 = fq_add(w[0], fq_mul(rj, fq_sub(w[2], w[0]))), q1 = fq_add(w[1], fq_mul(rj, fq_sub(w[3], w[1])));
+      (*fin)[c] = fq_add(q0, fq_mul(rj1, fq_sub(q1, q0)));
+    }
+    S.npend = 0;
+    E.lp.lap("pair_fin");
+    *done = true;
+    return 0;
+  }
+  S.npend = 2;
+  S.r[0] = rj;
+  S.r[1] = rj1;
+  return 0;
+}
+
+// Three rounds in one launch (k_layer_triple), from 2^log_len entries per vector. *done: these were the layer's last
+// rounds, the launch posted every vector's 2 x 2 x 2 corners and `fin` holds the final claims.
+static int round_triple(const LayerEnv& E, LayerState& S, size_t log_len, FqV* fin, bool* done) {
+  spg_ctx* ctx = E.ctx;
+  const int lgj = (int)log_len - 1;  // round j's half length 2^lgj; h = 2^(lgj - 2) elements per vector
+  const size_t nt = S.nt, h = (size_t)1 << (lgj - 2), El = nt * h;
+  const int BSt = El <= 1 ? 64 : 256;
+  const unsigned Kt = (unsigned)((El + BSt / 64 - 1) / (BSt / 64));
+  const bool ends = log_len == 3;  // the layer's last triple posts every vector's 2 x 2 x 2 corners
+  const int nf = S.npend;
+  TripleArgs P;
+  P.tr = E.dtr();
+  P.coeff = E.dcoef();
+  P.nt = (int)nt;
+  P.log_len = lgj;
+  P.nf = nf;
+  P.r1 = S.r[0];
+  P.r2 = S.r[1];
+  P.r3 = S.r[2];
+  P.r12 = fq_mul(S.r[0], S.r[1]);
+  P.r13 = fq_mul(S.r[0], S.r[2]);
+  P.r23 = fq_mul(S.r[1], S.r[2]);
+  P.r123 = fq_mul(P.r12, S.r[2]);
+  P.cin = E.cbuf[S.cur];
+  P.cout = E.cbuf[S.cur ^ 1];
+  P.partials = E.part;
+  P.counter = ctx->d_counter;
+  P.mb = ctx->d_mbox;
+  P.seq = ++ctx->mbox_seq;
+  P.ends = ends ? 1 : 0;
+  P.probe = nullptr;
+  {
+    // algorithmic bytes: per distinct vector and element, 8 corners from 8 2^nf entries, written back when folded
+    const double per = 32.0 * (8.0 * (double)(1 << nf) + (nf ? 8.0 : 0.0));
+    // Fq products per element: the 24 corners folded (2^nf - 1 each), 64 points x 3
+    KScope ks(ctx, "spark_layer_triple", per * (double)h * (double)(2 * nt + S.ngroups), 0.0,
+              (double)nt * (double)h * (192.0 + 24.0 * (double)((1 << nf) - 1)));
+    if (BSt == 64)
+      hipLaunchKernelGGL(k_layer_triple<64>, dim3(Kt), dim3(64), 0, ctx->stream, P);
+    else
+      hipLaunchKernelGGL(k_layer_triple<256>, dim3(Kt), dim3(256), 0, ctx->stream, P);
+  }
+  if (nf) S.cur ^= 1;
+  FqV ev(64 + (ends ? 24 * nt : 0));  // F(t, s, u) = ev[t + 4 s + 16 u], then the corners
+  const hipError_t le = hipGetLastError();
+  E.lp.lap(ends ? "triple_launch_end" : "triple_launch");
+  const int rc = le != hipSuccess ? set_err(ctx, SPG_E_HIP, std::string("layer triple: ") + hipGetErrorString(le))
+                                  : mbox_wait(ctx, P.seq, ev.data(), (int)ev.size());
+  if (rc) return rc;
+  E.lp.lap(ends ? "triple_wait_end" : "triple_wait");
+  // round j: F(X, s, u) over s, u in {0, 1} at X = 0, 2, 3
+  Fq ej[3];
+  for (int xi = 0; xi < 3; xi++) {
+    const int X = xi == 0 ? 0 : xi + 1;
+    ej[xi] = fq_add(fq_add(ev[X], ev[X + 4]), fq_add(ev[X + 16], ev[X + 20]));
+  }
+  const Fq rj = host_round(E, S, ej);
+  Fq L[4], M[4];
+  lagrange4(rj, L);
+  // round j + 1: t -> F(t, Y, 0) + F(t, Y, 1) at t = r_j, Y = 0, 2, 3
+  Fq ej1[3];
+  for (int yi = 0; yi < 3; yi++) {
+    const int Y = yi == 0 ? 0 : yi + 1;
+    Fq acc = fq_zero();
+    for (int a = 0; a < 4; a++) acc = fq_add(acc, fq_mul(L[a], fq_add(ev[a + 4 * Y], ev[a + 4 * Y + 16])));
+    ej1[yi] = acc;
+  }
+  const Fq rj1 = host_round(E, S, ej1);
+  lagrange4(rj1, M);
+  // round j + 2: (t, s) -> F(t, s, Z) at (r_j, r_j+1), Z = 0, 2, 3
+  Fq ej2[3];
+  for (int zi = 0; zi < 3; zi++) {
+    const int Z = zi == 0 ? 0 : zi + 1;
+    Fq acc = fq_zero();
+    for (int b = 0; b < 4; b++) {
+      Fq row = fq_zero();
+      for (int a = 0; a < 4; a++) row = fq_add(row, fq_mul(L[a], ev[a + 4 * b + 16 * Z]));
+      acc = fq_add(acc, fq_mul(M[b], row));
+    }
+    ej2[zi] = acc;
+  }
+  const Fq rj2 = host_round(E, S, ej2);
+  E.lp.lap("triple_host");
+  if (ends) {  // the 2 x 2 x 2 cube of every vector folded at (r_j, r_j+1, r_j+2): the layer's final claims
+    fin->resize(3 * nt);
+    auto fold3 = [&](size_t c0, size_t c1) {
+      for (size_t c = c0; c < c1; c++) {
+        const Fq* w = &ev[64 + 8 * c];  // corner m = 4 t + 2 s + u of vector c % 3 of triple c / 3
+        Fq q[4];
+        for (int j = 0; j < 4; j++) q[j] = fq_add(w[j], fq_mul(rj, fq_sub(w[j + 4], w[j])));
+        const Fq y0 = fq_add(q[0], fq_mul(rj1, fq_sub(q[2], q[0]))), y1 = fq_add(q[1], fq_mul(rj1, fq_sub(q[3], q[1])));
+        (*fin)[c] = fq_add(y0, fq_mul(rj2, fq_sub(y1, y0)));
+      }
+    };
+    // 7 products per vector: 500 for 24 circuits, ~8 us on one core; spread over the pool from 48 vectors
+    const size_t nv = 3 * nt;
+    const int K = nv >= 48 ? (int)std::min<size_t>(nv / 16, (size_t)pool().size() + 1) : 1;
+    if (K == 1)
+      fold3(0, nv);
+    else
+      pool().parallel_for(K, [&](int k) { fold3(nv * k / K, nv * (k + 1) / K); });
+    S.npend = 0;
+    E.lp.lap("triple_fin");
+    *done = true;
+    return 0;
+  }
+  S.npend = 3;
+  S.r[0] = rj;
+  S.r[1] = rj1;
+  S.r[2] = rj2;
+  return 0;
+}
+
+// Rounds while the vectors (2^log_len entries here) have more than one entry; `local` rounds sum over the ranks; with
+// close_after the layer's (or the shard's) final entries follow in `fin`. status: this rank already failed (skip mode).
+static int run_rounds(const LayerEnv& E, LayerState& S, size_t log_len, bool local, bool close_after, FqV* fin,
+                      int status) {
+  if (status) {  // the first local round's exchange carries the failure to every rank
+    if (!local || log_len == 0) return status;
+    Fq none[3] = {fq_zero(), fq_zero(), fq_zero()};
+    S.shared = true;
+    return comm_sum_fq(E.ctx, E.sh, status, none, 3);
+  }
+  const LayerKnobs& kn = layer_knobs();
+  const bool multi = kn.quad && !local && close_after;
+  while (log_len > 0) {
+    const int step = plan_step(kn, S.nt, S.ngroups, multi, log_len, S.npend);
+    if (step == 0) return set_err(E.ctx, SPG_E_ARG, "layer rounds: no launch plan");
+    bool done = false;
+    const int rc = step == 3   ? round_triple(E, S, log_len, fin, &done)
+                   : step == 2 ? round_pair(E, S, log_len, fin, &done)
+                               : round_single(E, S, log_len, local, close_after, fin, &done);
+    if (rc) return rc;
+    if (done) return 0;
+    log_len -= (size_t)step;
+  }
+  return close_after ? layer_close(E, S, *fin) : 0;
+}
+
+// A layer's descriptors and eq vector. The triples and coefficients ride in the eq-table launch's arguments when they
+// fit (no copy command on the stream), through page-locked staging otherwise; the eq table goes to cbuf[0]. `sharded`:
+// the local eq share, eq(rand)[W i' + r] = eq(rand_hi)[i'] * eq(rand_lo)[r], of hl entries. rc: skip mode.
+static int layer_setup(const LayerEnv& E, const std::vector<Triple>& tr, const FqV& coeffs, const FqV& rand,
+                       bool sharded, size_t hl, int rc) {
+  spg_ctx* ctx = E.ctx;
+  KBlob blob;  // 2.3 KB on the stack (contexts on other threads prove concurrently)
+  const size_t blob_bytes = E.tr_bytes + coeffs.size() * sizeof(Fq);
+  const bool in_args = blob_bytes <= sizeof(blob.w) && !getenv("SPG_LAYER_DESC_COPY");
+  if (in_args) {
+    memset(blob.w, 0, E.tr_bytes);
+    memcpy(blob.w, tr.data(), tr.size() * sizeof(Triple));
+    memcpy((uint8_t*)blob.w + E.tr_bytes, coeffs.data(), coeffs.size() * sizeof(Fq));
+    blob.nwords = (int)(blob_bytes / 4);
+  } else if (!rc) {  // free again here (the previous layer ended with a mailbox wait after its last launch)
+    uint8_t* st = (uint8_t*)pinned_get(ctx, blob_bytes + 64);
+    if (!st) {
+      rc = set_err(ctx, SPG_E_NOMEM, "layer staging");
+    } else {
+      memcpy(st, tr.data(), tr.size() * sizeof(Triple));
+      memcpy(st + E.tr_bytes, coeffs.data(), coeffs.size() * sizeof(Fq));
+      if (hipMemcpyAsync(E.ddesc, st, blob_bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
+        rc = set_err(ctx, SPG_E_HIP, "layer descriptors upload");
+    }
+  }
+  const KBlob* bp = in_args ? &blob : nullptr;
+  if (rc) return rc;  // skip mode: no device work this layer
+  if (!sharded) return dev_eq_table(ctx, rand.data(), (int)rand.size(), E.cbuf[0], bp, E.ddesc);
+  const size_t lgW = lg2(E.W), nh = rand.size() - lgW;
+  rc = dev_eq_table(ctx, rand.data(), (int)nh, E.cbuf[0], bp, E.ddesc);
+  Fq sc = fq_one();
+  for (size_t k = 0; k < lgW; k++)
+    sc = fq_mul(sc, ((E.rank >> (lgW - 1 - k)) & 1) ? rand[nh + k] : fq_sub(fq_one(), rand[nh + k]));
+  if (!rc) hipLaunchKernelGGL(k_scale, dim3(nblk(hl)), dim3(256), 0, ctx->stream, E.cbuf[0], hl, sc);
+  return rc;
+}
+
+// After a sharded layer's local rounds every vector has one entry per rank left (`mine`: this rank's, rank q's entry
+// is global index q): gathers them, and points the triples at the W gathered entries of each vector for the
+// replicated rounds. rc: skip mode. A failure of the exchange is known to every rank (S.shared).
+static int layer_gather(const LayerEnv& E, LayerState& S, std::vector<Triple>& tr, FqV& mine, int rc) {
+  spg_ctx* ctx = E.ctx;
+  hipStream_t s = ctx->stream;
+  const size_t nt = tr.size(), W = E.W;
+  mine.resize(3 * nt, fq_zero());
+  std::vector<uint8_t> all;
+  rc = comm_allgather(ctx, E.sh, rc, mine.data(), 3 * nt * sizeof(Fq), all);
+  if (rc) {
+    S.shared = true;
+    return rc;
+  }
+  const Fq* g = (const Fq*)all.data();
+  uint8_t* st = (uint8_t*)pinned_get(ctx, 3 * nt * W * sizeof(Fq) + E.tr_bytes + 64);
+  if (!st) return set_err(ctx, SPG_E_NOMEM, "gather staging");
+  Fq* hv = (Fq*)(st + E.tr_bytes);
+  for (size_t c = 0; c < nt; c++)
+    for (size_t k = 0; k < 3; k++)
+      for (size_t q = 0; q < W; q++) hv[(3 * c + k) * W + q] = g[q * 3 * nt + 3 * c + k];
+  Fq* gbuf = E.gbuf;
+  for (size_t c = 0; c < nt; c++) {
+    const bool own_c = tr[c].C != nullptr;
+    tr[c] = {gbuf + 3 * c * W, gbuf + (3 * c + 1) * W, own_c ? gbuf + (3 * c + 2) * W : nullptr};
+  }
+  memcpy(st, tr.data(), nt * sizeof(Triple));
+  if (hipMemcpyAsync(E.ddesc, st, nt * sizeof(Triple), hipMemcpyHostToDevice, s) != hipSuccess ||
+      hipMemcpyAsync(gbuf, hv, 3 * nt * W * sizeof(Fq), hipMemcpyHostToDevice, s) != hipSuccess ||
+      // the product circuits' shared eq vector (every product triple gathered the same entries)
+      (E.nc && hipMemcpyAsync(E.cbuf[S.cur], gbuf + 2 * W, W * sizeof(Fq), hipMemcpyDeviceToDevice, s) != hipSuccess))
+    return set_err(ctx, SPG_E_HIP, "gathered entries upload");
+  return 0;
+}
+
+// The layer's final claims fin = (A[0], B[0], C[0]) per triple into the proof and the transcript (ndotp dot-product
+// circuits after the nc product circuits); returns challenge_r_layer
+static Fq layer_finals(const LayerEnv& E, LayerState& S, const FqV& fin, size_t ndotp, BatchedProofP* out) {
+  const size_t nc = E.nc;
+  Tr& t = E.t;
+  for (size_t c = 0; c < nc; c++) {
+    S.proof.left.push_back(fin[3 * c]);
+    S.proof.right.push_back(fin[3 * c + 1]);
+  }
+  for (size_t c = 0; c < nc; c++) {
+    t.scalar("claim_prod_left", S.proof.left[c]);
+    t.scalar("claim_prod_right", S.proof.right[c]);
+  }
+  if (ndotp) {
+    for (size_t k = 0; k < ndotp; k++)
+      for (int i = 0; i < 3; i++) out->dotp[i].push_back(fin[3 * (nc + k) + i]);
+    for (size_t k = 0; k < ndotp; k++) {
+      t.scalar("claim_dotp_left", out->dotp[0][k]);
+      t.scalar("claim_dotp_right", out->dotp[1][k]);
+      t.scalar("claim_dotp_weight", out->dotp[2][k]);
+    }
+  }
+  return t.challenge("challenge_r_layer");
+}
+
+// ProductCircuitEvalProofBatched::prove (product_tree.rs:271-396) over the nc product circuits of `ts` (M leaves
+// each, claims = their ProductCircuit::evaluate) and, at layer 0, the dot-product circuits `dotp` (three device
+// vectors of M/2 entries each, folded in place) with claims `dotp_claims`. Every launch applies the folds pending
+// from the launch before it and evaluates one to three rounds (layer.hpp).
 // A layer whose vectors are sharded (global half length >= W) runs its first lg(half / W) rounds on the local
 // shares (pairs (i, i + len) stay on one rank while W | len; the round's (e0, e2, e3) are summed over the ranks),
 // then gathers the W remaining entries of every vector (k_layer_close without the fold when no round ran) and
 // runs the last lg W rounds replicated, exactly like an unsharded layer of that length.
-static int batched_prove_fused(spg_ctx* ctx, const TreeSh& ts, size_t nc, size_t M, FqV claims,
-                               const std::vector<Triple>& dotp, const FqV& dotp_claims, Tr& t, BatchedProofP* out,
-                               FqV* rand_out, const Shard& sh) {
-  hipStream_t s = ctx->stream;
+static int batched_prove(spg_ctx* ctx, const TreeSh& ts, size_t nc, size_t M, FqV claims,
+                         const std::vector<Triple>& dotp, const FqV& dotp_claims, Tr& t, BatchedProofP* out,
+                         FqV* rand_out, const Shard& sh) {
   const size_t L = lg2(M), W = (size_t)ts.W, lgW = lg2(W), m = ts.m, lgm = lg2(m);
   auto off = [](size_t MM, size_t k) { return 2 * MM - 2 * (MM >> k); };
   const size_t nt_max = nc + dotp.size();
   if (3 * nt_max + 1 > kMboxScalars) return set_err(ctx, SPG_E_ARG, "batched_prove: too many circuits for the mailbox");
   const size_t half_max = std::max<size_t>(M / 2 / W, 1);  // the longest eq vector held here
-  Fq* cbuf[2] = {(Fq*)ws_get(ctx, kWsC, std::max(half_max, W) * sizeof(Fq) + 64),
-                 (Fq*)ws_get(ctx, kWsC2, std::max(half_max, W) * sizeof(Fq) + 64)};
-  // triples, then their coefficients, in one buffer (one upload per layer)
-  const size_t tr_bytes = (nt_max * sizeof(Triple) + 63) & ~(size_t)63;
-  uint8_t* ddesc = (uint8_t*)ws_get(ctx, kWsTriples, tr_bytes + nt_max * sizeof(Fq) + 64);
-  Fq* part = (Fq*)ws_get(ctx, kWsPart, 3 * 2048 * sizeof(Fq) + 64);  // K <= 2048 workgroups per round
-  Fq* gbuf = W > 1 ? (Fq*)ws_get(ctx, kWsGather, 3 * nt_max * W * sizeof(Fq) + 64) : nullptr;
-  if (!cbuf[0] || !cbuf[1] || !ddesc || !part || (W > 1 && !gbuf)) return set_err(ctx, SPG_E_NOMEM, "batched_prove");
-  const Triple* dtr = (const Triple*)ddesc;
-  const Fq* dcoef = (const Fq*)(ddesc + tr_bytes);
-  FqV rand;
   Laps lp;
   lp.title = "ProductCircuitEvalProofBatched::prove";
+  LayerEnv E{ctx, t, sh, lp, nc};
+  E.cbuf[0] = (Fq*)ws_get(ctx, kWsC, std::max(half_max, W) * sizeof(Fq) + 64);
+  E.cbuf[1] = (Fq*)ws_get(ctx, kWsC2, std::max(half_max, W) * sizeof(Fq) + 64);
+  // triples, then their coefficients, in one buffer (one upload per layer)
+  E.tr_bytes = (nt_max * sizeof(Triple) + 63) & ~(size_t)63;
+  E.ddesc = (uint8_t*)ws_get(ctx, kWsTriples, E.tr_bytes + nt_max * sizeof(Fq) + 64);
+  E.part = (Fq*)ws_get(ctx, kWsPart, 3 * 2048 * sizeof(Fq) + 64);  // K <= 2048 workgroups per round
+  E.gbuf = W > 1 ? (Fq*)ws_get(ctx, kWsGather, 3 * nt_max * W * sizeof(Fq) + 64) : nullptr;
+  E.W = W;
+  E.rank = ts.r;
+  if (!E.cbuf[0] || !E.cbuf[1] || !E.ddesc || !E.part || (W > 1 && !E.gbuf))
+    return set_err(ctx, SPG_E_NOMEM, "batched_prove");
+  FqV rand;
   // W > 1: a failure on this rank alone (allocation, HIP, mailbox) is not returned at once -- the peers would wait
   // in the next exchange. The rank stops working (`fail`, skip mode) but keeps the exchange sequence, whose
   // shape depends only on public sizes, until its status reaches every rank: in the next sharded round's
   // exchange, or in the status exchange that ends the function. A failure learned in an exchange is known to
-  // every rank (`shared`) and returns at once.
+  // every rank (LayerState::shared) and returns at once.
   int fail = 0;
-  bool shared = false;
   for (size_t layer = L; layer-- > 0;) {
     const size_t half = M >> (layer + 1);  // |left| = |right| = |C| (global)
     // where this layer's vectors live: local shares (sharded), the replicated top tree, or the whole tree
@@ -761,7 +1193,6 @@ static int batched_prove_fused(spg_ctx* ctx, const TreeSh& ts, size_t nc, size_t
     const size_t hl = sharded ? half / W : half;  // entries of each vector held here
     int rc = fail;
     if (!rc && sharded && failpoint(ctx, "spark_layer")) rc = set_err(ctx, SPG_E_HIP, "failpoint spark_layer");
-    int cur = 0;  // the buffer holding the shared eq vector C
     const bool with_dotp = layer == 0 && !dotp.empty();
     std::vector<Triple> tr;
     for (size_t c = 0; c < nc; c++) {
@@ -773,710 +1204,42 @@ static int batched_prove_fused(spg_ctx* ctx, const TreeSh& ts, size_t nc, size_t
       for (auto& d : dotp) tr.push_back(d);
     }
     FqV coeffs = t.challenges("rand_coeffs_next_layer", claims.size());
-    Fq e = fq_zero();
-    for (size_t i = 0; i < claims.size(); i++) e = fq_add(e, fq_mul(claims[i], coeffs[i]));
-    // the layer's descriptors and coefficients ride in the eq-table launch's arguments when they fit (no copy
-    // command on the stream), through page-locked staging otherwise
-    KBlob blob;  // 2.3 KB on the stack (contexts on other threads prove concurrently)
-    const size_t blob_bytes = tr_bytes + coeffs.size() * sizeof(Fq);
-    const bool in_args = blob_bytes <= sizeof(blob.w) && !getenv("SPG_LAYER_DESC_COPY");
-    if (in_args) {
-      memset(blob.w, 0, tr_bytes);
-      memcpy(blob.w, tr.data(), tr.size() * sizeof(Triple));
-      memcpy((uint8_t*)blob.w + tr_bytes, coeffs.data(), coeffs.size() * sizeof(Fq));
-      blob.nwords = (int)(blob_bytes / 4);
-    } else if (!rc) {  // free again here (the previous layer ended with a mailbox wait after its last launch)
-      uint8_t* st = (uint8_t*)pinned_get(ctx, blob_bytes + 64);
-      if (!st) {
-        rc = set_err(ctx, SPG_E_NOMEM, "layer staging");
-      } else {
-        memcpy(st, tr.data(), tr.size() * sizeof(Triple));
-        memcpy(st + tr_bytes, coeffs.data(), coeffs.size() * sizeof(Fq));
-        if (hipMemcpyAsync(ddesc, st, blob_bytes, hipMemcpyHostToDevice, s) != hipSuccess)
-          rc = set_err(ctx, SPG_E_HIP, "layer descriptors upload");
-      }
-    }
-    const KBlob* bp = in_args ? &blob : nullptr;
-    if (rc) {
-      // skip mode: no device work this layer
-    } else if (sharded) {  // local eq share: eq(rand)[W i' + r] = eq(rand_hi)[i'] * eq(rand_lo)[r]
-      const size_t nh = rand.size() - lgW;
-      rc = dev_eq_table(ctx, rand.data(), (int)nh, cbuf[0], bp, ddesc);
-      Fq sc = fq_one();
-      for (size_t k = 0; k < lgW; k++)
-        sc = fq_mul(sc, ((ts.r >> (lgW - 1 - k)) & 1) ? rand[nh + k] : fq_sub(fq_one(), rand[nh + k]));
-      if (!rc) hipLaunchKernelGGL(k_scale, dim3(nblk(hl)), dim3(256), 0, s, cbuf[0], hl, sc);
-    } else {
-      rc = dev_eq_table(ctx, rand.data(), (int)rand.size(), cbuf[0], bp, ddesc);
-    }
+    LayerState S;
+    S.nt = tr.size();
+    S.ngroups = (nc ? 1 : 0) + (tr.size() - nc);
+    for (size_t i = 0; i < claims.size(); i++) S.e = fq_add(S.e, fq_mul(claims[i], coeffs[i]));
+    rc = layer_setup(E, tr, coeffs, rand, sharded, hl, rc);
     if (rc && W == 1) return rc;
     lp.lap("layer_setup");
-    LayerProofP lpf;
-    FqV r_prod;
-    bool pending = false;  // a bound_poly_var_top with r_pend not yet applied
-    Fq r_pend = fq_zero();
-    // after a paired launch (k_layer_pair): a second pending fold, with r_pend2 (bound after r_pend); only a paired
-    // launch applies two, and once a layer's rounds pair up they pair up to the layer's end
-    bool pend2 = false;
-    Fq r_pend2 = fq_zero();
-    // after a tripled launch (k_layer_triple): a third, r_pend3; only a triple follows it
-    bool pend3 = false;
-    Fq r_pend3 = fq_zero();
-    // A[0], B[0], C[0] of every triple (after the pending fold, if any), by mailbox
-    auto close = [&](FqV& fin) -> int {
-      if (pend2 || pend3) return set_err(ctx, SPG_E_ARG, "layer close after a paired round");  // (the last pair posts its ends)
-      fin.resize(3 * tr.size());
-      KScope ks(ctx, "spark_layer_close");
-      const uint32_t seq = ++ctx->mbox_seq;
-      hipLaunchKernelGGL(k_layer_close, dim3(1), dim3(256), 0, s, dtr, (int)tr.size(), pending ? 1 : 0, r_pend,
-                         cbuf[cur], ctx->d_mbox, seq);
-      SPG_HIP(ctx, hipGetLastError());
-      pending = false;
-      return mbox_wait(ctx, seq, fin.data(), (int)fin.size());
-    };
-    // the host half of a round: UniPoly from (e0, e2, e3), transcript, r_j
-    auto host_round = [&](const Fq ev[3]) -> Fq {
-      Fq evals[4] = {ev[0], fq_sub(e, ev[0]), ev[1], ev[2]};
-      FqV poly = uni_from_evals3(evals);
-      append_unipoly(t, poly);
-      Fq r_j = t.challenge("challenge_nextround");
-      r_prod.push_back(r_j);
-      e = uni_eval(poly, r_j);
-      lpf.polys.push_back({poly[0], poly[2], poly[3]});
-      return r_j;
-    };
-    // the remaining log_len rounds of the layer in one persistent launch (layer.hpp, k_layer_persist): the host
-    // answers each posted round through the downbox instead of launching the next one
-    auto run_persist = [&](size_t log_len, bool close_after, FqV* fin) -> int {
-      const int R = (int)log_len;
-      const size_t nt = tr.size();
-      static const size_t max_wgs = getenv("SPG_PERSIST_WGS") ? (size_t)atol(getenv("SPG_PERSIST_WGS")) : 64;
-      const unsigned K = (unsigned)std::max<size_t>(1, std::min<size_t>(((nt << (R - 1)) * 4 + 255) / 256, max_wgs));
-      const bool ends = close_after && 3 + 6 * nt <= kMboxScalars;
-      PersistArgs A;
-      A.tr = dtr;
-      A.coeff = dcoef;
-      A.nt = (int)nt;
-      A.rounds = R;
-      A.do_fold = pending ? 1 : 0;
-      A.r = r_pend;
-      A.cb[0] = cbuf[0];
-      A.cb[1] = cbuf[1];
-      A.cur = cur;
-      A.partials = part;
-      A.counter = ctx->d_counter;
-      A.mb = ctx->d_mbox;
-      A.seq0 = ctx->mbox_seq + 1;
-      A.down = ctx->d_down;
-      A.ends = ends ? 1 : 0;
-      A.timeout = 2000000000ULL;  // 20 s of the 100 MHz wall clock
-      static const bool relay_on = !getenv("SPG_PERSIST_RELAY") || atoi(getenv("SPG_PERSIST_RELAY")) != 0;
-      A.relay = nullptr;
-      if (relay_on && K > 1) {
-        A.relay = (uint32_t*)ws_get(ctx, kWsRelay, 64);
-        if (!A.relay) return set_err(ctx, SPG_E_NOMEM, "layer relay");
-      }
-      ctx->mbox_seq += (uint32_t)R;
-      ctx->down[0] = 0;  // clear a previous launch's abort word
-      {
-        KScope ks(ctx, "spark_layer_persist");
-        hipLaunchKernelGGL(k_layer_persist<256>, dim3(K), dim3(256), 0, s, A);
-      }
-      const hipError_t le = hipGetLastError();
-      if (le != hipSuccess) return set_err(ctx, SPG_E_HIP, std::string("layer rounds: ") + hipGetErrorString(le));
-      for (int k = 0; k < R; k++) {
-        const bool last_round = k == R - 1;
-        FqV ev(last_round && ends ? 3 + 6 * nt : 3);
-        const int rc2 = mbox_wait(ctx, A.seq0 + (uint32_t)k, ev.data(), (int)ev.size());
-        if (rc2) {
-          if (!last_round) {
-            down_post(ctx, kDownAbort, fq_zero());  // every workgroup leaves its wait
-            // ... and has left before the next launch clears the abort word: the stream drains here
-            (void)hipStreamSynchronize(s);
-            (void)hipGetLastError();
-          }
-          return rc2;
-        }
-        lp.lap("round_eval_wait");
-        if (pending) cur ^= 1;
-        r_pend = host_round(ev.data());
-        pending = true;
-        lp.lap("round_host");
-        if (!last_round) {
-          down_post(ctx, A.seq0 + (uint32_t)k, r_pend);
-        } else if (ends) {  // bound_poly_var_top of the length-2 vectors, on the host
-          fin->resize(3 * nt);
-          for (size_t c = 0; c < 3 * nt; c++) {
-            const Fq lo = ev[3 + 2 * c], hi = ev[4 + 2 * c];
-            (*fin)[c] = fq_add(lo, fq_mul(r_pend, fq_sub(hi, lo)));
-          }
-          pending = false;
-          return 0;
-        }
-      }
-      return close_after ? close(*fin) : 0;
-    };
-    // rounds while the vectors (2 len entries here) have len >= 1; `local` rounds sum over the ranks; with
-    // close_after the layer's (or the shard's) final entries follow in `fin`
-    static const bool ends_on = !getenv("SPG_LAYER_ENDS") || atoi(getenv("SPG_LAYER_ENDS")) != 0;
-    // off by default: same-box A/B (profiles/r04_ab_persist_fuse_bcomb.txt) measured 21.5 ms per prove with the
-    // resident launches against 18.9 ms without
-    static const bool persist_on = getenv("SPG_LAYER_PERSIST") && atoi(getenv("SPG_LAYER_PERSIST")) != 0;
-    auto run_rounds = [&](size_t log_len, bool local, bool close_after, FqV* fin, int status) -> int {
-      if (status) {  // skip mode: the first local round's exchange carries the failure to every rank
-        if (!local || log_len == 0) return status;
-        Fq none[3] = {fq_zero(), fq_zero(), fq_zero()};
-        shared = true;
-        return comm_sum_fq(ctx, sh, status, none, 3);
-      }
-      static const bool quad = !getenv("SPG_LAYER_QUAD") || atoi(getenv("SPG_LAYER_QUAD")) != 0;
-      static const size_t wide_min = getenv("SPG_WIDE_MIN") ? (size_t)atol(getenv("SPG_WIDE_MIN")) : ((size_t)1 << 19);
-      static const size_t persist_max = getenv("SPG_PERSIST_MAX") ? (size_t)atol(getenv("SPG_PERSIST_MAX")) : 4096;
-      static const bool pair_on = !getenv("SPG_LAYER_PAIR") || atoi(getenv("SPG_LAYER_PAIR")) != 0;
-      static const size_t pair_max = getenv("SPG_PAIR_MAX") ? (size_t)atol(getenv("SPG_PAIR_MAX")) : 4096;
-      static const bool triple_on = !getenv("SPG_LAYER_TRIPLE") || atoi(getenv("SPG_LAYER_TRIPLE")) != 0;
-      // elements (a wave each, four per workgroup) of a tripled launch: 64 partials per workgroup in `part`
-      static const size_t triple_max =
-          std::min<size_t>(getenv("SPG_TRIPLE_MAX") ? (size_t)atol(getenv("SPG_TRIPLE_MAX")) : 384, 384);
-      // relative wall of a launched single / paired / tripled round trip, for the launch plan below
-      static const std::vector<int> step_cost = [] {
-        std::vector<int> c = {18, 25, 30};
-        if (const char* e = getenv("SPG_STEP_COSTS")) sscanf(e, "%d,%d,%d", &c[0], &c[1], &c[2]);
-        return c;
-      }();
-      const size_t ngroups = (nc ? 1 : 0) + (tr.size() - nc);  // product circuits share one thread per index
-      const size_t nt_all = tr.size();
-      const bool multi = quad && !local && close_after && !(persist_on && ctx->nranks == 1);
-      // two rounds in one launch (k_layer_pair): small rounds of an unsharded layer, every element's 16 lanes within
-      // pair_max elements, the last pair's corners within the mailbox; three (k_layer_triple): a wave per element
-      // within triple_max elements, the last triple's corners within the mailbox
-      // a paired launch of E elements stores 16 partials per workgroup of BSp / 16 elements into `part` (3 x 2048
-      // scalars): 16 E / BSp * 16 <= 6144, so E <= 6144 with 256-thread workgroups and E <= 1536 with 64-thread ones
-      // (SPG_PAIR_BS = 64)
-      static const int pair_bs = getenv("SPG_PAIR_BS") ? atoi(getenv("SPG_PAIR_BS")) : 0;  // 64: more workgroups
-      const size_t pair_part_cap = pair_bs == 64 ? 1536 : 6144;
-      auto pair_ok = [&](size_t k) {
-        return pair_on && multi && k >= 2 && (nt_all << (k - 2)) <= std::min<size_t>(pair_max, pair_part_cap) &&
-               15 + 12 * nt_all <= kMboxScalars && ngroups * ((size_t)1 << (k - 1)) < wide_min;
-      };
-      auto triple_ok = [&](size_t k) {
-        return triple_on && multi && k >= 3 && (nt_all << (k - 3)) <= triple_max && 64 + 24 * nt_all <= kMboxScalars &&
-               ngroups * ((size_t)1 << (k - 1)) < wide_min;
-      };
-      // the launch plan: single rounds first, then pairs, then triples (a pair leaves two pending folds, which only
-      // a pair or a triple applies; a triple three, which only a triple applies), the cheapest by step_cost.
-      // Returns the rounds of the first launch from k rounds left in state mode (0: free, 1: after a pair, 2: after a
-      // triple), 0 when none finishes the layer.
-      auto plan = [&](size_t k, int mode) -> int {
-        const int inf = 1 << 28;
-        std::vector<std::array<int, 3>> best(k + 1), first(k + 1);
-        for (size_t j = 0; j <= k; j++)
-          for (int md = 0; md < 3; md++) {
-            int b = j == 0 ? 0 : inf, f = 0;
-            if (j >= 1 && md == 0 && best[j - 1][0] < inf && step_cost[0] + best[j - 1][0] < b)
-              b = step_cost[0] + best[j - 1][0], f = 1;
-            if (md <= 1 && pair_ok(j) && best[j - 2][1] < inf && step_cost[1] + best[j - 2][1] < b)
-              b = step_cost[1] + best[j - 2][1], f = 2;
-            if (triple_ok(j) && best[j - 3][2] < inf && step_cost[2] + best[j - 3][2] < b)
-              b = step_cost[2] + best[j - 3][2], f = 3;
-            best[j][md] = b;
-            first[j][md] = f;
-          }
-        return first[k][mode];
-      };
-      auto lagrange4 = [](const Fq& r, Fq L[4]) {  // the cubic Lagrange basis on 0..3 at r
-        static const Fq inv2 = fq_inv(fq_from_u64(2)), inv6 = fq_inv(fq_from_u64(6));
-        const Fq a0 = r, a1 = fq_sub(r, fq_one()), a2 = fq_sub(a1, fq_one()), a3 = fq_sub(a2, fq_one());
-        const Fq a01 = fq_mul(a0, a1), a23 = fq_mul(a2, a3);
-        L[0] = fq_neg(fq_mul(fq_mul(a1, a23), inv6));
-        L[1] = fq_mul(fq_mul(a0, a23), inv2);
-        L[2] = fq_neg(fq_mul(fq_mul(a01, a3), inv2));
-        L[3] = fq_mul(fq_mul(a01, a2), inv6);
-      };
-      while (log_len > 0) {
-        const int step = plan(log_len, pend3 ? 2 : (pend2 ? 1 : 0));
-        if (step == 0) return set_err(ctx, SPG_E_ARG, "layer rounds: no launch plan");
-        if (step == 3) {
-          const int lgj = (int)log_len - 1;  // round j's half length 2^lgj; h = 2^(lgj - 2) elements per vector
-          log_len -= 3;
-          const size_t nt = tr.size(), h = (size_t)1 << (lgj - 2), E = nt * h;
-          const int BSt = E <= 1 ? 64 : 256;
-          const unsigned Kt = (unsigned)((E + BSt / 64 - 1) / (BSt / 64));
-          const bool ends = log_len == 0;  // the layer's last triple posts every vector's 2 x 2 x 2 corners
-          const int nf = pend3 ? 3 : (pend2 ? 2 : (pending ? 1 : 0));
-          TripleArgs P;
-          P.tr = dtr;
-          P.coeff = dcoef;
-          P.nt = (int)nt;
-          P.log_len = lgj;
-          P.nf = nf;
-          P.r1 = r_pend;
-          P.r2 = r_pend2;
-          P.r3 = r_pend3;
-          P.r12 = fq_mul(r_pend, r_pend2);
-          P.r13 = fq_mul(r_pend, r_pend3);
-          P.r23 = fq_mul(r_pend2, r_pend3);
-          P.r123 = fq_mul(P.r12, r_pend3);
-          P.cin = cbuf[cur];
-          P.cout = cbuf[cur ^ 1];
-          P.partials = part;
-          P.counter = ctx->d_counter;
-          P.mb = ctx->d_mbox;
-          P.seq = ++ctx->mbox_seq;
-          P.ends = ends ? 1 : 0;
-          P.probe = nullptr;
-          {
-            // algorithmic bytes: per distinct vector and element, 8 corners from 8 2^nf entries, written back when folded
-            const double per = 32.0 * (8.0 * (double)(1 << nf) + (nf ? 8.0 : 0.0));
-            // Fq products per element: the 24 corners folded (2^nf - 1 each), 64 points x 3
-            KScope ks(ctx, "spark_layer_triple", per * (double)h * (double)(2 * nt + ngroups), 0.0,
-                      (double)nt * (double)h * (192.0 + 24.0 * (double)((1 << nf) - 1)));
-            if (BSt == 64)
-              hipLaunchKernelGGL(k_layer_triple<64>, dim3(Kt), dim3(64), 0, s, P);
-            else
-              hipLaunchKernelGGL(k_layer_triple<256>, dim3(Kt), dim3(256), 0, s, P);
-          }
-          if (nf) cur ^= 1;
-          FqV ev(64 + (ends ? 24 * nt : 0));  // F(t, s, u) = ev[t + 4 s + 16 u], then the corners
-          const hipError_t le = hipGetLastError();
-          lp.lap(ends ? "triple_launch_end" : "triple_launch");
-          const int rc2 = le != hipSuccess ? set_err(ctx, SPG_E_HIP, std::string("layer triple: ") + hipGetErrorString(le))
-                                           : mbox_wait(ctx, P.seq, ev.data(), (int)ev.size());
-          if (rc2) return rc2;
-          lp.lap(ends ? "triple_wait_end" : "triple_wait");
-          // round j: F(X, s, u) over s, u in {0, 1} at X = 0, 2, 3
-          Fq ej[3];
-          for (int xi = 0; xi < 3; xi++) {
-            const int X = xi == 0 ? 0 : xi + 1;
-            ej[xi] = fq_add(fq_add(ev[X], ev[X + 4]), fq_add(ev[X + 16], ev[X + 20]));
-          }
-          const Fq rj = host_round(ej);
-          Fq L[4], M[4];
-          lagrange4(rj, L);
-          // round j + 1: t -> F(t, Y, 0) + F(t, Y, 1) at t = r_j, Y = 0, 2, 3
-          Fq ej1[3];
-          for (int yi = 0; yi < 3; yi++) {
-            const int Y = yi == 0 ? 0 : yi + 1;
-            Fq acc = fq_zero();
-            for (int a = 0; a < 4; a++) acc = fq_add(acc, fq_mul(L[a], fq_add(ev[a + 4 * Y], ev[a + 4 * Y + 16])));
-            ej1[yi] = acc;
-          }
-          const Fq rj1 = host_round(ej1);
-          lagrange4(rj1, M);
-          // round j + 2: (t, s) -> F(t, s, Z) at (r_j, r_j+1), Z = 0, 2, 3
-          Fq ej2[3];
-          for (int zi = 0; zi < 3; zi++) {
-            const int Z = zi == 0 ? 0 : zi + 1;
-            Fq acc = fq_zero();
-            for (int b = 0; b < 4; b++) {
-              Fq row = fq_zero();
-              for (int a = 0; a < 4; a++) row = fq_add(row, fq_mul(L[a], ev[a + 4 * b + 16 * Z]));
-              acc = fq_add(acc, fq_mul(M[b], row));
-            }
-            ej2[zi] = acc;
-          }
-          const Fq rj2 = host_round(ej2);
-          lp.lap("triple_host");
-          if (ends) {  // the 2 x 2 x 2 cube of every vector folded at (r_j, r_j+1, r_j+2): the layer's final claims
-            fin->resize(3 * nt);
-            auto fold3 = [&](size_t c0, size_t c1) {
-              for (size_t c = c0; c < c1; c++) {
-                const Fq* w = &ev[64 + 8 * c];  // corner m = 4 t + 2 s + u of vector c % 3 of triple c / 3
-                Fq q[4];
-                for (int j = 0; j < 4; j++) q[j] = fq_add(w[j], fq_mul(rj, fq_sub(w[j + 4], w[j])));
-                const Fq y0 = fq_add(q[0], fq_mul(rj1, fq_sub(q[2], q[0]))),
-                         y1 = fq_add(q[1], fq_mul(rj1, fq_sub(q[3], q[1])));
-                (*fin)[c] = fq_add(y0, fq_mul(rj2, fq_sub(y1, y0)));
-              }
-            };
-            // 7 products per vector: 500 for 24 circuits, ~8 us on one core; spread over the pool from 48 vectors
-            const size_t nv = 3 * nt;
-            const int K = nv >= 48 ? (int)std::min<size_t>(nv / 16, (size_t)pool().size() + 1) : 1;
-            if (K == 1)
-              fold3(0, nv);
-            else
-              pool().parallel_for(K, [&](int k) { fold3(nv * k / K, nv * (k + 1) / K); });
-            pending = pend2 = pend3 = false;
-            lp.lap("triple_fin");
-            return 0;
-          }
-          pending = pend2 = pend3 = true;
-          r_pend = rj;
-          r_pend2 = rj1;
-          r_pend3 = rj2;
-          continue;
-        }
-        if (step == 2) {
-          if (pend3) return set_err(ctx, SPG_E_ARG, "paired layer round after a tripled one");
-          const int lgj = (int)log_len - 1;  // round j's half length 2^lgj; round j + 1's 2^(lgj - 1)
-          log_len -= 2;
-          const size_t nt = tr.size(), h = (size_t)1 << (lgj - 1), lanes = 16 * nt * h;
-          const int BSp = lanes <= 64 || pair_bs == 64 ? 64 : 256;
-          const unsigned Kp = (unsigned)((lanes + BSp - 1) / BSp);
-          const bool ends = log_len == 0;  // the layer's last pair posts every vector's 2 x 2 corners
-          const int nf = pend2 ? 2 : (pending ? 1 : 0);
-          PairArgs P;
-          P.tr = dtr;
-          P.coeff = dcoef;
-          P.nt = (int)nt;
-          P.log_len = lgj;
-          P.nf = nf;
-          P.r1 = r_pend;
-          P.r2 = r_pend2;
-          P.r12 = fq_mul(r_pend, r_pend2);
-          P.cin = cbuf[cur];
-          P.cout = cbuf[cur ^ 1];
-          P.partials = part;
-          P.counter = ctx->d_counter;
-          P.mb = ctx->d_mbox;
-          P.seq = ++ctx->mbox_seq;
-          P.ends = ends ? 1 : 0;
-          P.probe = nullptr;
-          {
-            // algorithmic bytes: per distinct vector and element, 4 corners from 4 2^nf entries, written back when folded
-            const double per = 32.0 * (4.0 * (double)(1 << nf) + (nf ? 4.0 : 0.0));
-            // Fq products per element: the corners folded (12 x 3 with two pending folds, 12 with one), 15 points x 3
-            KScope ks(ctx, "spark_layer_pair", per * (double)h * (double)(2 * nt + ngroups), 0.0,
-                      (double)nt * (double)h * (45.0 + (nf == 2 ? 36.0 : nf == 1 ? 12.0 : 0.0)));
-            if (BSp == 64)
-              hipLaunchKernelGGL(k_layer_pair<64>, dim3(Kp), dim3(64), 0, s, P);
-            else
-              hipLaunchKernelGGL(k_layer_pair<256>, dim3(Kp), dim3(256), 0, s, P);
-          }
-          if (nf) cur ^= 1;
-          FqV ev(15 + (ends ? 12 * nt : 0));
-          const hipError_t le = hipGetLastError();
-          lp.lap(ends ? "pair_launch_end" : "pair_launch");
-          const int rc2 = le != hipSuccess ? set_err(ctx, SPG_E_HIP, std::string("layer pair: ") + hipGetErrorString(le))
-                                           : mbox_wait(ctx, P.seq, ev.data(), (int)ev.size());
-          if (rc2) return rc2;
-          lp.lap(ends ? "pair_wait_end" : "pair_wait");
-          // round j: F(X, 0) + F(X, 1) at X = 0, 2, 3
-          const Fq ej[3] = {fq_add(ev[0], ev[12]), fq_add(ev[2], ev[13]), fq_add(ev[3], ev[14])};
-          const Fq rj = host_round(ej);
-          // round j + 1: the cubics t -> F(t, Y) through t = 0..3 (lines Y = 0, 2, 3) at t = r_j
-          Fq L[4];
-          lagrange4(rj, L);
-          Fq ej1[3];
-          for (int y = 0; y < 3; y++) {
-            Fq acc = fq_zero();
-            for (int k = 0; k < 4; k++) acc = fq_add(acc, fq_mul(L[k], ev[4 * y + k]));
-            ej1[y] = acc;
-          }
-          const Fq rj1 = host_round(ej1);
-          lp.lap("pair_host");
-          if (ends) {  // the 2 x 2 cube of every vector folded at (r_j, r_j+1): the layer's final claims
-            fin->resize(3 * nt);
-            for (size_t c = 0; c < 3 * nt; c++) {
-              const Fq* w = &ev[15 + 4 * c];  // p00, p01, p10, p11 of vector c % 3 of triple c / 3
-              const Fq q0 = fq_add(w[0], fq_mul(rj, fq_sub(w[2], w[0]))), q1 = fq_add(w[1], fq_mul(rj, fq_sub(w[3], w[1])));
-              (*fin)[c] = fq_add(q0, fq_mul(rj1, fq_sub(q1, q0)));
-            }
-            pending = pend2 = false;
-            lp.lap("pair_fin");
-            return 0;
-          }
-          pending = pend2 = true;
-          r_pend = rj;
-          r_pend2 = rj1;
-          continue;
-        }
-        if (pend2 || pend3) return set_err(ctx, SPG_E_ARG, "single layer round after a paired one");
-        // every remaining round is a quad round of at most persist_max elements: one persistent launch for them all
-        // (one process per GPU only: processes sharing a GPU time-slice its queues, and a resident loop could then
-        // wait out its timeout while descheduled)
-        if (persist_on && quad && !local && ctx->nranks == 1 && (tr.size() << (log_len - 1)) <= persist_max &&
-            ngroups * ((size_t)1 << (log_len - 1)) < wide_min)
-          return run_persist(log_len, close_after, fin);
-        log_len--;
-        const size_t len = (size_t)1 << log_len;
-        unsigned K;
-        int BS;
-        // algorithmic HBM bytes of the round: per distinct vector (A, B of every triple; the shared C once; each
-        // dot-product circuit's own C) and index, 2 entries read, or with the pending fold 4 read + 2 written
-        const double layer_bytes = (pending ? 192.0 : 64.0) * (double)len * (double)(2 * tr.size() + ngroups);
-        if (ngroups * len >= wide_min) {  // throughput form for rounds that fill the chip
-          K = (unsigned)std::min<size_t>((ngroups * len + 255) / 256, 2048);
-          // Fq products per index: per product circuit k A B at 3 points from the folded A, B (3 + 2 + 4 folds), the
-          // shared C folded once (2) and multiplied in (3); a dot-product circuit 14 (its own C folded too)
-          const double fqm_w = (double)len * ((pending ? 2.0 : 0.0) + 3.0 + (double)nc * (pending ? 9.0 : 5.0) +
-                                              (double)(tr.size() - nc) * (pending ? 14.0 : 8.0));
-          KScope ks(ctx, "spark_layer_round", layer_bytes, 0.0, fqm_w);
-          hipLaunchKernelGGL(k_layer_round_wide<256>, dim3(K), dim3(256), 0, s, dtr, dcoef, (int)nc, (int)tr.size(),
-                             (int)log_len, pending ? 1 : 0, r_pend, cbuf[cur], cbuf[cur ^ 1], part, ctx->d_counter,
-                             ctx->d_mbox, ++ctx->mbox_seq);
-        } else if (quad) {  // a quad per element, about one element per quad
-          const size_t Wd = tr.size() * len;
-          BS = Wd <= 16 ? 64 : 256;
-          K = (unsigned)std::min<size_t>((Wd * 4 + BS - 1) / BS, 2048);
-        } else {
-          layer_grid(tr.size() * len, &K, &BS);
-        }
-        // the layer's last round in one workgroup also posts every vector's two entries: the host then folds the
-        // final claims with the round's challenge, and no close launch (another round trip) follows
-        const bool ends = close_after && log_len == 0 && quad && K == 1 && 3 + 6 * tr.size() <= kMboxScalars &&
-                          ngroups * len < wide_min && ends_on;
-        if (ngroups * len < wide_min) {
-          // Fq products per element: lanes 0..2 fold their vector's two entries (6) and form k A B C at their point (9)
-          KScope ks(ctx, "spark_layer_round", layer_bytes, 0.0, (double)tr.size() * (double)len * (pending ? 15.0 : 9.0));
-          const int nt = (int)tr.size(), lg = (int)log_len, df = pending ? 1 : 0;
-          const uint32_t seq = ++ctx->mbox_seq;
-          if (quad && BS == 64)
-            hipLaunchKernelGGL(k_layer_round_q<64>, dim3(K), dim3(64), 0, s, dtr, dcoef, nt, lg, df, r_pend, cbuf[cur],
-                               cbuf[cur ^ 1], part, ctx->d_counter, ctx->d_mbox, seq, nullptr, ends ? 1 : 0);
-          else if (quad)
-            hipLaunchKernelGGL(k_layer_round_q<256>, dim3(K), dim3(256), 0, s, dtr, dcoef, nt, lg, df, r_pend,
-                               cbuf[cur], cbuf[cur ^ 1], part, ctx->d_counter, ctx->d_mbox, seq, nullptr, ends ? 1 : 0);
-          else if (BS == 64)
-            hipLaunchKernelGGL(k_layer_round<64>, dim3(K), dim3(64), 0, s, dtr, dcoef, nt, lg, df, r_pend, cbuf[cur],
-                               cbuf[cur ^ 1], part, ctx->d_counter, ctx->d_mbox, seq, nullptr);
-          else
-            hipLaunchKernelGGL(k_layer_round<256>, dim3(K), dim3(256), 0, s, dtr, dcoef, nt, lg, df, r_pend, cbuf[cur],
-                               cbuf[cur ^ 1], part, ctx->d_counter, ctx->d_mbox, seq, nullptr);
-        }
-        if (pending) cur ^= 1;
-        FqV ev(ends ? 3 + 6 * tr.size() : 3);
-        const hipError_t le = hipGetLastError();
-        int rc2 = le != hipSuccess ? set_err(ctx, SPG_E_HIP, std::string("layer round: ") + hipGetErrorString(le))
-                                   : mbox_wait(ctx, ctx->mbox_seq, ev.data(), (int)ev.size());
-        if (local) {
-          rc2 = comm_sum_fq(ctx, sh, rc2, ev.data(), 3);
-          if (rc2) shared = true;
-        }
-        if (rc2) return rc2;
-        lp.lap("round_eval_wait");
-        r_pend = host_round(ev.data());
-        pending = true;
-        lp.lap("round_host");
-        if (ends) {  // bound_poly_var_top of the length-2 vectors, on the host
-          fin->resize(3 * tr.size());
-          for (size_t c = 0; c < 3 * tr.size(); c++) {
-            const Fq lo = ev[3 + 2 * c], hi = ev[4 + 2 * c];
-            (*fin)[c] = fq_add(lo, fq_mul(r_pend, fq_sub(hi, lo)));
-          }
-          pending = false;
-          return 0;
-        }
-      }
-      return close_after ? close(*fin) : 0;
-    };
     FqV fin;
     if (sharded) {
-      // gather: every vector has one entry per rank left; rank q's entry is global index q
       FqV mine;
-      rc = run_rounds(lg2(hl), true, true, &mine, rc);
-      if (rc && shared) return rc;
-      mine.resize(3 * tr.size(), fq_zero());
-      std::vector<uint8_t> all;
-      rc = comm_allgather(ctx, sh, rc, mine.data(), 3 * tr.size() * sizeof(Fq), all);
-      if (rc) return rc;  // known to every rank
-      const Fq* g = (const Fq*)all.data();
-      const size_t nt = tr.size();
-      uint8_t* st = (uint8_t*)pinned_get(ctx, 3 * nt * W * sizeof(Fq) + tr_bytes + 64);
-      if (!st) {
-        rc = set_err(ctx, SPG_E_NOMEM, "gather staging");
-      } else {
-        Fq* hv = (Fq*)(st + tr_bytes);
-        for (size_t c = 0; c < nt; c++)
-          for (size_t k = 0; k < 3; k++)
-            for (size_t q = 0; q < W; q++) hv[(3 * c + k) * W + q] = g[q * 3 * nt + 3 * c + k];
-        for (size_t c = 0; c < nt; c++) {
-          const bool own_c = tr[c].C != nullptr;
-          tr[c] = {gbuf + 3 * c * W, gbuf + (3 * c + 1) * W, own_c ? gbuf + (3 * c + 2) * W : nullptr};
-        }
-        memcpy(st, tr.data(), nt * sizeof(Triple));
-        if (hipMemcpyAsync(ddesc, st, nt * sizeof(Triple), hipMemcpyHostToDevice, s) != hipSuccess ||
-            hipMemcpyAsync(gbuf, hv, 3 * nt * W * sizeof(Fq), hipMemcpyHostToDevice, s) != hipSuccess ||
-            // the product circuits' shared eq vector (every product triple gathered the same entries)
-            (nc && hipMemcpyAsync(cbuf[cur], gbuf + 2 * W, W * sizeof(Fq), hipMemcpyDeviceToDevice, s) != hipSuccess))
-          rc = set_err(ctx, SPG_E_HIP, "gathered entries upload");
-      }
-      rc = run_rounds(lgW, false, true, &fin, rc);
+      rc = run_rounds(E, S, lg2(hl), true, true, &mine, rc);
+      if (rc && S.shared) return rc;
+      rc = layer_gather(E, S, tr, mine, rc);
+      if (rc && S.shared) return rc;
+      rc = run_rounds(E, S, lgW, false, true, &fin, rc);
     } else {
-      rc = run_rounds(lg2(hl), false, true, &fin, rc);
+      rc = run_rounds(E, S, lg2(hl), false, true, &fin, rc);
     }
-    if (rc && (W == 1 || shared)) return rc;
+    if (rc && (W == 1 || S.shared)) return rc;
     if (rc) {  // this rank alone: skip mode until an exchange carries it
       fail = rc;
       continue;
     }
-    for (size_t c = 0; c < nc; c++) {
-      lpf.left.push_back(fin[3 * c]);
-      lpf.right.push_back(fin[3 * c + 1]);
-    }
-    for (size_t c = 0; c < nc; c++) {
-      t.scalar("claim_prod_left", lpf.left[c]);
-      t.scalar("claim_prod_right", lpf.right[c]);
-    }
-    if (with_dotp) {
-      for (size_t k = 0; k < dotp.size(); k++)
-        for (int i = 0; i < 3; i++) out->dotp[i].push_back(fin[3 * (nc + k) + i]);
-      for (size_t k = 0; k < dotp.size(); k++) {
-        t.scalar("claim_dotp_left", out->dotp[0][k]);
-        t.scalar("claim_dotp_right", out->dotp[1][k]);
-        t.scalar("claim_dotp_weight", out->dotp[2][k]);
-      }
-    }
-    Fq r_layer = t.challenge("challenge_r_layer");
+    const Fq r_layer = layer_finals(E, S, fin, with_dotp ? dotp.size() : 0, out);
+    const LayerProofP& lpf = S.proof;
     claims.assign(nc, fq_zero());
     for (size_t c = 0; c < nc; c++) claims[c] = fq_add(lpf.left[c], fq_mul(r_layer, fq_sub(lpf.right[c], lpf.left[c])));
     rand.assign(1, r_layer);
-    rand.insert(rand.end(), r_prod.begin(), r_prod.end());
-    out->layers.push_back(std::move(lpf));
+    rand.insert(rand.end(), S.r_prod.begin(), S.r_prod.end());
+    out->layers.push_back(std::move(S.proof));
     lp.lap("layer_finals");
   }
   if (W > 1) {  // every rank's status, so a failure still pending here fails every rank alike
     std::vector<uint8_t> none;
     const int rc = comm_allgather(ctx, sh, fail, nullptr, 0, none);
     if (rc) return rc;
-  }
-  lp.print();
-  *rand_out = rand;
-  return 0;
-}
-
-// ProductCircuitEvalProofBatched::prove (product_tree.rs:271-396) over the nc product circuits of `tree`
-// (M leaves each, claims = their ProductCircuit::evaluate) and, at layer 0, the dot-product circuits
-// `dotp` (three device vectors of M/2 entries each, folded in place) with claims `dotp_claims`.
-static int batched_prove(spg_ctx* ctx, const TreeSh& ts, size_t nc, size_t M, FqV claims,
-                         const std::vector<Triple>& dotp, const FqV& dotp_claims, Tr& t, BatchedProofP* out,
-                         FqV* rand_out, const Shard& sh) {
-  static const bool fused = !getenv("SPG_LAYER_FUSED") || atoi(getenv("SPG_LAYER_FUSED")) != 0;
-  if (fused || ts.W > 1) return batched_prove_fused(ctx, ts, nc, M, claims, dotp, dotp_claims, t, out, rand_out, sh);
-  Fq* tree = ts.loc;
-  hipStream_t s = ctx->stream;
-  const size_t L = lg2(M), stride = 2 * M;
-  auto off = [&](size_t k) { return 2 * M - 2 * (M >> k); };
-  const size_t nt_max = nc + dotp.size();
-  Fq* dC = (Fq*)ws_get(ctx, kWsC, (M / 2) * sizeof(Fq) + 64);
-  Triple* dtr = (Triple*)ws_get(ctx, kWsTriples, nt_max * sizeof(Triple) + 64);
-  Fq* dcoef = (Fq*)ws_get(ctx, kWsCoeff, nt_max * sizeof(Fq) + 64);
-  Fq** dptr = (Fq**)ws_get(ctx, kWsFoldPtr, (2 * nc + 1 + 3 * dotp.size()) * sizeof(Fq*) + 64);
-  Fq* part = (Fq*)ws_get(ctx, kWsPart, 3 * std::max<size_t>(2048, nt_max) * sizeof(Fq) + 64);
-  Fq* dfin = (Fq*)ws_get(ctx, kWsFinals, 3 * nt_max * sizeof(Fq) + 64);
-  if (!dC || !dtr || !dcoef || !dptr || !part || !dfin) return set_err(ctx, SPG_E_NOMEM, "batched_prove");
-  FqV rand;
-  Laps lp;
-  lp.title = "ProductCircuitEvalProofBatched::prove";
-  for (size_t layer = L; layer-- > 0;) {
-    const size_t half = M >> (layer + 1);  // |left| = |right| = |C|
-    const size_t rounds = lg2(half);
-    int rc = eq_table(ctx, rand, dC);
-    if (rc) return rc;
-    const bool with_dotp = layer == 0 && !dotp.empty();
-    std::vector<Triple> tr;
-    std::vector<Fq*> fold;
-    for (size_t c = 0; c < nc; c++) {
-      Fq* v = tree + c * stride + off(layer);
-      tr.push_back({v, v + half, dC});
-      fold.push_back(v);
-      fold.push_back(v + half);
-    }
-    fold.push_back(dC);
-    if (with_dotp) {
-      claims.insert(claims.end(), dotp_claims.begin(), dotp_claims.end());
-      for (auto& d : dotp) {
-        tr.push_back(d);
-        fold.push_back(d.A);
-        fold.push_back(d.B);
-        fold.push_back(d.C);
-      }
-    }
-    FqV coeffs = t.challenges("rand_coeffs_next_layer", claims.size());
-    Fq e = fq_zero();
-    for (size_t i = 0; i < claims.size(); i++) e = fq_add(e, fq_mul(claims[i], coeffs[i]));
-    {  // descriptors up through page-locked staging (a pageable source blocks the host for a staging blit);
-       // the staging is free again here: the previous layer ended with a synchronising download
-      const size_t b1 = tr.size() * sizeof(Triple), b2 = coeffs.size() * sizeof(Fq), b3 = fold.size() * sizeof(Fq*);
-      uint8_t* st = (uint8_t*)pinned_get(ctx, b1 + b2 + b3 + 64);
-      if (!st) return set_err(ctx, SPG_E_NOMEM, "layer staging");
-      memcpy(st, tr.data(), b1);
-      memcpy(st + b1, coeffs.data(), b2);
-      memcpy(st + b1 + b2, fold.data(), b3);
-      SPG_HIP(ctx, hipMemcpyAsync(dtr, st, b1, hipMemcpyHostToDevice, s));
-      SPG_HIP(ctx, hipMemcpyAsync(dcoef, st + b1, b2, hipMemcpyHostToDevice, s));
-      SPG_HIP(ctx, hipMemcpyAsync(dptr, st + b1 + b2, b3, hipMemcpyHostToDevice, s));
-    }
-    lp.lap("layer_setup");
-    LayerProofP lpf;
-    FqV r_prod;
-    size_t log_len = rounds;
-    bool pending = false;  // a bound_poly_var_top with r_pend not yet launched
-    Fq r_pend = fq_zero();
-    static const bool tiny_ok = !getenv("SPG_SPARK_TINY") || atoi(getenv("SPG_SPARK_TINY")) != 0;
-    static const size_t tiny_max = getenv("SPG_SPARK_TINY_MAX") ? (size_t)atoi(getenv("SPG_SPARK_TINY_MAX")) : 2048;
-    for (size_t j = 0; j < rounds; j++) {
-      log_len--;
-      const size_t len = (size_t)1 << log_len;
-      const unsigned nbx = (unsigned)std::min<size_t>(nblk(len), std::max<size_t>(1, 2048 / tr.size()));
-      const bool tiny = tiny_ok && tr.size() * len <= tiny_max;
-      if (pending && !tiny) {
-        KScope ks(ctx, "spark_fold", 96.0 * fold.size() * (2 * len));
-        hipLaunchKernelGGL(k_fold_many, dim3(nblk(fold.size() * 2 * len)), dim3(256), 0, s, dptr, fold.size(),
-                           (int)log_len + 1, r_pend);
-        pending = false;
-      }
-      if (tiny) {  // the pending fold and this round's evaluations in one workgroup
-        KScope ks(ctx, "spark_layer_tiny", 192.0 * tr.size() * len + (pending ? 192.0 * fold.size() * len : 0.0));
-        hipLaunchKernelGGL(k_layer_tiny, dim3(1), dim3(1024), 0, s, dtr, dcoef, (int)tr.size(), (int)log_len, dptr,
-                           (int)fold.size(), pending ? 1 : 0, r_pend, ctx->d_mbox, ++ctx->mbox_seq);
-        pending = false;
-      } else {
-        KScope ks(ctx, "spark_layer_eval", 192.0 * tr.size() * len);
-        hipLaunchKernelGGL(k_layer_eval, dim3(nbx, (unsigned)tr.size()), dim3(256), 0, s, dtr, dcoef, len, part,
-                           ctx->d_counter, ctx->d_mbox, ++ctx->mbox_seq);
-      }
-      Fq ev[3];
-      rc = eval_reduce_finish(ctx, ev);
-      if (rc) return rc;
-      lp.lap("round_eval_wait");
-      Fq evals[4] = {ev[0], fq_sub(e, ev[0]), ev[1], ev[2]};
-      FqV poly = uni_from_evals3(evals);
-      append_unipoly(t, poly);
-      Fq r_j = t.challenge("challenge_nextround");
-      r_prod.push_back(r_j);
-      lp.lap("round_host");
-      pending = true;  // bound_poly_var_top with r_j: launched with (or before) the next round's evaluation
-      r_pend = r_j;
-      SPG_HIP(ctx, hipGetLastError());
-      e = uni_eval(poly, r_j);
-      lpf.polys.push_back({poly[0], poly[2], poly[3]});
-      lp.lap("round_fold_launch");
-    }
-    if (pending) {  // the last round's fold
-      KScope ks(ctx, "spark_fold", 96.0 * fold.size());
-      hipLaunchKernelGGL(k_fold_many, dim3(nblk(fold.size())), dim3(256), 0, s, dptr, fold.size(), 0, r_pend);
-      pending = false;
-    }
-    // final claims: A[0], B[0] (and C[0] for the dot-product circuits)
-    hipLaunchKernelGGL(k_finals, dim3(nblk(tr.size())), dim3(256), 0, s, dtr, tr.size(), dfin);
-    FqV fin(3 * tr.size());
-    rc = d2h_fq(ctx, dfin, fin.data(), fin.size());
-    if (rc) return rc;
-    for (size_t c = 0; c < nc; c++) {
-      lpf.left.push_back(fin[3 * c]);
-      lpf.right.push_back(fin[3 * c + 1]);
-    }
-    for (size_t c = 0; c < nc; c++) {
-      t.scalar("claim_prod_left", lpf.left[c]);
-      t.scalar("claim_prod_right", lpf.right[c]);
-    }
-    if (with_dotp) {
-      for (size_t k = 0; k < dotp.size(); k++)
-        for (int i = 0; i < 3; i++) out->dotp[i].push_back(fin[3 * (nc + k) + i]);
-      for (size_t k = 0; k < dotp.size(); k++) {
-        t.scalar("claim_dotp_left", out->dotp[0][k]);
-        t.scalar("claim_dotp_right", out->dotp[1][k]);
-        t.scalar("claim_dotp_weight", out->dotp[2][k]);
-      }
-    }
-    Fq r_layer = t.challenge("challenge_r_layer");
-    claims.assign(nc, fq_zero());
-    for (size_t c = 0; c < nc; c++) claims[c] = fq_add(lpf.left[c], fq_mul(r_layer, fq_sub(lpf.right[c], lpf.left[c])));
-    rand.assign(1, r_layer);
-    rand.insert(rand.end(), r_prod.begin(), r_prod.end());
-    out->layers.push_back(std::move(lpf));
-    lp.lap("layer_finals");
   }
   lp.print();
   *rand_out = rand;
@@ -1724,7 +1487,7 @@ namespace spg {
 //                      product tree; ProductCircuit::compute_layer pairs i with i + len/2, which keeps the low
 //                      lg W bits, so every level stays local down to one entry per rank; those W entries are
 //                      allgathered and the top lg W levels built on every rank (TreeSh)
-//   layer sumchecks    batched_prove_fused: local rounds with (e0, e2, e3) summed over the ranks, then a gather
+//   layer sumchecks    batched_prove: local rounds with (e0, e2, e3) summed over the ranks, then a gather
 //   hash-layer evals   contiguous shares of each dot product, summed (seg_dots)
 //   PolyEvalProofs     L.Z rows split, partial vectors summed; Bullet replicated (poly_eval_prove)
 // A circuit set of fewer than 2W leaves (or W not a power of two) stays whole on every rank. Every collective

@@ -211,7 +211,7 @@ def _tree_worker(rank, world, port, q):
 
 @pytest.mark.parametrize("world", [2, 4])
 def test_interleaved_product_tree_shards(world):
-    """the sharded SPARK layout (spark.hip spark_prove_core / batched_prove_fused): interleaved local product
+    """the sharded SPARK layout (spark.hip spark_prove_core / batched_prove): interleaved local product
     trees meet the global tree's W-entry level, and local layer rounds summed over gloo ranks + gathered tail
     rounds give the unsharded round polynomials and final claims"""
     import random

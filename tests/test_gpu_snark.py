@@ -91,11 +91,8 @@ ROUND_FORMS = {
     "eval_one_thread": {"SPG_SC_QUAD_MAX": "0"},
     "eval_quad_everywhere": {"SPG_SC_QUAD_MAX": str(1 << 40)},
     "fold_launches": {"SPG_SC_FUSE": "0"},
-    "layer_persist": {"SPG_LAYER_PERSIST": "1"},
-    "layer_persist_host_polls": {"SPG_LAYER_PERSIST": "1", "SPG_PERSIST_RELAY": "0"},
-    "layer_persist_one_wg": {"SPG_LAYER_PERSIST": "1", "SPG_PERSIST_WGS": "1", "SPG_PERSIST_MAX": str(1 << 20)},
-    "layer_persist_wide": {"SPG_LAYER_PERSIST": "1", "SPG_PERSIST_WGS": "256", "SPG_PERSIST_MAX": str(1 << 20)},
-    "layer_persist_no_ends": {"SPG_LAYER_PERSIST": "1", "SPG_LAYER_ENDS": "0"},
+    # single rounds whose last one posts no entries: the layer's final claims come from the close launch (k_layer_close)
+    "layer_close_launch": {"SPG_LAYER_ENDS": "0", "SPG_LAYER_PAIR": "0", "SPG_LAYER_TRIPLE": "0"},
     "z_fill_in_order": {"SPG_Z_SIDE": "0"},
     "z_fill_after_round_0": {"SPG_Z_AFTER": "0"},
     "z_fill_at_phase2": {"SPG_Z_AFTER": "100000"},
@@ -117,7 +114,6 @@ ROUND_FORMS = {
     "tree_levels_per_launch": {"SPG_TREE_TOP": "0"},
     "tree_one_launch": {"SPG_TREE_TOP": str(1 << 40)},
     "delta_bucket_msm": {"SPG_DELTA_COMB": "0"},
-    "bullet_comb_rolled": {"SPG_BCOMB_ROLL": "1"},
     "dotlog_cy_beta_in_order": {"SPG_DOTLOG_EARLY": "0"},
     "delta_scalars_from_host": {"SPG_DELTA_DEV": "0"},
     "spmv_and_z_fill_untiled": {"SPG_SPMV_TILED": "0", "SPG_Z_TILED": "0"},
@@ -138,9 +134,9 @@ def test_round_forms(form):
     """the sumcheck rounds in every launch form, against the golden proof's bytes (the default mixes them by round
     size; a fresh process reads the switches): R1CSProof evaluations one thread per point (SPG_SC_QUAD_MAX=0) or a
     quad per point everywhere; phase-1 and phase-2 folds as launches of their own (SPG_SC_FUSE=0) instead of inside the next
-    round's evaluation; SPARK layer rounds in the resident launch (SPG_LAYER_PERSIST=1; the default launches each
-    round), with workgroup 0 relaying the host's answer or every workgroup polling the host, with one workgroup over
-    every round, with 256 workgroups, and without posting the layer's entries; the R1CS Z fill in stream order
+    round's evaluation; SPARK layer rounds one per launch with the layer's final claims from the close launch
+    (SPG_LAYER_ENDS=0 without pairs and triples; by default the layer's last launch posts its entries); the R1CS Z
+    fill in stream order
     (SPG_Z_SIDE=0) or on the second stream after phase-1 round 0 or only at phase 2 (SPG_Z_AFTER); one eq table
     per launch (SPG_EQ_MULTI=0); device witness parts copied instead of read in place (SPG_WIT_IN_PLACE=0); SPARK layer
     rounds one per launch (SPG_LAYER_PAIR=0) instead of two per launch where they are small, paired rounds over 64-thread
