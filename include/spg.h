@@ -169,6 +169,50 @@ int spg_r1cs_multiply_vec_block(spg_ctx* ctx, const struct spg_r1cs_inst* inst, 
                                 const size_t* num_proofs, size_t max_num_proofs, const size_t* num_inputs,
                                 size_t max_num_inputs, size_t num_witness_secs, const uint64_t* z_mont, spg_pqx** Az,
                                 spg_pqx** Bz, spg_pqx** Cz);
+/* -- memory checking and the grand-product argument on caller vectors (csrc/prodc.hip): what SparseMatPolyEvalProof
+ * runs between its commitments (Layers::new, ProductLayerProof::prove; src/sparse_mlpoly.rs:689-736, 1105-1356), one
+ * call at a time. Single-rank: spg_set_comm does not shard these. */
+struct spg_transcript;
+/* Layers::build_hash_layer (src/sparse_mlpoly.rs:612-687): hash(addr, val, ts) = ts r_hash^2 + val r_hash + addr -
+ * r_multiset. eval_table, audit_ts: num_mem_cells scalars; addrs[k], derefs[k], read_ts[k]: num_ops scalars each,
+ * k < n (n >= 1; both sizes powers of two). init[i] = hash(i, eval_table[i], 0), audit[i] = hash(i, eval_table[i],
+ * audit_ts[i]), reads[k][i] = hash(addrs[k][i], derefs[k][i], read_ts[k][i]), writes[k][i] the same with ts + 1.
+ * Outputs are new spg_bufs the caller frees: *init, *audit (num_mem_cells), reads[k], writes[k] (num_ops). */
+int spg_hash_layer(spg_ctx* ctx, const spg_buf* eval_table, const spg_buf* const* addrs, const spg_buf* const* derefs,
+                   const spg_buf* const* read_ts, size_t n, const spg_buf* audit_ts, const uint64_t* r_hash_mont,
+                   const uint64_t* r_multiset_mont, spg_buf** init, spg_buf** reads, spg_buf** writes, spg_buf** audit);
+/* nc product circuits of M leaves each in one tree allocation. spg_prodc_new = ProductCircuit::new
+ * (src/product_tree.rs:18-58) for nc polynomials of one power-of-two length M >= 2 (the inputs are left unchanged);
+ * spg_prodc_evaluate = evaluate (:58-65) of every circuit (nc scalars); spg_prodc_layer = left_vec[layer],
+ * right_vec[layer] of circuit c (M >> (layer + 1) scalars each, layer < log2 M), for inspection. */
+typedef struct spg_prodc spg_prodc;
+int spg_prodc_new(spg_ctx* ctx, const spg_buf* const* polys, size_t nc, spg_prodc** out);
+int spg_prodc_free(spg_ctx* ctx, spg_prodc* p);
+int spg_prodc_shape(const spg_prodc* p, size_t* nc, size_t* num_leaves);
+int spg_prodc_evaluate(spg_ctx* ctx, const spg_prodc* p, uint64_t* out_mont);
+int spg_prodc_layer(spg_ctx* ctx, const spg_prodc* p, size_t c, size_t layer, uint64_t* left_mont,
+                    uint64_t* right_mont);
+/* SumcheckInstanceProof::prove_cubic_batched (src/sumcheck.rs:264-434) with comb A B C: n_par pairs (A_par[i],
+ * B_par[i]) sharing C_par with coefficients coeffs[0 .. n_par), then n_seq triples with coeffs[n_par ..); all of one
+ * length 2^k, k >= num_rounds. Every vector is bound in place as in the reference: afterwards it holds its 2^(k -
+ * num_rounds) bound values and has that length (spg_buf_len). polys: num_rounds x 3 (CompressedUniPoly), r:
+ * num_rounds, claims_par: A finals (n_par), B finals (n_par), C_par[0]; claims_seq: A, B, C finals (n_seq each). With
+ * n_par = 0, C_par may be NULL (else it is bound too and claims_par receives C_par[0]). The rounds are the SPARK
+ * prover's layer launches, whose results come back through one mailbox page: 3 (n_par + n_seq) 2^(k - num_rounds) + 1
+ * scalars must fit it (2047), else SPG_E_ARG. */
+int spg_prove_cubic_batched(spg_ctx* ctx, const uint64_t* claim_mont, size_t num_rounds, spg_buf* const* A_par,
+                            spg_buf* const* B_par, size_t n_par, spg_buf* C_par, spg_buf* const* A_seq,
+                            spg_buf* const* B_seq, spg_buf* const* C_seq, size_t n_seq, const uint64_t* coeffs_mont,
+                            struct spg_transcript* t, uint64_t* polys_mont, uint64_t* r_mont, uint64_t* claims_par_mont,
+                            uint64_t* claims_seq_mont);
+/* ProductCircuitEvalProofBatched::prove (src/product_tree.rs:260-396) over `prod` and nd dot-product circuits
+ * (dotp[3k .. 3k+2] = left, right, weight of circuit k, M/2 scalars each, bound in place: one scalar each afterwards).
+ * proof: the reference's bincode bytes of the struct; *len = their number, also when cap is too small (SPG_E_ARG,
+ * nothing is run and prod stays usable); rand: log2(M) scalars. 3 (nc + nd) + 1 scalars must fit the mailbox (2047).
+ * `prod` is consumed: its layers hold bound values afterwards, as the reference's &mut circuits do; only
+ * spg_prodc_free is defined on it after this call. */
+int spg_prodc_prove_batched(spg_ctx* ctx, spg_prodc* prod, spg_buf* const* dotp, size_t nd, struct spg_transcript* t,
+                            uint8_t* proof, size_t cap, size_t* len, uint64_t* rand_mont, size_t* rand_len);
 
 /* ---- generators ------------------------------------------------------------------------------
  * MultiCommitGens::new(n, label) (src/commitments.rs:15-33): n+1 points from SHAKE256(label ||

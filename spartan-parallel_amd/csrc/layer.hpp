@@ -7,12 +7,10 @@
 #include "lds.hpp"
 #include "qsum.hpp"
 #include "cube.hpp"
+#include "prodc.hpp"
 
 namespace spg {
 
-struct Triple {
-  Fq *A, *B, *C;
-};
 __device__ __forceinline__ void block_sum3_sp(Fq& v0, Fq& v1, Fq& v2) {
   __shared__ uint32_t sh[3][soa_words<Fq, 256>()];  // component-major: no bank conflicts
   int t = threadIdx.x;

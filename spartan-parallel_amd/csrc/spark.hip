@@ -566,24 +566,47 @@ static void append_unipoly(Tr& t, const FqV& c) {
   t.msg("poly", "UniPoly_end");
 }
 
-struct LayerProofP {
-  std::vector<FqV> polys;  // CompressedUniPoly per round
-  FqV left, right;
-};
-struct BatchedProofP {  // ProductCircuitEvalProofBatched
-  std::vector<LayerProofP> layers;
-  FqV dotp[3];
-  void ser(Writer& w) const {
-    w.u64(layers.size());
-    for (auto& l : layers) {
-      w.u64(l.polys.size());
-      for (auto& p : l.polys) w.fqs(p);
-      w.fqs(l.left);
-      w.fqs(l.right);
-    }
-    for (int i = 0; i < 3; i++) w.fqs(dotp[i]);
+int tree_build(spg_ctx* ctx, Fq* tree, size_t nc, size_t M, Fq* tops) {
+  hipStream_t s = ctx->stream;
+  KScope ks(ctx, "spark_product_tree", 96.0 * nc * M / 2);
+  // levels of more than kTopHalf products per circuit: one grid-wide launch each; the rest and the tops: k_tree_top
+  static const size_t kTopHalf = getenv("SPG_TREE_TOP") ? (size_t)atol(getenv("SPG_TREE_TOP")) : 1024;
+  size_t k = 0;
+  for (; k + 1 < lg2(M) && (M >> (k + 1)) > kTopHalf; k++) {
+    size_t ok = 2 * M - 2 * (M >> k), ok1 = 2 * M - 2 * (M >> (k + 1));
+    hipLaunchKernelGGL(k_tree_level, dim3(nblk(nc * (M >> (k + 1)))), dim3(256), 0, s, tree, nc, 2 * M, ok, ok1,
+                       (int)lg2(M >> (k + 1)));
   }
-};
+  if (kTopHalf) {
+    hipLaunchKernelGGL(k_tree_top, dim3((unsigned)nc), dim3(256), 0, s, tree, 2 * M, (int)lg2(M), (int)k, tops);
+  } else {
+    for (; k + 1 < lg2(M); k++) {
+      size_t ok = 2 * M - 2 * (M >> k), ok1 = 2 * M - 2 * (M >> (k + 1));
+      hipLaunchKernelGGL(k_tree_level, dim3(nblk(nc * (M >> (k + 1)))), dim3(256), 0, s, tree, nc, 2 * M, ok, ok1,
+                         (int)lg2(M >> (k + 1)));
+    }
+    const size_t top = 2 * M - 4;  // v_{L-1}
+    hipLaunchKernelGGL(k_tops, dim3(nblk(nc)), dim3(256), 0, s, tree, nc, 2 * M, top, tops);
+  }
+  SPG_HIP(ctx, hipGetLastError());
+  return 0;
+}
+
+int dotp_evaluate(spg_ctx* ctx, const std::vector<Triple>& dotp, size_t n, Fq* out) {
+  const size_t nd = dotp.size();
+  if (!nd) return 0;
+  Triple* dtr = (Triple*)ws_get(ctx, kWsTriples, 3 * nd * sizeof(Triple) + 64);
+  unsigned nb = (unsigned)std::min<size_t>(nblk(n), std::max<size_t>(1, 2048 / nd));
+  Fq* part = (Fq*)ws_get(ctx, kWsSegPart, nd * nb * sizeof(Fq) + 64);
+  Fq* dres = (Fq*)ws_get(ctx, kWsSeg, nd * sizeof(Fq) + 64);
+  if (!dtr || !part || !dres) return set_err(ctx, SPG_E_NOMEM, "dotp eval");
+  SPG_HIP(ctx, hipMemcpyAsync(dtr, dotp.data(), nd * sizeof(Triple), hipMemcpyHostToDevice, ctx->stream));
+  KScope ks(ctx, "spark_dotp_eval", 96.0 * nd * n);
+  hipLaunchKernelGGL(k_dot3, dim3(nb, (unsigned)nd), dim3(256), 0, ctx->stream, dtr, n, part);
+  hipLaunchKernelGGL(k_sum_seg, dim3((unsigned)nd), dim3(256), 0, ctx->stream, part, (int)nb, dres);
+  SPG_HIP(ctx, hipGetLastError());
+  return d2h_fq(ctx, dres, out, nd);
+}
 
 // workgroups and block size of a fused layer round over W = nt * len elements: one workgroup up to kOneWgMax
 // elements (no ticket), else about kEltPerThread elements per thread over 256-thread workgroups
@@ -601,17 +624,6 @@ static void layer_grid(size_t W, unsigned* K, int* BS) {
     *K = (unsigned)std::min<size_t>((W + 256 * ept - 1) / (256 * ept), 2048);
   }
 }
-
-// A set of nc product circuits (M leaves each), possibly sharded over the W ranks of a proof (see "sharded
-// proof" at spark_prove_core): rank r holds leaves i = W i' + r as a local tree of m = M / W leaves (levels of
-// >= 2 entries at loc + c 2m, the usual back-to-back layout), and every rank holds the global levels of <= W
-// entries as a replicated "top" tree (circuit c at top + c 2W, W entries first). W == 1: loc is the whole tree.
-struct TreeSh {
-  Fq* loc = nullptr;
-  size_t m = 0;
-  Fq* top = nullptr;
-  int W = 1, r = 0;
-};
 
 // ------------------------------------------------------------------------------------ the layer prover
 // ProductCircuitEvalProofBatched::prove (product_tree.rs:271-396): batched_prove below walks the layers; per layer
@@ -1149,6 +1161,23 @@ static Fq layer_finals(const LayerEnv& E, LayerState& S, const FqV& fin, size_t 
   return t.challenge("challenge_r_layer");
 }
 
+// the workspace of a prove's layers: nt_max triples, eq vectors of up to c_len entries, trees sharded over W ranks
+static int layer_env_init(LayerEnv& E, size_t nt_max, size_t c_len, size_t W, int rank) {
+  spg_ctx* ctx = E.ctx;
+  E.cbuf[0] = (Fq*)ws_get(ctx, kWsC, std::max(c_len, W) * sizeof(Fq) + 64);
+  E.cbuf[1] = (Fq*)ws_get(ctx, kWsC2, std::max(c_len, W) * sizeof(Fq) + 64);
+  // triples, then their coefficients, in one buffer (one upload per layer)
+  E.tr_bytes = (nt_max * sizeof(Triple) + 63) & ~(size_t)63;
+  E.ddesc = (uint8_t*)ws_get(ctx, kWsTriples, E.tr_bytes + nt_max * sizeof(Fq) + 64);
+  E.part = (Fq*)ws_get(ctx, kWsPart, 3 * 2048 * sizeof(Fq) + 64);  // K <= 2048 workgroups per round
+  E.gbuf = W > 1 ? (Fq*)ws_get(ctx, kWsGather, 3 * nt_max * W * sizeof(Fq) + 64) : nullptr;
+  E.W = W;
+  E.rank = rank;
+  if (!E.cbuf[0] || !E.cbuf[1] || !E.ddesc || !E.part || (W > 1 && !E.gbuf))
+    return set_err(ctx, SPG_E_NOMEM, "batched_prove");
+  return 0;
+}
+
 // ProductCircuitEvalProofBatched::prove (product_tree.rs:271-396) over the nc product circuits of `ts` (M leaves
 // each, claims = their ProductCircuit::evaluate) and, at layer 0, the dot-product circuits `dotp` (three device
 // vectors of M/2 entries each, folded in place) with claims `dotp_claims`. Every launch applies the folds pending
@@ -1157,9 +1186,8 @@ static Fq layer_finals(const LayerEnv& E, LayerState& S, const FqV& fin, size_t 
 // shares (pairs (i, i + len) stay on one rank while W | len; the round's (e0, e2, e3) are summed over the ranks),
 // then gathers the W remaining entries of every vector (k_layer_close without the fold when no round ran) and
 // runs the last lg W rounds replicated, exactly like an unsharded layer of that length.
-static int batched_prove(spg_ctx* ctx, const TreeSh& ts, size_t nc, size_t M, FqV claims,
-                         const std::vector<Triple>& dotp, const FqV& dotp_claims, Tr& t, BatchedProofP* out,
-                         FqV* rand_out, const Shard& sh) {
+int batched_prove(spg_ctx* ctx, const TreeSh& ts, size_t nc, size_t M, FqV claims, const std::vector<Triple>& dotp,
+                  const FqV& dotp_claims, Tr& t, BatchedProofP* out, FqV* rand_out, const Shard& sh) {
   const size_t L = lg2(M), W = (size_t)ts.W, lgW = lg2(W), m = ts.m, lgm = lg2(m);
   auto off = [](size_t MM, size_t k) { return 2 * MM - 2 * (MM >> k); };
   const size_t nt_max = nc + dotp.size();
@@ -1168,17 +1196,7 @@ static int batched_prove(spg_ctx* ctx, const TreeSh& ts, size_t nc, size_t M, Fq
   Laps lp;
   lp.title = "ProductCircuitEvalProofBatched::prove";
   LayerEnv E{ctx, t, sh, lp, nc};
-  E.cbuf[0] = (Fq*)ws_get(ctx, kWsC, std::max(half_max, W) * sizeof(Fq) + 64);
-  E.cbuf[1] = (Fq*)ws_get(ctx, kWsC2, std::max(half_max, W) * sizeof(Fq) + 64);
-  // triples, then their coefficients, in one buffer (one upload per layer)
-  E.tr_bytes = (nt_max * sizeof(Triple) + 63) & ~(size_t)63;
-  E.ddesc = (uint8_t*)ws_get(ctx, kWsTriples, E.tr_bytes + nt_max * sizeof(Fq) + 64);
-  E.part = (Fq*)ws_get(ctx, kWsPart, 3 * 2048 * sizeof(Fq) + 64);  // K <= 2048 workgroups per round
-  E.gbuf = W > 1 ? (Fq*)ws_get(ctx, kWsGather, 3 * nt_max * W * sizeof(Fq) + 64) : nullptr;
-  E.W = W;
-  E.rank = ts.r;
-  if (!E.cbuf[0] || !E.cbuf[1] || !E.ddesc || !E.part || (W > 1 && !E.gbuf))
-    return set_err(ctx, SPG_E_NOMEM, "batched_prove");
+  if (int rc = layer_env_init(E, nt_max, half_max, W, ts.r)) return rc;
   FqV rand;
   // W > 1: a failure on this rank alone (allocation, HIP, mailbox) is not returned at once -- the peers would wait
   // in the next exchange. The rank stops working (`fail`, skip mode) but keeps the exchange sequence, whose
@@ -1243,6 +1261,34 @@ static int batched_prove(spg_ctx* ctx, const TreeSh& ts, size_t nc, size_t M, Fq
   }
   lp.print();
   *rand_out = rand;
+  return 0;
+}
+
+int cubic_layer(spg_ctx* ctx, const std::vector<Triple>& tr, size_t nc, const Fq* c_shared, size_t log_len,
+                const FqV& coeffs, const Fq& e, Tr& t, LayerProofP* proof, FqV* r, FqV* fin) {
+  const size_t nt = tr.size(), len = (size_t)1 << log_len;
+  if (!nt || coeffs.size() != nt || nc > nt || (nc && !c_shared))
+    return set_err(ctx, SPG_E_ARG, "cubic_layer: one coefficient per triple, a shared vector for the pairs");
+  if (3 * nt + 1 > kMboxScalars) return set_err(ctx, SPG_E_ARG, "cubic_layer: too many triples for the mailbox");
+  Laps lp;
+  lp.title = "SumcheckInstanceProof::prove_cubic_batched";
+  const Shard sh;
+  LayerEnv E{ctx, t, sh, lp, nc};
+  if (int rc = layer_env_init(E, nt, len, 1, 0)) return rc;
+  LayerState S;
+  S.nt = nt;
+  S.ngroups = (nc ? 1 : 0) + (nt - nc);
+  S.e = e;
+  // the descriptors as for a prover's layer (the launch writes the one-entry eq() of no variables into cbuf[0]), then
+  // the caller's shared vector in its place
+  int rc = layer_setup(E, tr, coeffs, FqV(), false, len, 0);
+  if (rc) return rc;
+  if (nc) SPG_HIP(ctx, hipMemcpyAsync(E.cbuf[0], c_shared, len * sizeof(Fq), hipMemcpyDeviceToDevice, ctx->stream));
+  rc = run_rounds(E, S, log_len, false, true, fin, 0);
+  if (rc) return rc;
+  *r = S.r_prod;
+  *proof = std::move(S.proof);
+  lp.print();
   return 0;
 }
 
@@ -1564,32 +1610,9 @@ int spark_prove_core(spg_ctx* ctx, spg_spark* S, FqV ex, FqV ey, const FqV& eval
     hipLaunchKernelGGL(k_hash_mem, dim3(nblk(2 * mm)), dim3(256), 0, s, S->d_audit, mem_rx, mem_ry, (int)lg2(cells),
                        (int)lg2(mm), (uint32_t)tsm.W, (uint32_t)tsm.r, rh, rh2, rms, tsm.loc);
   }
-  for (int which = 0; which < 2; which++) {  // ProductCircuit::new (product_tree.rs:36-58), local trees
-    Fq* tree = which ? tsm.loc : tso.loc;
-    const size_t M = which ? mm : mo, nc = which ? 4 : 4 * B;
-    KScope ks(ctx, "spark_product_tree", 96.0 * nc * M / 2);
-    // levels of more than kTopHalf products per circuit: one grid-wide launch each; the rest and the tops: k_tree_top
-    static const size_t kTopHalf = getenv("SPG_TREE_TOP") ? (size_t)atol(getenv("SPG_TREE_TOP")) : 1024;
-    size_t k = 0;
-    for (; k + 1 < lg2(M) && (M >> (k + 1)) > kTopHalf; k++) {
-      size_t ok = 2 * M - 2 * (M >> k), ok1 = 2 * M - 2 * (M >> (k + 1));
-      hipLaunchKernelGGL(k_tree_level, dim3(nblk(nc * (M >> (k + 1)))), dim3(256), 0, s, tree, nc, 2 * M, ok, ok1,
-                         (int)lg2(M >> (k + 1)));
-    }
-    if (kTopHalf) {
-      hipLaunchKernelGGL(k_tree_top, dim3((unsigned)nc), dim3(256), 0, s, tree, 2 * M, (int)lg2(M), (int)k,
-                         dtops + (which ? 4 * B : 0));
-    } else {
-      for (; k + 1 < lg2(M); k++) {
-        size_t ok = 2 * M - 2 * (M >> k), ok1 = 2 * M - 2 * (M >> (k + 1));
-        hipLaunchKernelGGL(k_tree_level, dim3(nblk(nc * (M >> (k + 1)))), dim3(256), 0, s, tree, nc, 2 * M, ok, ok1,
-                           (int)lg2(M >> (k + 1)));
-      }
-      const size_t top = 2 * M - 4;  // v_{L-1}
-      hipLaunchKernelGGL(k_tops, dim3(nblk(nc)), dim3(256), 0, s, tree, nc, 2 * M, top, dtops + (which ? 4 * B : 0));
-    }
-  }
-  SPG_HIP(ctx, hipGetLastError());
+  rc = tree_build(ctx, tso.loc, 4 * B, mo, dtops);  // ProductCircuit::new (product_tree.rs:36-58), local trees
+  if (!rc) rc = tree_build(ctx, tsm.loc, 4, mm, dtops + 4 * B);
+  if (rc) return rc;
   FqV tops(4 * B + 4);
   rc = d2h_fq(ctx, dtops, tops.data(), tops.size());
   if (tso.W > 1 || tsm.W > 1) {
@@ -1646,23 +1669,9 @@ int spark_prove_core(spg_ctx* ctx, spg_spark* S, FqV ex, FqV ey, const FqV& eval
                      BN, N, hN, hNl, (uint32_t)tso.W, (uint32_t)tso.r);
   SPG_HIP(ctx, hipGetLastError());
   FqV dotp_claims(2 * B);
-  {
-    Triple* dtr = (Triple*)ws_get(ctx, kWsTriples, 6 * B * sizeof(Triple) + 64);
-    unsigned nb = (unsigned)std::min<size_t>(nblk(hNl), std::max<size_t>(1, 2048 / (2 * B)));
-    Fq* part = (Fq*)ws_get(ctx, kWsSegPart, 2 * B * nb * sizeof(Fq) + 64);
-    Fq* dres = (Fq*)ws_get(ctx, kWsSeg, 2 * B * sizeof(Fq) + 64);
-    if (!dtr || !part || !dres) rc = set_err(ctx, SPG_E_NOMEM, "dotp eval");
-    if (!rc) {
-      SPG_HIP(ctx, hipMemcpyAsync(dtr, dotp.data(), dotp.size() * sizeof(Triple), hipMemcpyHostToDevice, s));
-      KScope ks(ctx, "spark_dotp_eval", 96.0 * 2 * B * hNl);
-      hipLaunchKernelGGL(k_dot3, dim3(nb, (unsigned)(2 * B)), dim3(256), 0, s, dtr, hNl, part);
-      hipLaunchKernelGGL(k_sum_seg, dim3((unsigned)(2 * B)), dim3(256), 0, s, part, (int)nb, dres);
-      SPG_HIP(ctx, hipGetLastError());
-      rc = d2h_fq(ctx, dres, dotp_claims.data(), 2 * B);
-    }
-    if (tso.W > 1) rc = comm_sum_fq(ctx, sh, rc, dotp_claims.data(), 2 * B);
-    if (rc) return rc;
-  }
+  rc = dotp_evaluate(ctx, dotp, hNl, dotp_claims.data());
+  if (tso.W > 1) rc = comm_sum_fq(ctx, sh, rc, dotp_claims.data(), 2 * B);
+  if (rc) return rc;
   FqV dl(B), dr(B);
   for (size_t b = 0; b < B; b++) {
     dl[b] = dotp_claims[2 * b];

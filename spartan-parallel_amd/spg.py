@@ -672,6 +672,158 @@ def r1cs_multiply_vec_block(ctx, inst, num_proofs, max_num_proofs, num_inputs, m
     return tuple(out)
 
 
+# ---- memory checking and the grand-product argument on device vectors (csrc/prodc.hip)
+def _buf_from_handle(ctx, h):
+    b = Buf.__new__(Buf)
+    b.ctx = ctx
+    b._h = h
+    lib().spg_buf_len.restype = ctypes.c_size_t
+    b.n = int(lib().spg_buf_len(h))
+    return b
+
+
+def _buf_array(bufs):
+    """a C array of spg_buf* (kept alive by the caller for the call's duration)"""
+    return (ctypes.c_void_p * max(len(bufs), 1))(*[b.handle.value for b in bufs])
+
+
+def _sync_len(bufs):
+    lib().spg_buf_len.restype = ctypes.c_size_t
+    for b in bufs:
+        b.n = int(lib().spg_buf_len(b.handle))
+
+
+def hash_layer(ctx, eval_table, addrs, derefs, read_ts, audit_ts, r_hash, r_multiset):
+    """Layers::build_hash_layer (src/sparse_mlpoly.rs:612-687) on Bufs: eval_table, audit_ts of num_mem_cells scalars;
+    addrs, derefs, read_ts lists of n Bufs of num_ops scalars. Returns (init, reads, writes, audit): new Bufs (reads,
+    writes lists of n)."""
+    n = len(addrs)
+    if n == 0 or len(derefs) != n or len(read_ts) != n:
+        raise ValueError("hash_layer: addrs, derefs, read_ts must be n >= 1 vectors each")
+    if audit_ts.n != eval_table.n:
+        raise ValueError("hash_layer: audit_ts must hold one scalar per memory cell")
+    if any(b.n != addrs[0].n for b in list(addrs) + list(derefs) + list(read_ts)):
+        raise ValueError("hash_layer: addrs, derefs, read_ts must have one length")
+    a, d, t = _buf_array(addrs), _buf_array(derefs), _buf_array(read_ts)
+    init, audit = ctypes.c_void_p(), ctypes.c_void_p()
+    reads, writes = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
+    ctx.check(lib().spg_hash_layer(ctx.handle, eval_table.handle, a, d, t, ctypes.c_size_t(n), audit_ts.handle,
+                                   _p(_scalars(r_hash)), _p(_scalars(r_multiset)), ctypes.byref(init), reads, writes,
+                                   ctypes.byref(audit)), "spg_hash_layer")
+    mk = lambda h: _buf_from_handle(ctx, ctypes.c_void_p(h))  # noqa: E731
+    return mk(init.value), [mk(h) for h in reads], [mk(h) for h in writes], mk(audit.value)
+
+
+class ProductCircuits:
+    """nc ProductCircuits of M leaves each (src/product_tree.rs:18-108) built on the device from Bufs of one
+    power-of-two length M >= 2 (spg_prodc_*); the inputs are left unchanged."""
+
+    def __init__(self, ctx, polys):
+        polys = list(polys)
+        if not polys or any(b.n != polys[0].n for b in polys):
+            raise ValueError("ProductCircuits: one or more polynomials of one length")
+        M = polys[0].n
+        if M < 2 or M & (M - 1):
+            raise ValueError("ProductCircuits: the length must be a power of two >= 2")
+        self.ctx = ctx
+        self.nc, self.M = len(polys), M
+        self._h = ctypes.c_void_p()
+        ctx.check(lib().spg_prodc_new(ctx.handle, _buf_array(polys), ctypes.c_size_t(self.nc), ctypes.byref(self._h)),
+                  "spg_prodc_new")
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def shape(self):
+        """(nc, num_leaves) as the library holds them"""
+        nc, m = ctypes.c_size_t(), ctypes.c_size_t()
+        assert lib().spg_prodc_shape(self._h, ctypes.byref(nc), ctypes.byref(m)) == 0
+        return int(nc.value), int(m.value)
+
+    def evaluate(self):
+        """ProductCircuit::evaluate of every circuit: [nc, 4]"""
+        out = np.zeros((self.nc, 4), dtype=np.uint64)
+        self.ctx.check(lib().spg_prodc_evaluate(self.ctx.handle, self._h, _p(out)), "spg_prodc_evaluate")
+        return out
+
+    def layer(self, c, k):
+        """(left_vec[k], right_vec[k]) of circuit c: M >> (k + 1) scalars each"""
+        if not (0 <= c < self.nc) or not (0 <= k < self.M.bit_length() - 1):
+            raise ValueError("ProductCircuits.layer: no such circuit layer")
+        half = self.M >> (k + 1)
+        left, right = np.zeros((half, 4), dtype=np.uint64), np.zeros((half, 4), dtype=np.uint64)
+        self.ctx.check(lib().spg_prodc_layer(self.ctx.handle, self._h, ctypes.c_size_t(c), ctypes.c_size_t(k), _p(left),
+                                             _p(right)), "spg_prodc_layer")
+        return left, right
+
+    def proof_size(self, nd):
+        """bytes of bincode(ProductCircuitEvalProofBatched) for these circuits and nd dot-product circuits"""
+        L = self.M.bit_length() - 1
+        return 8 + 3 * (8 + 32 * nd) + sum(8 + j * 104 + 2 * (8 + 32 * self.nc) for j in range(L))
+
+    def prove_batched(self, dotp, transcript, cap=None):
+        """ProductCircuitEvalProofBatched::prove (src/product_tree.rs:260-396): dotp a list of (left, right, weight)
+        Bufs of M/2 scalars, bound in place. Returns (proof bytes, rand [log2 M, 4]); the circuits are consumed."""
+        flat = [b for tr in dotp for b in tr]
+        if any(len(tr) != 3 for tr in dotp) or any(b.n != self.M // 2 for b in flat):
+            raise ValueError("prove_batched: dot-product circuits are (left, right, weight) of M/2 scalars each")
+        cap = self.proof_size(len(dotp)) if cap is None else cap
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        n, rl = ctypes.c_size_t(0), ctypes.c_size_t(0)
+        rand = np.zeros((self.M.bit_length(), 4), dtype=np.uint64)
+        rc = lib().spg_prodc_prove_batched(self.ctx.handle, self._h, _buf_array(flat), ctypes.c_size_t(len(dotp)),
+                                           transcript.handle, _p(out), ctypes.c_size_t(cap), ctypes.byref(n), _p(rand),
+                                           ctypes.byref(rl))
+        self.last_len = int(n.value)
+        self.ctx.check(rc, "spg_prodc_prove_batched")
+        _sync_len(flat)
+        return out[:n.value].tobytes(), rand[:rl.value].copy()
+
+    def free(self):
+        if self._h:
+            lib().spg_prodc_free(self.ctx.handle, self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def prove_cubic_batched(ctx, claim, num_rounds, A_par, B_par, C_par, A_seq, B_seq, C_seq, coeffs, transcript):
+    """SumcheckInstanceProof::prove_cubic_batched with comb A B C (src/sumcheck.rs:264-434): pairs (A_par[i], B_par[i])
+    sharing C_par (None allowed without pairs), triples (A_seq[i], B_seq[i], C_seq[i]); every Buf of one length 2^k,
+    k >= num_rounds, bound in place. Returns (polys [num_rounds, 3, 4], r [num_rounds, 4], claims_par [2 n_par + 1, 4]
+    (A finals, B finals, C_par[0]; empty without C_par), claims_seq [3, n_seq, 4])."""
+    A_par, B_par, A_seq, B_seq, C_seq = (list(x) for x in (A_par, B_par, A_seq, B_seq, C_seq))
+    n_par, n_seq = len(A_par), len(A_seq)
+    if len(B_par) != n_par or len(B_seq) != n_seq or len(C_seq) != n_seq or n_par + n_seq == 0:
+        raise ValueError("prove_cubic_batched: one B per A (and one C per sequential A), at least one term")
+    if n_par and C_par is None:
+        raise ValueError("prove_cubic_batched: the pairs need C_par")
+    bufs = A_par + B_par + ([C_par] if C_par is not None else []) + A_seq + B_seq + C_seq
+    n = bufs[0].n
+    if n == 0 or n & (n - 1) or any(b.n != n for b in bufs) or (1 << num_rounds) > n:
+        raise ValueError("prove_cubic_batched: every vector must hold 2^k scalars, one k >= num_rounds")
+    co = _scalars(coeffs)
+    if co.shape[0] != n_par + n_seq:
+        raise ValueError("prove_cubic_batched: one coefficient per term")
+    polys = np.zeros((max(num_rounds, 1), 3, 4), dtype=np.uint64)
+    r = np.zeros((max(num_rounds, 1), 4), dtype=np.uint64)
+    cpar = np.zeros((2 * n_par + 1, 4), dtype=np.uint64)
+    cseq = np.zeros((3, max(n_seq, 1), 4), dtype=np.uint64)
+    ctx.check(lib().spg_prove_cubic_batched(
+        ctx.handle, _p(_scalars(claim)), ctypes.c_size_t(num_rounds), _buf_array(A_par), _buf_array(B_par),
+        ctypes.c_size_t(n_par), C_par.handle if C_par is not None else None, _buf_array(A_seq), _buf_array(B_seq),
+        _buf_array(C_seq), ctypes.c_size_t(n_seq), _p(co), transcript.handle, _p(polys), _p(r), _p(cpar), _p(cseq)),
+        "spg_prove_cubic_batched")
+    _sync_len(bufs)
+    return polys[:num_rounds], r[:num_rounds], cpar if C_par is not None else cpar[:0], cseq[:, :n_seq]
+
+
 def r1cs_multi_evaluate(ctx, inst, num_instances, rx, ry):
     """R1CSInstance::multi_evaluate -> (3 * num_instances, 4) limbs [A_0, B_0, C_0, A_1, ...]"""
     rx = _scalars(rx)
