@@ -81,6 +81,13 @@ int spgh_roundtrip(const uint8_t* in, uint8_t* out) {
   ext_compress(p, out);
   return 1;
 }
+// the same round trip through the host's radix-2^51 decoder (hcurve.hpp), the one the verifier and proto.hip use
+int spgh_hext_roundtrip(const uint8_t* in, uint8_t* out) {
+  h::HExt p;
+  if (!h::hext_decompress(in, p)) return 0;
+  h::hext_compress(p, out);
+  return 1;
+}
 // op: 0 add, 1 double, 2 madd via niels, 3 madd negated
 int spgh_point_op(int op, const uint8_t* a, const uint8_t* b, uint8_t* out) {
   Ext p, q;

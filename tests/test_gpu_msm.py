@@ -8,6 +8,8 @@ import os
 import numpy as np
 import pytest
 
+import fieldref
+
 pytestmark = pytest.mark.gpu
 G = os.path.join(os.path.dirname(__file__), "golden")
 Q = 2**252 + 27742317777372353535851937790883648493
@@ -22,6 +24,13 @@ def gens64(ctx):
 
 def rand_fq(oracle, rng, n):
     return oracle.fq_from_bytes_wide(rng.integers(0, 256, 64 * n, dtype=np.uint8).tobytes())
+
+
+def carry_scalars():
+    """Montgomery scalars whose every c-bit window sits on the signed recode's d > NB decision (NB, NB + 1, NB - 1,
+    2^c - 1, NB + 1 / NB - 1 alternating), for c in 8, 9, 10, 12, 13, 14: the inline copies of the recode in msm.hip,
+    msm_big.hip and comb.hip see the patterns tests/test_gpu_primitives.py feeds bullet.hpp's"""
+    return fieldref.arr_u64([fieldref.to_mont(v) for v in fieldref.api_carry_scalars()])
 
 
 def test_gens_derive_matches_oracle(ctx, oracle, gens64):
@@ -79,6 +88,12 @@ def test_msm_edge_scalars(ctx, oracle, gens64):
         "same_random": np.tile(rand_fq(oracle, np.random.default_rng(1), 1)[0], (n, 1)),
         "pow2_252": np.tile(oracle.fq_from_raw([0, 0, 0, 1 << 60]), (n, 1)),
     }
+    cs = carry_scalars()
+    cases["carry_patterns"] = np.concatenate([cs] * (n // len(cs) + 1))[:n]
+    for i in range(0, len(cs), 6):  # six patterns at a time, alone among zeros
+        lone = np.zeros((n, 4), np.uint64)
+        lone[7:13] = cs[i:i + 6]
+        cases["carry_patterns_%d" % i] = lone
     for name, s in cases.items():
         assert gens64.msm(s) == oracle.msm(pts[:n], s), name
     assert gens64.msm(np.tile(zero, (n, 1))) == bytes(32)  # identity
@@ -160,6 +175,9 @@ def test_commit_rows_comb(ctx, oracle, gens64, L, R):
     Z[3 * R:4 * R] = 0
     Z[4 * R:5 * R] = one
     Z[5 * R::7] = minus1
+    if (L, R) == (64, 256):  # rows 6 and 7: every window on the recode's carry decision (carry_scalars)
+        cs = carry_scalars()
+        Z[6 * R:8 * R] = np.concatenate([cs] * (2 * R // len(cs) + 1))[:2 * R]
     assert np.array_equal(gens64.commit_rows(Z, L, R), oracle.commit_rows(pts[:R], pts[1024].tobytes(), Z, L, R))
     bl = rand_fq(oracle, rng, L)
     bl[0] = minus1
@@ -239,6 +257,11 @@ def edge_and_skew_checks(oracle, gens_big):
     assert gens_big.msm(s[:m], gen_offset=1500) == oracle.msm(pts[1500:n], s[:m]), "offset"
     zeros = np.zeros((n, 4), np.uint64)
     assert gens_big.msm(zeros) == bytes(32), "identity"
+    cs = carry_scalars()
+    carry = s.copy()
+    for i in range(0, n - len(cs), 997):  # every window on the recode's carry decision, spread over the workgroups
+        carry[i:i + len(cs)] = cs
+    assert gens_big.msm(carry) == oracle.msm(pts[:n], carry), "carry patterns"
 
 
 @pytest.mark.parametrize("c", ["8", "10", "13", "14"])
