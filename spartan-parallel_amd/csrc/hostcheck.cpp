@@ -254,8 +254,8 @@ int spgh_dbl_compress_check(const uint8_t* uni, size_t n) {
   return bad;
 }
 
-// The cross-rank exchange of every sharded call (comm.hpp: api.hip's comm_sum_fq, which Prover::sum_ranks and the
-// SPARK / multi_evaluate shards use): gather every rank's status and n partial scalars through the caller's
+// The cross-rank exchange of every sharded call (comm.hpp: api.hip's comm_sum_fq, which Prover::sum_ranks -- the R1CS
+// prover's p1_round_single / p2_round_single -- and the SPARK / multi_evaluate shards use): gather every rank's status and n partial scalars through the caller's
 // allgather and sum them mod q. Returns the transport's error (-1), else the first non-zero status of any rank
 // (so a failing rank fails every rank alike), else 0 with out = the sums.
 int spgh_comm_sum(spg_allgather_fn fn, void* user, int nranks, int status, const uint64_t* mine, size_t n,

@@ -357,6 +357,47 @@ __global__ void __launch_bounds__(256) k_sum_segments(const Fq* __restrict__ par
 // ------------------------------------------------------------------------------------ host helpers
 // (eq tables, UniPoly::from_evals, short MLE evaluations: hostmath.hpp)
 
+// the prover's switches and limits (environment, read once per process)
+struct R1csKnobs {
+  bool tape_ahead;     // SPG_TAPE_AHEAD: ZKRounds computes every round's randomness-only points in one burst at init
+  bool sc_fuse;        // SPG_SC_FUSE: a round's fold rides in the next round's evaluation (sumcheck.hip, FOLD kernels);
+                       // 0 restores the separate fold launch
+  bool z_tiled;        // SPG_Z_TILED: k_z_fill_tiled when every instance's row is whole 256-element tiles
+  bool z_side;         // SPG_Z_SIDE: the Z fill runs on the second stream beside phase 1 (ZFill); 0 fills it in order
+  size_t z_after;      // SPG_Z_AFTER (4): the phase-1 round whose evaluation the side-stream Z fill is queued after
+  bool spmv_tiled;     // SPG_SPMV_TILED: k_spmv<true> when every instance's q rows are whole 256-row tiles
+  bool p1_pair;        // SPG_P1_PAIR: two phase-1 rounds per launch (k_phase1_pair); 0: one per launch
+  size_t p1_pair_max;  // SPG_P1_PAIR_MAX (8192, at most kP1PairMax): points of a phase-1 pair's second round
+  bool sigma_ahead;    // SPG_SIGMA_AHEAD: every point of the three sigma protocols in one host burst ahead of the
+                       // transcript sequence; 0: each protocol commits on its own
+  bool q_bound_all;    // SPG_Q_BOUND_ALL: every q fold of Z in one pass (k_pqx_bound_q); 0: one launch per challenge
+  bool p2_pair;        // SPG_P2_PAIR: two phase-2 y rounds per launch (k_phase2_pair); 0: one per launch
+  size_t p2_pair_max;  // SPG_P2_PAIR_MAX (8192, at most kP1PairMax): elements of a phase-2 pair
+  bool wit_in_place;   // SPG_WIT_IN_PLACE: witness parts resident on this device are read in place, not copied
+};
+static const R1csKnobs& r1cs_knobs() {
+  static const R1csKnobs kn = [] {
+    auto on = [](const char* name) { return !getenv(name) || atoi(getenv(name)) != 0; };
+    auto num = [](const char* name, size_t dflt) { return getenv(name) ? (size_t)atol(getenv(name)) : dflt; };
+    R1csKnobs k;
+    k.tape_ahead = on("SPG_TAPE_AHEAD");
+    k.sc_fuse = on("SPG_SC_FUSE");
+    k.z_tiled = on("SPG_Z_TILED");
+    k.z_side = on("SPG_Z_SIDE");
+    k.z_after = num("SPG_Z_AFTER", 4);
+    k.spmv_tiled = on("SPG_SPMV_TILED");
+    k.p1_pair = on("SPG_P1_PAIR");
+    k.p1_pair_max = std::min<size_t>(kP1PairMax, num("SPG_P1_PAIR_MAX", 8192));
+    k.sigma_ahead = on("SPG_SIGMA_AHEAD");
+    k.q_bound_all = on("SPG_Q_BOUND_ALL");
+    k.p2_pair = on("SPG_P2_PAIR");
+    k.p2_pair_max = std::min<size_t>(kP1PairMax, num("SPG_P2_PAIR_MAX", 8192));
+    k.wit_in_place = on("SPG_WIT_IN_PLACE");
+    return k;
+  }();
+  return kn;
+}
+
 // ZK sumcheck round bookkeeping shared by phase 1 and phase 2 (sumcheck.rs:1247-1370).
 // The RandomTape is a transcript that only ever absorbs labels, so the values a round draws do not depend on
 // the proof: init() draws blinds_poly / blinds_evals as the reference does, then reads every round's
@@ -380,8 +421,7 @@ struct ZKRounds {
     blinds_evals = tape.vec("blinds_evals", rounds);
     claim = c;
     blind_claim = b;
-    static const bool on = !getenv("SPG_TAPE_AHEAD") || atoi(getenv("SPG_TAPE_AHEAD")) != 0;
-    ahead = on && rounds > 0 && g.gens_4.G.size() == 4;
+    ahead = r1cs_knobs().tape_ahead && rounds > 0 && g.gens_4.G.size() == 4;
     if (!ahead) {
       comm_claim = commit_batch(g, {CJob(g.gens_1, {c}, b)})[0];
       return;
@@ -461,18 +501,12 @@ struct ZKRounds {
   }
 };
 
-// host wall-clock breakdown of one prove (printed to stderr when SPG_TRACE is set)
-
-// device eq table of a host vector (uploads through the kernel argument)
-
 // workspace slots used here (msm.hip uses 0..12, proto.hip 20..22)
 enum {
   WS_AZ = 30, WS_BZ, WS_CZ, WS_Z, WS_ABC, WS_TP, WS_TQ, WS_TX, WS_EQRX, WS_EQP, WS_PART, WS_OUT3, WS_DESC,
   WS_L, WS_BPART, WS_BOUT, WS_EV_RX, WS_EV_RY, WS_EV_PART, WS_EV_OUT, WS_EV_DESC, WS_C1, WS_C2, WS_TQ2, WS_TX2, WS_ABC2,
   WS_EQQ  // (56; spark.hip starts at 60)
 };
-// phase-1 rounds in modes x and q fold inside the next round's evaluation (sumcheck.hip, FOLD kernels); SPG_SC_FUSE=0
-// restores the separate fold launch
 // the cubic Lagrange basis on the nodes 0..3 at r (a pair's round j + 1 from its grid at t = r_j)
 static void lagrange4(const Fq& r, Fq L[4]) {
   static const Fq inv2 = fq_inv(fq_from_u64(2)), inv6 = fq_inv(fq_from_u64(6));
@@ -498,10 +532,158 @@ static void pair_round_j1(const Fq ev[15], const Fq& r_j, Fq ej1[3]) {
     ej1[y] = acc;
   }
 }
-static bool sc_fuse_on() {
-  static const bool on = !getenv("SPG_SC_FUSE") || atoi(getenv("SPG_SC_FUSE")) != 0;
-  return on;
+
+// ------------------------------------------------------------------------------------ the R1CS prover
+// R1CSProof::prove (r1csproof.rs). Prover::run_stages calls the stages in protocol order: setup_tables (Z, Az, Bz, Cz
+// shapes, descriptors, tau eq tables, k_spmv), run_phase1, sigma1, phase2_prep (ABC, the Z join and q folds, eq(rp)),
+// run_phase2, witness_evals (lz_bound on the device), polyeval_batched, final_claims. A phase's loop asks
+// p*_next_launch for the next launch form after every challenge; p*_round_single and p*_round_pair are its two arms
+// (round_pair_arm is the host sequence both phases' pair arms share).
+
+// the sizes of one prove
+struct Shape {
+  size_t np, nq, nx, nw, ny;                       // variables of p, q, x (constraints), w (sections), y (inputs)
+  size_t PLn;                                      // this rank's instances [p0, p1)
+  std::vector<size_t> l_proofs, l_inputs, l_cons;  // their proofs, inputs and constraints
+  size_t num_cons;                                 // the padded maximum of constraints
+  bool single;                                     // one matrix triple shared by every instance
+};
+
+// a ragged table's shape: instance p owns rows[p] x secs x cols[p] elements, packed in order (total: all of them);
+// the four padded maxima are the Pqx fields the folds halve. The caller allocates d.
+static PqxDev pqx_shape(const std::vector<size_t>& rows, size_t secs, const std::vector<size_t>& cols,
+                        size_t num_instances, size_t max_num_proofs, size_t num_witness_secs, size_t max_num_inputs) {
+  PqxDev T;
+  const size_t n = rows.size();
+  T.zlen = n;
+  T.off.resize(n);
+  T.anp = rows;
+  T.anw.assign(n, secs);
+  T.ani = cols;
+  for (size_t p = 0; p < n; p++) {
+    T.off[p] = T.total;
+    T.total += rows[p] * secs * cols[p];
+  }
+  T.num_instances = num_instances;
+  T.max_num_proofs = max_num_proofs;
+  T.num_witness_secs = num_witness_secs;
+  T.max_num_inputs = max_num_inputs;
+  T.num_proofs = rows;
+  T.num_inputs = cols;
+  return T;
 }
+
+// The Z fill. k_spmv gathers from the witness itself, so the fill only has to land before phase 2. On the second
+// stream it is queued once phase 1's round SPG_Z_AFTER (default 4) has been evaluated, and runs beside the later,
+// smaller rounds: overlapping k_spmv or the first, HBM-bound rounds, the kernels slow each other (rocprof and same-box
+// A/Bs: DESIGN §4, round 4). SPG_Z_SIDE=0 fills it in order at setup. Whatever way the prove returns, `stream` is
+// ordered after the fill before anything later reuses the Z slot (the destructor joins).
+struct ZFill {
+  spg_ctx* c = nullptr;
+  const ZDesc* dz = nullptr;
+  const SecDesc* dsec = nullptr;
+  int n = 0, nws = 0;  // local instances, witness sections
+  Fq* Z = nullptr;
+  size_t total = 0;
+  bool tiled = false;  // k_z_fill_tiled: every instance's row is whole 256-element tiles
+  bool side = false;
+  bool queued = false, armed = false;
+  int queue() {
+    if (queued) return 0;
+    queued = true;
+    const hipStream_t main_stream = c->stream;
+    if (side) {
+      SPG_HIP(c, hipEventRecord(c->ev_pre, main_stream));
+      SPG_HIP(c, hipStreamWaitEvent(c->stream2, c->ev_pre, 0));
+      c->stream = c->stream2;
+    }
+    {
+      KScope ks(c, "z_fill", 64.0 * total);
+      if (tiled)  // (total is a multiple of 256 then, and so is every instance's offset)
+        hipLaunchKernelGGL(k_z_fill_tiled, dim3((uint32_t)(total / 256)), dim3(256), 0, c->stream, dz, n, dsec, nws, Z);
+      else
+        hipLaunchKernelGGL(k_z_fill, dim3(blocks_for(total)), dim3(256), 0, c->stream, dz, n, dsec, nws, Z,
+                           (uint64_t)total);
+    }
+    c->stream = main_stream;
+    SPG_HIP(c, hipGetLastError());
+    if (side) {
+      SPG_HIP(c, hipEventRecord(c->ev_side, c->stream2));
+      armed = true;
+    }
+    return 0;
+  }
+  int join() {
+    if (!armed) return 0;
+    armed = false;
+    return hipStreamWaitEvent(c->stream, c->ev_side, 0) == hipSuccess ? 0 : set_err(c, SPG_E_HIP, "z_fill join");
+  }
+  ~ZFill() { join(); }
+};
+
+// what the stages hand on to later ones
+struct Carry {
+  // device tables: Z; Az with Bz, Cz of its shape; ABC; the tau eq tables of phase 1; eq(rx), eq(rp) of phase 2
+  PqxDev Zp, Az, ABC;
+  Fq *Bz = nullptr, *Cz = nullptr;
+  Fq *Ap = nullptr, *Aq = nullptr, *Ax = nullptr;
+  Fq *eq_rx = nullptr, *eq_p = nullptr;
+  Fq* partials = nullptr;  // round evaluations: 3 per workgroup; pair launches: one per element
+  MatDesc* dmd = nullptr;  // the matrices' descriptors (k_spmv, k_abc)
+  // challenges: phase 1's (x and q also in the reference's reversed order), phase 2's
+  FqV rx, rq, rq_rev, rp, ry, rw, rp2;
+  Fq claims1[4], claims2[3];  // (tau, Az, Bz, Cz) at phase 1's point; (eq, ABC, Z) at phase 2's
+  Fq Az_blind, Bz_blind, Cz_blind, blind_post1, blind_post2;
+  Fq claim2, blind2;          // phase 2's claim and its blind
+  Pt comm_Az, comm_Bz, comm_Cz, comm_prod;
+};
+
+// how the folds of the `pending` rounds whose challenges are drawn reach the tables, and what evaluates the next round
+struct NextLaunch {
+  bool ride;   // the next launch applies them; else a launch of their own does (then the compaction, when due)
+  int rounds;  // of the next launch: 0 (none left), 1 or 2
+};
+
+// phase 1 as it goes (Prover::run_phase1)
+struct Phase1 {
+  size_t rounds = 0;
+  ZKRounds zk;
+  size_t cons_len, proof_len, instance_len;  // the half lengths of the reference's loop
+  size_t lenP, lenQ, lenX;                   // live lengths of the eq tables
+  std::vector<size_t> sc_np, sc_nc;          // local; P rounds use all-ones of length P
+  PqxDev Ac;                                 // compact Az for the instance rounds; TB, TC share its shape there
+  PqxDev* T = nullptr;                       // Az, then Ac
+  Fq *TB = nullptr, *TC = nullptr;
+  Fq *Aq = nullptr, *Ax = nullptr;           // the live eq(tau_q), eq(tau_x)
+  Fq *Aq2 = nullptr, *Ax2 = nullptr;         // the other halves of their ping-pong pairs (a fused fold writes there)
+  const Fq* Ap_l = nullptr;                  // eq(tau_p) indexed by the global instance in the x / q rounds
+  bool cur_pair = false;                     // the launch in flight evaluates rounds j, j + 1
+  FqV r;                                     // the challenges so far
+};
+// phase 2 as it goes (Prover::run_phase2)
+struct Phase2 {
+  size_t rounds = 0;
+  ZKRounds zk;
+  size_t inputs_len, ws_len, instance_len;
+  size_t lenP;
+  std::vector<size_t> sc_ni;
+  PqxDev Zc, ABCc;              // compact Z and ABC for the instance rounds
+  PqxDev *TZ = nullptr, *TA = nullptr;
+  const Fq* eq_l = nullptr;     // eq(rp) at the local instances
+  bool fuse2 = false;           // a single round's fold may ride in the next evaluation
+  Fq* ABC2 = nullptr;           // a shared ABC's ping-pong buffer
+  size_t W2 = 0;                // witness-section rows per instance of a pair
+  bool cur_pair = false;
+  FqV r;
+};
+
+// a witness-section polynomial (section w, instance p) in the batched opening
+struct PolyRef {
+  size_t w, p, np, ni, Rs;
+  bool mine;
+  FqV LZ, R;
+  Fq ev;
+};
 
 struct Prover {
   spg_ctx* ctx;
@@ -555,7 +737,6 @@ struct Prover {
     while (r + 1 < nranks && shard_begin(P, nranks, r + 1) <= p) r++;
     return r;
   }
-  int allgather(const void* send, size_t bytes, std::vector<uint8_t>& recv);
   int sum_ranks(Fq e[3]);
   // the exchanges of a sharded prove, in order (payload bytes per rank): their sequence depends only on public
   // sizes, so a rank that fails locally between two of them takes part in the next one with its failure as status
@@ -567,13 +748,56 @@ struct Prover {
   int exchange(const void* send, size_t bytes, std::vector<uint8_t>& recv);
   int gather_first(const std::vector<const PqxDev*>& tabs, std::vector<std::vector<Fq>>& full);
 
+  const R1csKnobs& kn = r1cs_knobs();
+  Shape sh;
+  Carry cy;
+  Laps lp;
+
   int run();
-  int run_inner(Laps& lp);
+  int run_stages();
+  int setup_tables(ZFill& zf);
+  // phase 1
+  int p1_mode(size_t j) const { return j < sh.nx ? MODE_X : (j < sh.nx + sh.nq ? MODE_Q : MODE_P); }
+  int p1_advance(Phase1& s, size_t j);
+  int p1_launch_single(Phase1& s, size_t j, const FoldPlan* fold);
+  bool p1_pair_ok(const Phase1& s, size_t j) const;
+  int p1_launch_pair(Phase1& s, size_t j, int nf, const FoldPlan* fp, const Fq& r1, const Fq& r2);
+  int p1_fold2x(Phase1& s, int m, const Fq& r1, const Fq& r2);
+  int p1_to_compact(Phase1& s);
+  NextLaunch p1_next_launch(const Phase1& s, size_t j_next, int pending) const;
+  int p1_launch_next(Phase1& s, size_t j_next, int pending, const Fq& r1, const Fq& r2);
+  int p1_round_single(Phase1& s, size_t j, ZFill& zf);
+  int p1_round_pair(Phase1& s, size_t j, ZFill& zf);
+  int run_phase1(ZFill& zf, FqV& r_all);
+  void sigma1();
+  int phase2_prep(ZFill& zf);
+  // phase 2
+  int p2_mode(size_t j) const { return j < sh.ny ? MODE_X : (j < sh.ny + sh.nw ? MODE_W : MODE_P); }
+  int p2_launch_single(Phase2& s, size_t j, const Fold2* fold);
+  bool p2_pair_ok(const Phase2& s, size_t j, bool fold_pending) const;
+  int p2_launch_pair(Phase2& s, int nf, const Fq& r1, const Fq& r2);
+  int p2_fold2x(Phase2& s, const Fq& r1, const Fq& r2);
+  int p2_to_compact(Phase2& s);
+  NextLaunch p2_next_launch(const Phase2& s, size_t j_next, int pending) const;
+  int p2_launch_next(Phase2& s, size_t j_next, int pending, const Fq& r1, const Fq& r2);
+  int p2_round_single(Phase2& s, size_t j);
+  int p2_round_pair(Phase2& s, size_t j);
+  int run_phase2();
+  // the pair arm of both phases once the grid `ev` is in: rounds j and j + 1, with the phase's `launch_next` between
+  // round j + 1's challenge and the rest of its proof; `laps`: the phase's eval / host / fold lap names
+  template <class Ph>
+  int round_pair_arm(Ph& s, size_t j, const Fq ev[15], const char* const laps[3],
+                     int (Prover::*launch_next)(Ph&, size_t, int, const Fq&, const Fq&));
+  // openings and final claims
+  int lz_bound(std::vector<PolyRef>& polys, size_t lz_total, std::vector<Fq>& lz_mine);
+  int witness_evals(std::vector<PolyRef>& polys, std::vector<FqV>& eval_list);
+  int polyeval_batched(std::vector<PolyRef>& polys);
+  void final_claims(const std::vector<FqV>& eval_list);
 };
 
 int Prover::run() {
-  Laps lp;
-  int rc0 = run_inner(lp);
+  lp = Laps();  // the breakdown's clock starts here
+  int rc0 = run_stages();
   lp.print();
   if (rc0 && nranks > 1 && !xshared && xdone < xplan.size()) {
     // this rank failed alone: the next exchange of the plan carries the failure to every rank
@@ -589,7 +813,8 @@ int Prover::run() {
 int Prover::exchange(const void* send, size_t bytes, std::vector<uint8_t>& recv) {
   const Shard sh{(int)rank, (int)nranks};
   if (nranks > 1 && (xdone >= xplan.size() || xplan[xdone] != bytes)) {
-    // the plan is a restatement of run_inner's control flow; a mismatch is a library bug
+    // the plan is a restatement of the stages' control flow (sum_ranks in p*_round_single, gather_first in
+    // p*_to_compact, the L.Z gather in witness_evals); a mismatch is a library bug
     const int rc = set_err(ctx, SPG_E_ARG, "sharded R1CSProof: exchange " + std::to_string(xdone) + " of " +
                                                std::to_string(bytes) + " bytes is not in the exchange plan");
     xshared = true;
@@ -602,7 +827,6 @@ int Prover::exchange(const void* send, size_t bytes, std::vector<uint8_t>& recv)
   if (rc) xshared = true;
   return rc;
 }
-int Prover::allgather(const void* send, size_t bytes, std::vector<uint8_t>& recv) { return exchange(send, bytes, recv); }
 // (e0, e2, e3) summed over the ranks' instance shards
 int Prover::sum_ranks(Fq e[3]) {
   if (nranks == 1) return 0;
@@ -624,21 +848,23 @@ void Prover::plan_exchanges(size_t np, size_t nq, size_t nx, size_t nw, size_t n
   xshared = false;
   if (nranks == 1) return;
   const size_t PL = (P + nranks - 1) / nranks, sum = 3 * sizeof(Fq);
-  // phase 1: one sum per x / q round, the gather of Az, Bz, Cz before the instance rounds
+  // phase 1: one sum per x / q round (p1_round_single), the gather of Az, Bz, Cz before the instance rounds
+  // (p1_to_compact)
   const size_t r1 = nx + nq + np;
   if (r1 && nx + nq == 0) xplan.push_back(PL * 3 * sizeof(Fq));
   for (size_t j = 0; j < r1; j++) {
     if (j < nx + nq) xplan.push_back(sum);
     if (j + 1 == nx + nq && np > 0) xplan.push_back(PL * 3 * sizeof(Fq));
   }
-  // phase 2: one sum per y / w round, the gather of Z (and ABC unless shared) before the instance rounds
+  // phase 2: one sum per y / w round (p2_round_single), the gather of Z (and ABC unless shared) before the instance
+  // rounds (p2_to_compact)
   const size_t k2 = inst.num_instances == 1 ? 1 : 2, r2 = ny + nw + np;
   if (r2 && ny + nw == 0) xplan.push_back(PL * k2 * sizeof(Fq));
   for (size_t j = 0; j < r2; j++) {
     if (j < ny + nw) xplan.push_back(sum);
     if (j + 1 == ny + nw && np > 0) xplan.push_back(PL * k2 * sizeof(Fq));
   }
-  // the L.Z bounds of every witness polynomial
+  // the L.Z bounds of every witness polynomial (witness_evals)
   size_t lz_total = 0;
   for (size_t i = 0; i < nws; i++)
     for (size_t p = 0; p < wit.num_proofs[i].size(); p++) lz_total += lz_width(wit.num_proofs[i][p], wit.num_inputs[i][p]);
@@ -673,7 +899,7 @@ int Prover::gather_first(const std::vector<const PqxDev*>& tabs, std::vector<std
       if (int rc = flush()) return rc;
   }
   std::vector<uint8_t> r;
-  int rc = allgather(mine.data(), mine.size() * sizeof(Fq), r);
+  int rc = exchange(mine.data(), mine.size() * sizeof(Fq), r);
   if (rc) return rc;
   const Fq* v = (const Fq*)r.data();
   full.assign(k, std::vector<Fq>(P, fq_zero()));
@@ -686,112 +912,96 @@ int Prover::gather_first(const std::vector<const PqxDev*>& tabs, std::vector<std
 // a table of n instances holding one element each (what remains of a Pqx table when only the instance
 // variables are left unbound); its index / index_high behave exactly like the full table's at (p,0,0,0)
 static PqxDev compact_table(Fq* d, size_t n, size_t P) {
-  PqxDev T;
+  const std::vector<size_t> ones(n, 1);
+  PqxDev T = pqx_shape(ones, 1, ones, npow2(n), 1, 1, 1);
   T.d = d;
-  T.zlen = n;
-  T.total = n;
-  for (size_t p = 0; p < n; p++) T.off.push_back(p);
-  T.anp.assign(n, 1);
-  T.anw.assign(n, 1);
-  T.ani.assign(n, 1);
-  T.num_instances = npow2(n);
-  T.max_num_proofs = 1;
-  T.num_witness_secs = 1;
-  T.max_num_inputs = 1;
   T.num_proofs.assign(P, 1);
   T.num_inputs.assign(P, 1);
   return T;
 }
 
-int Prover::run_inner(Laps& lp) {
-  hipStream_t s = ctx->stream;
+int Prover::run_stages() {
   t.protocol("R1CS proof");
-  size_t num_cons = inst.max_num_cons;
+  sh.num_cons = inst.max_num_cons;
+  sh.single = inst.num_instances == 1;
   std::vector<size_t> block_num_cons(P);
-  for (size_t p = 0; p < P; p++) block_num_cons[p] = inst.num_cons[inst.num_instances == 1 ? 0 : p];
-  size_t np = lg2(npow2(P)), nq = lg2(max_np), nx = lg2(num_cons), nw = lg2(nws), ny = lg2(Y);
-  plan_exchanges(np, nq, nx, nw, ny);
+  for (size_t p = 0; p < P; p++) block_num_cons[p] = inst.num_cons[sh.single ? 0 : p];
+  sh.np = lg2(npow2(P)), sh.nq = lg2(max_np), sh.nx = lg2(sh.num_cons), sh.nw = lg2(nws), sh.ny = lg2(Y);
+  plan_exchanges(sh.np, sh.nq, sh.nx, sh.nw, sh.ny);
   // this rank's instances [p0, p1): everything O(N) lives only here; nranks == 1 -> all of them
-  const size_t PLn = p1 - p0;
-  std::vector<size_t> l_proofs(num_proofs.begin() + p0, num_proofs.begin() + p1);
-  std::vector<size_t> l_inputs(num_inputs.begin() + p0, num_inputs.begin() + p1);
-  std::vector<size_t> l_cons(block_num_cons.begin() + p0, block_num_cons.begin() + p1);
+  sh.PLn = p1 - p0;
+  sh.l_proofs.assign(num_proofs.begin() + p0, num_proofs.begin() + p1);
+  sh.l_inputs.assign(num_inputs.begin() + p0, num_inputs.begin() + p1);
+  sh.l_cons.assign(block_num_cons.begin() + p0, block_num_cons.begin() + p1);
 
-  // ---- Z table (p, q_rev, w, x_rev)
-  PqxDev Zp;
-  Zp.zlen = PLn;
-  Zp.off.resize(PLn);
-  Zp.anp = l_proofs;
-  Zp.anw.assign(PLn, nws);
-  Zp.ani = l_inputs;
-  size_t ztot = 0;
-  static const bool z_tiles_on = !getenv("SPG_Z_TILED") || atoi(getenv("SPG_Z_TILED")) != 0;
-  bool z_tiled = z_tiles_on;  // k_z_fill_tiled: every instance's row is whole 256-element tiles
-  for (size_t p = 0; p < PLn; p++) {
-    Zp.off[p] = ztot;
-    ztot += l_proofs[p] * nws * l_inputs[p];
-    if (l_inputs[p] < 256) z_tiled = false;
-  }
-  Zp.total = ztot;
-  Zp.num_instances = npow2(P);
-  Zp.max_num_proofs = max_np;
-  Zp.num_witness_secs = npow2(nws);
-  Zp.max_num_inputs = Y;
-  Zp.num_proofs = l_proofs;
-  Zp.num_inputs = l_inputs;
-  Zp.d = (Fq*)ws_get(ctx, WS_Z, ztot * sizeof(Fq) + 64);
-  if (!Zp.d) return set_err(ctx, SPG_E_NOMEM, "Z table");
-  // ---- Az, Bz, Cz = multiply_vec_block (p, q_rev, 0, x_rev) for the local instances
-  PqxDev Az;
-  Az.zlen = PLn;
-  Az.off.resize(PLn);
-  Az.anp = l_proofs;
-  Az.anw.assign(PLn, 1);
-  Az.ani = l_cons;
-  size_t atot = 0;
-  for (size_t p = 0; p < PLn; p++) {
-    Az.off[p] = atot;
-    atot += l_proofs[p] * l_cons[p];
-  }
-  Az.total = atot;
-  Az.num_instances = npow2(P);
-  Az.max_num_proofs = max_np;
-  Az.num_witness_secs = 1;
-  Az.max_num_inputs = num_cons;
-  Az.num_proofs = l_proofs;
-  Az.num_inputs = l_cons;
+  ZFill zf;
+  int rc = setup_tables(zf);
+  if (!rc && !kn.z_side) rc = zf.queue();
+  if (rc) return rc;
+  lp.lap("setup");
+  cy.partials = (Fq*)ws_get(ctx, WS_PART, std::max(3 * (size_t)kScGridMax, kP1PairMax) * sizeof(Fq) + 64);
+  if (!cy.partials) return set_err(ctx, SPG_E_NOMEM, "partials");
+  FqV r1;  // phase 1's challenges in round order: x, q, p
+  if ((rc = run_phase1(zf, r1))) return rc;
+  lp.lap("p1_claims");
+  const FqV rx_rev(r1.begin(), r1.begin() + sh.nx);
+  cy.rq_rev.assign(r1.begin() + sh.nx, r1.begin() + sh.nx + sh.nq);
+  cy.rp.assign(r1.begin() + sh.nx + sh.nq, r1.end());
+  cy.rx.assign(rx_rev.rbegin(), rx_rev.rend());
+  cy.rq.assign(cy.rq_rev.rbegin(), cy.rq_rev.rend());
+  // eq(rx) of phase 2 depends on phase 1's challenges alone: on the device while the host runs the sigma protocols
+  cy.eq_rx = (Fq*)ws_get(ctx, WS_EQRX, (sizeof(Fq) << sh.nx) + 64);
+  if (!cy.eq_rx) return set_err(ctx, SPG_E_NOMEM, "eq(rx)");
+  if ((rc = eq_table(ctx, cy.rx, cy.eq_rx))) return rc;
+  sigma1();
+  lp.lap("sigma1");
+  if ((rc = phase2_prep(zf))) return rc;
+  lp.lap("p2_prep");
+  if ((rc = run_phase2())) return rc;
+  std::vector<PolyRef> polys;
+  std::vector<FqV> eval_list;
+  if ((rc = witness_evals(polys, eval_list))) return rc;
+  lp.lap("polyeval_bound");
+  if ((rc = polyeval_batched(polys))) return rc;
+  lp.lap("polyeval_dotlog");
+  final_claims(eval_list);
+  lp.lap("final");
+  return 0;
+}
+
+// Z (p, q_rev, w, x_rev) and Az, Bz, Cz = multiply_vec_block (p, q_rev, 0, x_rev) for the local instances: shapes,
+// workspace, every setup descriptor in one host-to-device copy, the tau eq tables, k_spmv; zf: the Z fill, made ready
+int Prover::setup_tables(ZFill& zf) {
+  const size_t PLn = sh.PLn, np = sh.np, nq = sh.nq, nx = sh.nx;
+  cy.Zp = pqx_shape(sh.l_proofs, nws, sh.l_inputs, npow2(P), max_np, npow2(nws), Y);
+  const size_t ztot = cy.Zp.total;
+  cy.Zp.d = (Fq*)ws_get(ctx, WS_Z, ztot * sizeof(Fq) + 64);
+  if (!cy.Zp.d) return set_err(ctx, SPG_E_NOMEM, "Z table");
+  PqxDev& Az = cy.Az;
+  Az = pqx_shape(sh.l_proofs, 1, sh.l_cons, npow2(P), max_np, 1, sh.num_cons);
+  const size_t atot = Az.total;
   Az.d = (Fq*)ws_get(ctx, WS_AZ, atot * sizeof(Fq) + 64);
-  Fq* Bz = (Fq*)ws_get(ctx, WS_BZ, atot * sizeof(Fq) + 64);
-  Fq* Cz = (Fq*)ws_get(ctx, WS_CZ, atot * sizeof(Fq) + 64);
-  if (!Az.d || !Bz || !Cz) return set_err(ctx, SPG_E_NOMEM, "Az/Bz/Cz");
-  static const bool z_side = !getenv("SPG_Z_SIDE") || atoi(getenv("SPG_Z_SIDE")) != 0;
-  // whatever way this returns, `stream` is ordered after the fill before anything later reuses the Z slot
-  struct SideJoin {
-    spg_ctx* c;
-    bool armed = false;
-    int join() {
-      if (!armed) return 0;
-      armed = false;
-      return hipStreamWaitEvent(c->stream, c->ev_side, 0) == hipSuccess ? 0 : set_err(c, SPG_E_HIP, "z_fill join");
-    }
-    ~SideJoin() { join(); }
-  } z_join{ctx};
+  cy.Bz = (Fq*)ws_get(ctx, WS_BZ, atot * sizeof(Fq) + 64);
+  cy.Cz = (Fq*)ws_get(ctx, WS_CZ, atot * sizeof(Fq) + 64);
+  if (!Az.d || !cy.Bz || !cy.Cz) return set_err(ctx, SPG_E_NOMEM, "Az/Bz/Cz");
   // every descriptor of the setup kernels (Z fill, Az/Bz/Cz) goes up in one host-to-device copy
   SecDesc* dsec = nullptr;
   ZDesc* dz = nullptr;
-  MatDesc* dmd = nullptr;
   SpDesc* dsd = nullptr;
   double visits = 0;
+  bool z_tiled = kn.z_tiled, spmv_tiled = kn.spmv_tiled;
   int rc = 0;
   {
     std::vector<ZDesc> zd(PLn);
     std::vector<SecDesc> sd(nws * PLn);
     for (size_t p = 0; p < PLn; p++) {
-      zd[p].dom_off = Zp.off[p];
-      zd[p].z_off = Zp.off[p];
-      zd[p].lg_q = (uint32_t)lg2(l_proofs[p]);
-      zd[p].ni = (uint32_t)l_inputs[p];
-      zd[p].lg_ni = (uint32_t)lg2(l_inputs[p]);
+      zd[p].dom_off = cy.Zp.off[p];
+      zd[p].z_off = cy.Zp.off[p];
+      zd[p].lg_q = (uint32_t)lg2(sh.l_proofs[p]);
+      zd[p].ni = (uint32_t)sh.l_inputs[p];
+      zd[p].lg_ni = (uint32_t)lg2(sh.l_inputs[p]);
+      if (sh.l_inputs[p] < 256) z_tiled = false;
+      if (sh.l_cons[p] < 256) spmv_tiled = false;
       for (size_t w = 0; w < nws; w++) {
         size_t pw = wit.num_proofs[w].size() == 1 ? 0 : p0 + p;
         if (!wit.ptr[w][pw]) return set_err(ctx, SPG_E_ARG, "witness shard does not hold instance");
@@ -807,434 +1017,371 @@ int Prover::run_inner(Laps& lp) {
     }
     std::vector<SpDesc> spd(PLn);
     for (size_t p = 0; p < PLn; p++) {
-      size_t pi = inst.num_instances == 1 ? 0 : p0 + p;
+      size_t pi = sh.single ? 0 : p0 + p;
       spd[p].dom_off = Az.off[p];
       spd[p].out_off = Az.off[p];
       spd[p].pi = (uint32_t)pi;
-      spd[p].lg_q = (uint32_t)lg2(l_proofs[p]);
-      spd[p].nrows = (uint32_t)l_cons[p];
-      spd[p].lg_rows = (uint32_t)lg2(l_cons[p]);
-      spd[p].ni = (uint32_t)l_inputs[p];
-      spd[p].lg_ni = (uint32_t)lg2(l_inputs[p]);
-      visits += (double)l_proofs[p] * (inst.nnz[3 * pi] + inst.nnz[3 * pi + 1] + inst.nnz[3 * pi + 2]);
+      spd[p].lg_q = (uint32_t)lg2(sh.l_proofs[p]);
+      spd[p].nrows = (uint32_t)sh.l_cons[p];
+      spd[p].lg_rows = (uint32_t)lg2(sh.l_cons[p]);
+      spd[p].ni = (uint32_t)sh.l_inputs[p];
+      spd[p].lg_ni = (uint32_t)lg2(sh.l_inputs[p]);
+      visits += (double)sh.l_proofs[p] * (inst.nnz[3 * pi] + inst.nnz[3 * pi + 1] + inst.nnz[3 * pi + 2]);
     }
     rc = stage_desc(zd, &dz);
     if (!rc) rc = stage_desc(sd, &dsec);
-    if (!rc) rc = stage_desc(md, &dmd);
+    if (!rc) rc = stage_desc(md, &cy.dmd);
     if (!rc) rc = stage_desc(spd, &dsd);
     if (!rc) rc = flush_desc();
     if (rc) return rc;
   }
+  zf.c = ctx, zf.dz = dz, zf.dsec = dsec, zf.n = (int)PLn, zf.nws = (int)nws;
+  zf.Z = cy.Zp.d, zf.total = ztot, zf.tiled = z_tiled, zf.side = kn.z_side;
   // ---- tau tables (identical on every rank)
   FqV tau_p = t.challenges("challenge_tau_p", np);
   FqV tau_q = t.challenges("challenge_tau_q", nq);
   FqV tau_x = t.challenges("challenge_tau_x", nx);
   if (getenv("SPG_DEBUG_TR")) fprintf(stderr, "[prove] r1cs P=%zu np=%zu nq=%zu nx=%zu tau_x0 %08x\n", (size_t)P, (size_t)np, (size_t)nq, (size_t)nx, tau_x[0].l[0]);
-  Fq* Ap = (Fq*)ws_get(ctx, WS_TP, (sizeof(Fq) << np) + 64);
-  Fq* Aq = (Fq*)ws_get(ctx, WS_TQ, (sizeof(Fq) << nq) + 64);
-  Fq* Ax = (Fq*)ws_get(ctx, WS_TX, (sizeof(Fq) << nx) + 64);
-  if (!Ap || !Aq || !Ax) return set_err(ctx, SPG_E_NOMEM, "eq tables");
-  rc = eq_tables(ctx, {{tau_p, Ap}, {tau_q, Aq}, {tau_x, Ax}});
+  cy.Ap = (Fq*)ws_get(ctx, WS_TP, (sizeof(Fq) << np) + 64);
+  cy.Aq = (Fq*)ws_get(ctx, WS_TQ, (sizeof(Fq) << nq) + 64);
+  cy.Ax = (Fq*)ws_get(ctx, WS_TX, (sizeof(Fq) << nx) + 64);
+  if (!cy.Ap || !cy.Aq || !cy.Ax) return set_err(ctx, SPG_E_NOMEM, "eq tables");
+  rc = eq_tables(ctx, {{tau_p, cy.Ap}, {tau_q, cy.Aq}, {tau_x, cy.Ax}});
   if (rc) return rc;
+  // ---- Az, Bz, Cz: outputs, CSR row pointers, and per visited entry its column, value and z gather
+  KScope ks(ctx, "spmv_block", 96.0 * atot + 12.0 * atot + 68.0 * visits);
+  hipLaunchKernelGGL(spmv_tiled ? k_spmv<true> : k_spmv<false>, dim3(blocks_for(atot)), dim3(256), 0, ctx->stream, dsd,
+                     (int)PLn, cy.dmd, inst.d_rowptr, inst.d_col, inst.d_val, dsec, (int)nws, (uint32_t)Y, Az.d, cy.Bz,
+                     cy.Cz, (uint64_t)atot);
+  SPG_HIP(ctx, hipGetLastError());
+  return 0;
+}
 
-  {  // ---- Az, Bz, Cz: outputs, CSR row pointers, and per visited entry its column, value and z gather
-    KScope ks(ctx, "spmv_block", 96.0 * atot + 12.0 * atot + 68.0 * visits);
-    static const bool tiles_on = !getenv("SPG_SPMV_TILED") || atoi(getenv("SPG_SPMV_TILED")) != 0;
-    bool tiled = tiles_on;  // every instance's q rows are whole 256-row tiles
-    for (size_t p = 0; p < PLn; p++)
-      if (l_cons[p] < 256) tiled = false;
-    if (tiled)
-      hipLaunchKernelGGL(k_spmv<true>, dim3(blocks_for(atot)), dim3(256), 0, s, dsd, (int)PLn, dmd, inst.d_rowptr,
-                         inst.d_col, inst.d_val, dsec, (int)nws, (uint32_t)Y, Az.d, Bz, Cz, (uint64_t)atot);
-    else
-      hipLaunchKernelGGL(k_spmv<false>, dim3(blocks_for(atot)), dim3(256), 0, s, dsd, (int)PLn, dmd, inst.d_rowptr,
-                         inst.d_col, inst.d_val, dsec, (int)nws, (uint32_t)Y, Az.d, Bz, Cz, (uint64_t)atot);
-    SPG_HIP(ctx, hipGetLastError());
+// ---- phase 1 (sumcheck.rs:1067-1380)
+// round j's sizes: the half lengths of the reference's loop and the per-instance domain sizes of the round
+int Prover::p1_advance(Phase1& s, size_t j) {
+  const int mode = p1_mode(j);
+  if (s.cons_len > 1) s.cons_len /= 2;
+  else if (s.proof_len > 1) s.proof_len /= 2;
+  else s.instance_len /= 2;
+  if (mode != MODE_P)
+    for (size_t p = 0; p < s.sc_np.size(); p++) {  // instance_len >= P here: every instance takes part
+      if (mode == MODE_X && s.sc_nc[p] > 1) s.sc_nc[p] /= 2;
+      if (mode == MODE_Q && s.sc_np[p] > 1) s.sc_np[p] /= 2;
+    }
+  return mode;
+}
+// round j's evaluation is enqueued right after round j-1's folds, so it runs on the device while the host finishes
+// round j-1's proof (comm_eval, DotProductProof); eval_wait then collects (e0, e2, e3)
+int Prover::p1_launch_single(Phase1& s, size_t j, const FoldPlan* fold) {
+  const int mode = p1_advance(s, j);
+  if (mode == MODE_P) {
+    std::vector<size_t> ones(P, 1);
+    return phase1_eval(ctx, *s.T, mode, s.proof_len, s.cons_len, s.instance_len, ones, ones, cy.Ap, s.Aq, s.Ax, s.T->d,
+                       s.TB, s.TC, cy.partials, nullptr);
   }
-  // k_spmv gathers from the witness itself, so the Z fill only has to land before phase 2. On the second stream it
-  // is queued once phase 1's round SPG_Z_AFTER (default 4) has been evaluated, and runs beside the later, smaller
-  // rounds: overlapping k_spmv or the first, HBM-bound rounds, the kernels slow each other (rocprof and same-box
-  // A/Bs: DESIGN §4, round 4). SPG_Z_SIDE=0 fills it in order here.
-  bool z_queued = false;
-  static const size_t z_after = getenv("SPG_Z_AFTER") ? (size_t)atol(getenv("SPG_Z_AFTER")) : 4;
-  auto queue_z_fill = [&]() -> int {
-    if (z_queued) return 0;
-    z_queued = true;
-    const hipStream_t main_stream = ctx->stream;
-    if (z_side) {
-      SPG_HIP(ctx, hipEventRecord(ctx->ev_pre, main_stream));
-      SPG_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_pre, 0));
-      ctx->stream = ctx->stream2;
-    }
-    {
-      KScope ks(ctx, "z_fill", 64.0 * ztot);
-      if (z_tiled)  // (ztot is a multiple of 256 then, and so is every instance's offset)
-        hipLaunchKernelGGL(k_z_fill_tiled, dim3((uint32_t)(ztot / 256)), dim3(256), 0, ctx->stream, dz, (int)PLn, dsec,
-                           (int)nws, Zp.d);
-      else
-        hipLaunchKernelGGL(k_z_fill, dim3(blocks_for(ztot)), dim3(256), 0, ctx->stream, dz, (int)PLn, dsec, (int)nws,
-                           Zp.d, (uint64_t)ztot);
-    }
-    ctx->stream = main_stream;
-    SPG_HIP(ctx, hipGetLastError());
-    if (z_side) {
-      SPG_HIP(ctx, hipEventRecord(ctx->ev_side, ctx->stream2));
-      z_join.armed = true;
-    }
-    return 0;
-  };
-  if (!z_side && (rc = queue_z_fill())) return rc;
-
-  lp.lap("setup");
-  // (round evaluations: 3 per workgroup; pair launches: one per element)
-  Fq* partials = (Fq*)ws_get(ctx, WS_PART, std::max(3 * (size_t)kScGridMax, kP1PairMax) * sizeof(Fq) + 64);
-  if (!partials) return set_err(ctx, SPG_E_NOMEM, "partials");
-
-  // ---- phase 1 (sumcheck.rs:1067-1380)
-  FqV rx_all;
-  Fq blind_post1;
-  Fq claims1[4];
-  {
-    size_t rounds = nx + nq + np;
-    ZKRounds zk;
-    size_t cons_len = (size_t)1 << nx, proof_len = (size_t)1 << nq, instance_len = (size_t)1 << np;
-    size_t lenP = instance_len, lenQ = proof_len, lenX = cons_len;
-    std::vector<size_t> sc_np = l_proofs, sc_nc = l_cons;  // local; P rounds use all-ones of length P
-    PqxDev Ac;  // compact Az for the instance rounds; Bc/Cc share its shape
-    Fq *Bc = nullptr, *Cc = nullptr;
-    PqxDev* T = &Az;
-    Fq *TB = Bz, *TC = Cz;
-    const Fq* Ap_l = Ap + p0;  // eq(tau_p) indexed by the global instance in the x / q rounds
-    // round j's evaluation is enqueued right after round j-1's folds, so it runs on the device while the
-    // host finishes round j-1's proof (comm_eval, DotProductProof); eval_wait then collects (e0, e2, e3)
-    auto mode_of = [&](size_t j) { return j < nx ? MODE_X : (j < nx + nq ? MODE_Q : MODE_P); };
-    // round j's sizes: the half lengths of the reference's loop and the per-instance domain sizes of the round
-    auto advance = [&](size_t j) -> int {
-      const int mode = mode_of(j);
-      if (cons_len > 1) cons_len /= 2;
-      else if (proof_len > 1) proof_len /= 2;
-      else instance_len /= 2;
-      if (mode != MODE_P)
-        for (size_t p = 0; p < sc_np.size(); p++) {  // instance_len >= P here: every instance takes part
-          if (mode == MODE_X && sc_nc[p] > 1) sc_nc[p] /= 2;
-          if (mode == MODE_Q && sc_np[p] > 1) sc_np[p] /= 2;
-        }
-      return mode;
-    };
-    auto launch_eval = [&](size_t j, const FoldPlan* fold) -> int {
-      const int mode = advance(j);
-      if (mode == MODE_P) {
-        std::vector<size_t> ones(P, 1);
-        return phase1_eval(ctx, *T, mode, proof_len, cons_len, instance_len, ones, ones, Ap, Aq, Ax, T->d, TB, TC,
-                           partials, nullptr);
-      }
-      return phase1_eval(ctx, *T, mode, proof_len, cons_len, instance_len, sc_np, sc_nc, Ap_l, Aq, Ax, T->d, TB,
-                         TC, partials, nullptr, fold);
-    };
-    // the other halves of the Aq / Ax ping-pong pairs (a fused fold writes the folded side table there)
-    Fq* Aq2 = nullptr;
-    Fq* Ax2 = nullptr;
-    if (sc_fuse_on()) {
-      Aq2 = (Fq*)ws_get(ctx, WS_TQ2, (sizeof(Fq) << nq) + 64);
-      Ax2 = (Fq*)ws_get(ctx, WS_TX2, (sizeof(Fq) << nx) + 64);
-      if (!Aq2 || !Ax2) return set_err(ctx, SPG_E_NOMEM, "eq tables");
-    }
-    // before the first instance round: collect every instance's remaining (Az, Bz, Cz) value
-    auto to_compact = [&]() -> int {
-      std::vector<std::vector<Fq>> full;
-      PqxDev Bt = Az, Ct = Az;
-      Bt.d = Bz;
-      Ct.d = Cz;
-      int r2 = gather_first({&Az, &Bt, &Ct}, full);
-      if (r2) return r2;
-      Fq* buf = (Fq*)ws_get(ctx, WS_C1, 3 * P * sizeof(Fq) + 64);
-      if (!buf) return set_err(ctx, SPG_E_NOMEM, "compact tables");
-      for (int i = 0; i < 3; i++)
-        SPG_HIP(ctx, hipMemcpyAsync(buf + i * P, full[i].data(), P * sizeof(Fq), hipMemcpyHostToDevice, s));
-      SPG_HIP(ctx, hipStreamSynchronize(s));
-      Ac = compact_table(buf, P, P);
-      Bc = buf + P;
-      Cc = buf + 2 * P;
-      T = &Ac;
-      TB = Bc;
-      TC = Cc;
-      return 0;
-    };
-    // ---- two rounds per launch (sumcheck.hip k_phase1_pair; SPG_P1_PAIR=0: one per launch). A pair takes rounds j,
-    // j + 1 of one mode (x or q) when every instance's size in that mode is >= 4 and round j + 1's domain holds at most
-    // SPG_P1_PAIR_MAX (default 8192) points: the latency-bound rounds. Unsharded proofs only (a sharded round sums 3
-    // scalars over the ranks, a pair would sum 15).
-    static const bool pair_on = !getenv("SPG_P1_PAIR") || atoi(getenv("SPG_P1_PAIR")) != 0;
-    static const size_t pair_max = std::min<size_t>(
-        kP1PairMax, getenv("SPG_P1_PAIR_MAX") ? (size_t)atol(getenv("SPG_P1_PAIR_MAX")) : (size_t)8192);
-    auto pair_ok = [&](size_t j) -> bool {
-      if (!pair_on || !Aq2 || nranks != 1 || j + 1 >= rounds || T != &Az) return false;
-      const int m = mode_of(j);
-      if (m == MODE_P || mode_of(j + 1) != m) return false;
-      size_t dom = 0;
-      for (size_t p = 0; p < sc_np.size(); p++) {
-        const size_t N = m == MODE_X ? T->num_inputs[p] : T->num_proofs[p];
-        const size_t Nl = m == MODE_X ? sc_nc[p] : sc_np[p];  // the round's local size before its halving
-        if (N < 4 || N != Nl) return false;
-        dom += m == MODE_X ? sc_np[p] * (N / 4) : (N / 4) * sc_nc[p];
-      }
-      return dom > 0 && dom <= pair_max;
-    };
-    // rounds j, j + 1 in one launch; nf = 1: round j - 1's pending fold (fp), 2: the previous pair's (r1, r2)
-    auto launch_pair = [&](size_t j, int nf, const FoldPlan* fp, const Fq& r1, const Fq& r2) -> int {
-      const int m = advance(j);
-      P1Pair pp;
-      pp.mode = m;
-      pp.c = m == MODE_X ? cons_len : proof_len;  // round j's half length of the mode's eq table
-      for (size_t p = 0; p < sc_np.size(); p++) {
-        const size_t N = m == MODE_X ? T->num_inputs[p] : T->num_proofs[p];
-        if (m == MODE_X) {
-          pp.rows.push_back(sc_np[p]);
-          pp.cols.push_back(N / 4);
-          pp.step_x.push_back(pp.c / (N / 2));
-          pp.step_q.push_back(proof_len / sc_np[p]);
-        } else {
-          pp.rows.push_back(N / 4);
-          pp.cols.push_back(sc_nc[p]);
-          pp.step_q.push_back(pp.c / (N / 2));
-          pp.step_x.push_back(cons_len / sc_nc[p]);
-        }
-      }
-      advance(j + 1);
-      pp.nf = nf;
-      pp.r1 = r1;
-      pp.r2 = r2;
-      Fq*& E = m == MODE_X ? Ax : Aq;
-      Fq*& Ealt = m == MODE_X ? Ax2 : Aq2;
-      size_t& lenE = m == MODE_X ? lenX : lenQ;
-      if (nf == 1) {
-        pp.fstride = fp->stride;
-        pp.fmode = fp->arg.fmode;
-        pp.side_in = fp->arg.side_in;
-        pp.side_out = fp->arg.side_out;
-        pp.side_live = fp->arg.side_half;
-      } else if (nf == 2) {  // the previous pair's folds of this mode's eq table: E (live lenE) -> Ealt (lenE / 4)
-        pp.fmode = m;
-        pp.side_in = E;
-        pp.side_out = Ealt;
-        pp.side_live = lenE / 4;
-        std::swap(E, Ealt);
-        lenE /= 4;
-      }
-      pp.Ap = Ap_l;
-      pp.Aq = Aq;
-      pp.Ax = Ax;
-      pp.B = T->d;
-      pp.C = TB;
-      pp.D = TC;
-      int r = phase1_pair(ctx, *T, pp, partials, nullptr);
-      if (r) return r;
-      // the size bookkeeping of both rounds' folds (the folds themselves ride in the next launch)
-      FoldPlan tmp;
-      if ((r = pqx_fold_plan(ctx, *T, m, &tmp)) || (r = pqx_fold_plan(ctx, *T, m, &tmp))) return r;
-      return 0;
-    };
-    // a pair's pending folds (r1, r2) on their own launch, before a single round or the instance rounds
-    auto fold2x = [&](int m, const Fq& r1, const Fq& r2) -> int {
-      P1Pair pp;
-      pp.mode = m;
-      for (size_t p = 0; p < sc_np.size(); p++) {
-        pp.rows.push_back(T->num_proofs[p]);
-        pp.cols.push_back(T->num_inputs[p]);
-      }
-      Fq*& E = m == MODE_X ? Ax : Aq;
-      Fq*& Ealt = m == MODE_X ? Ax2 : Aq2;
-      size_t& lenE = m == MODE_X ? lenX : lenQ;
-      pp.r1 = r1;
-      pp.r2 = r2;
-      pp.side_in = E;
-      pp.side_out = Ealt;
-      pp.side_live = lenE / 4;
-      pp.B = T->d;
-      pp.C = TB;
-      pp.D = TC;
-      std::swap(E, Ealt);
-      lenE /= 4;
-      return phase1_fold2x(ctx, *T, pp);
-    };
-    if (rounds && nx + nq == 0) rc = to_compact();
-    bool cur_pair = false;  // the launch in flight evaluates rounds j, j + 1
-    if (!rc && rounds) {
-      cur_pair = pair_ok(0);
-      rc = cur_pair ? launch_pair(0, 0, nullptr, fq_zero(), fq_zero()) : launch_eval(0, nullptr);
-    }
-    if (rc) return rc;
-    zk.init(g, tape, rounds, fq_zero(), fq_zero());  // host precomputation while round 0 evaluates
-    for (size_t j = 0; j < rounds;) {
-      if (cur_pair) {
-        const int mode = mode_of(j);
-        Fq ev[15];
-        rc = pair_wait(ctx, ev);
-        if (!rc && (j == z_after || j + 1 == z_after)) rc = queue_z_fill();
-        if (!rc && (j == 1 || j + 1 == 1) && failpoint(ctx, "r1cs_round")) rc = set_err(ctx, SPG_E_HIP, "failpoint r1cs_round");
-        if (rc) return rc;
-        lp.lap("p1_eval");
-        // round j: F(X, 0) + F(X, 1) at X = 0, 2, 3
-        Fq ej[3], ej1[3];
-        pair_round_j(ev, ej);
-        const Fq r_j = zk.begin(g, t, j, ej);
-        zk.finish(g, t, tape, j, r_j);
-        rx_all.push_back(r_j);
-        // round j + 1: the cubics t -> F(t, Y) (Y = 0, 2, 3) at t = r_j
-        pair_round_j1(ev, r_j, ej1);
-        const Fq r_j1 = zk.begin(g, t, j + 1, ej1);
-        lp.lap("p1_host");
-        // the next launch: another pair of this mode (the two folds ride in it), else the folds on their own launch
-        // and a single round (or the compaction before the instance rounds)
-        if (j + 2 < rounds && mode_of(j + 2) == mode && pair_ok(j + 2)) {
-          rc = launch_pair(j + 2, 2, nullptr, r_j, r_j1);
-          cur_pair = true;
-        } else {
-          rc = fold2x(mode, r_j, r_j1);
-          if (!rc && j + 2 == nx + nq && np > 0) rc = to_compact();
-          if (!rc && j + 2 < rounds) {
-            cur_pair = pair_ok(j + 2);
-            rc = cur_pair ? launch_pair(j + 2, 0, nullptr, fq_zero(), fq_zero()) : launch_eval(j + 2, nullptr);
-          }
-        }
-        if (rc) return rc;
-        lp.lap("p1_fold");
-        zk.finish(g, t, tape, j + 1, r_j1);
-        lp.lap("p1_host");
-        rx_all.push_back(r_j1);
-        j += 2;
-        continue;
-      }
-      int mode = mode_of(j);
-      Fq e[3];
-      rc = eval_wait(ctx, e);
-      if (!rc && j == z_after) rc = queue_z_fill();  // round j is done and round j + 1 not yet queued
-      if (!rc && j == 1 && failpoint(ctx, "r1cs_round")) rc = set_err(ctx, SPG_E_HIP, "failpoint r1cs_round");
-      if (!rc && mode != MODE_P) rc = sum_ranks(e);
-      if (rc) return rc;
-      lp.lap("p1_eval");
-      Fq r_j = zk.begin(g, t, j, e);
-      lp.lap("p1_host");
-      // the round's eq factor is bound in the same launch as Az, Bz, Cz: by the next round's evaluation (fused) when
-      // one follows in mode x or q on the same tables, else by a fold launch of its own
-      Fq* side = mode == MODE_P ? Ap : (mode == MODE_Q ? Aq : Ax);
-      size_t& side_len = mode == MODE_P ? lenP : (mode == MODE_Q ? lenQ : lenX);
-      const bool compact_next = j + 1 == nx + nq && np > 0;
-      const int next_mode = mode_of(j + 1);
-      cur_pair = false;
-      if (Aq2 && mode != MODE_P && j + 1 < rounds && !compact_next && next_mode != MODE_P) {
-        FoldPlan fp;
-        rc = pqx_fold_plan(ctx, *T, mode, &fp);
-        Fq*& cur = mode == MODE_Q ? Aq : Ax;
-        Fq*& alt = mode == MODE_Q ? Aq2 : Ax2;
-        fp.arg.r = r_j;
-        fp.arg.fmode = mode;
-        fp.arg.side_in = cur;
-        fp.arg.side_out = alt;
-        fp.arg.side_half = (uint32_t)(side_len / 2);
-        std::swap(cur, alt);
-        side_len /= 2;
-        if (!rc) {
-          cur_pair = pair_ok(j + 1);
-          rc = cur_pair ? launch_pair(j + 1, 1, &fp, r_j, fq_zero()) : launch_eval(j + 1, &fp);
-        }
-      } else {
-        rc = pqx_bound(ctx, *T, TB, TC, r_j, mode, side, side_len);
-        side_len /= 2;
-        if (!rc && compact_next) rc = to_compact();
-        if (!rc && j + 1 < rounds) {
-          cur_pair = pair_ok(j + 1);
-          rc = cur_pair ? launch_pair(j + 1, 0, nullptr, fq_zero(), fq_zero()) : launch_eval(j + 1, nullptr);
-        }
-      }
-      if (rc) return rc;
-      lp.lap("p1_fold");
-      zk.finish(g, t, tape, j, r_j);
-      lp.lap("p1_host");
-      rx_all.push_back(r_j);
-      j++;
-    }
-    Fq a[6];  // eq factors, then Az, Bz, Cz (a single instance: it sits on this (only) rank's local tables)
-    rc = np == 0 ? d2h_multi(ctx, {{Ap, 1}, {Aq, 1}, {Ax, 1}, {Az.d, 1}, {Bz, 1}, {Cz, 1}}, a)
-                 : d2h_multi(ctx, {{Ap, 1}, {Aq, 1}, {Ax, 1}, {T->d, 1}, {TB, 1}, {TC, 1}}, a);
-    if (rc) return rc;
-    claims1[1] = a[3];
-    claims1[2] = a[4];
-    claims1[3] = a[5];
-    claims1[0] = fq_mul(fq_mul(a[0], a[1]), a[2]);
-    blind_post1 = zk.blinds_evals[rounds - 1];
-    pf.sc1 = std::move(zk.out);
-  }
-  lp.lap("p1_claims");
-  FqV rx_rev(rx_all.begin(), rx_all.begin() + nx), rq_rev(rx_all.begin() + nx, rx_all.begin() + nx + nq),
-      rp(rx_all.begin() + nx + nq, rx_all.end());
-  FqV rx(rx_rev.rbegin(), rx_rev.rend()), rq(rq_rev.rbegin(), rq_rev.rend());
-  // eq(rx) of phase 2 depends on phase 1's challenges alone: on the device while the host runs the sigma protocols
-  Fq* eq_rx = (Fq*)ws_get(ctx, WS_EQRX, (sizeof(Fq) << nx) + 64);
-  if (!eq_rx) return set_err(ctx, SPG_E_NOMEM, "eq(rx)");
-  rc = eq_table(ctx, rx, eq_rx);
+  return phase1_eval(ctx, *s.T, mode, s.proof_len, s.cons_len, s.instance_len, s.sc_np, s.sc_nc, s.Ap_l, s.Aq, s.Ax,
+                     s.T->d, s.TB, s.TC, cy.partials, nullptr, fold);
+}
+// before the first instance round: collect every instance's remaining (Az, Bz, Cz) value
+int Prover::p1_to_compact(Phase1& s) {
+  std::vector<std::vector<Fq>> full;
+  PqxDev Bt = cy.Az, Ct = cy.Az;
+  Bt.d = cy.Bz;
+  Ct.d = cy.Cz;
+  int rc = gather_first({&cy.Az, &Bt, &Ct}, full);
   if (rc) return rc;
-  Fq tau_claim = claims1[0], Az_claim = claims1[1], Bz_claim = claims1[2], Cz_claim = claims1[3];
-  Fq Az_blind = tape.scalar("Az_blind"), Bz_blind = tape.scalar("Bz_blind"), Cz_blind = tape.scalar("Cz_blind"),
-     prod_blind = tape.scalar("prod_Az_Bz_blind");
-  Pt comm_Cz, comm_Az, comm_Bz, comm_prod;
-  Fq prod = fq_mul(Az_claim, Bz_claim);
-  Fq blind_expected1 = fq_mul(tau_claim, fq_sub(prod_blind, Cz_blind));
-  Fq claim_post1 = fq_mul(fq_sub(prod, Cz_claim), tau_claim);
-  // every point of the three sigma protocols in one host burst ahead of the transcript sequence (SPG_SIGMA_AHEAD=0:
-  // each protocol commits on its own)
-  static const bool sigma_ahead = !getenv("SPG_SIGMA_AHEAD") || atoi(getenv("SPG_SIGMA_AHEAD")) != 0;
+  Fq* buf = (Fq*)ws_get(ctx, WS_C1, 3 * P * sizeof(Fq) + 64);
+  if (!buf) return set_err(ctx, SPG_E_NOMEM, "compact tables");
+  for (int i = 0; i < 3; i++)
+    SPG_HIP(ctx, hipMemcpyAsync(buf + i * P, full[i].data(), P * sizeof(Fq), hipMemcpyHostToDevice, ctx->stream));
+  SPG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  s.Ac = compact_table(buf, P, P);
+  s.T = &s.Ac;
+  s.TB = buf + P;
+  s.TC = buf + 2 * P;
+  return 0;
+}
+// Two rounds per launch (sumcheck.hip k_phase1_pair; SPG_P1_PAIR=0: one per launch). A pair takes rounds j, j + 1 of
+// one mode (x or q) when every instance's size in that mode is >= 4 and round j + 1's domain holds at most
+// SPG_P1_PAIR_MAX (default 8192) points: the latency-bound rounds. Unsharded proofs only (a sharded round sums 3
+// scalars over the ranks, a pair would sum 15).
+bool Prover::p1_pair_ok(const Phase1& s, size_t j) const {
+  if (!kn.p1_pair || !s.Aq2 || nranks != 1 || j + 1 >= s.rounds || s.T != &cy.Az) return false;
+  const int m = p1_mode(j);
+  if (m == MODE_P || p1_mode(j + 1) != m) return false;
+  size_t dom = 0;
+  for (size_t p = 0; p < s.sc_np.size(); p++) {
+    const size_t N = m == MODE_X ? s.T->num_inputs[p] : s.T->num_proofs[p];
+    const size_t Nl = m == MODE_X ? s.sc_nc[p] : s.sc_np[p];  // the round's local size before its halving
+    if (N < 4 || N != Nl) return false;
+    dom += m == MODE_X ? s.sc_np[p] * (N / 4) : (N / 4) * s.sc_nc[p];
+  }
+  return dom > 0 && dom <= kn.p1_pair_max;
+}
+// rounds j, j + 1 in one launch; nf = 1: round j - 1's pending fold (fp), 2: the previous pair's (r1, r2)
+int Prover::p1_launch_pair(Phase1& s, size_t j, int nf, const FoldPlan* fp, const Fq& r1, const Fq& r2) {
+  const int m = p1_advance(s, j);
+  P1Pair pp;
+  pp.mode = m;
+  pp.c = m == MODE_X ? s.cons_len : s.proof_len;  // round j's half length of the mode's eq table
+  for (size_t p = 0; p < s.sc_np.size(); p++) {
+    const size_t N = m == MODE_X ? s.T->num_inputs[p] : s.T->num_proofs[p];
+    if (m == MODE_X) {
+      pp.rows.push_back(s.sc_np[p]);
+      pp.cols.push_back(N / 4);
+      pp.step_x.push_back(pp.c / (N / 2));
+      pp.step_q.push_back(s.proof_len / s.sc_np[p]);
+    } else {
+      pp.rows.push_back(N / 4);
+      pp.cols.push_back(s.sc_nc[p]);
+      pp.step_q.push_back(pp.c / (N / 2));
+      pp.step_x.push_back(s.cons_len / s.sc_nc[p]);
+    }
+  }
+  p1_advance(s, j + 1);
+  pp.nf = nf;
+  pp.r1 = r1;
+  pp.r2 = r2;
+  Fq*& E = m == MODE_X ? s.Ax : s.Aq;
+  Fq*& Ealt = m == MODE_X ? s.Ax2 : s.Aq2;
+  size_t& lenE = m == MODE_X ? s.lenX : s.lenQ;
+  if (nf == 1) {
+    pp.fstride = fp->stride;
+    pp.fmode = fp->arg.fmode;
+    pp.side_in = fp->arg.side_in;
+    pp.side_out = fp->arg.side_out;
+    pp.side_live = fp->arg.side_half;
+  } else if (nf == 2) {  // the previous pair's folds of this mode's eq table: E (live lenE) -> Ealt (lenE / 4)
+    pp.fmode = m;
+    pp.side_in = E;
+    pp.side_out = Ealt;
+    pp.side_live = lenE / 4;
+    std::swap(E, Ealt);
+    lenE /= 4;
+  }
+  pp.Ap = s.Ap_l;
+  pp.Aq = s.Aq;
+  pp.Ax = s.Ax;
+  pp.B = s.T->d;
+  pp.C = s.TB;
+  pp.D = s.TC;
+  int rc = phase1_pair(ctx, *s.T, pp, cy.partials, nullptr);
+  if (rc) return rc;
+  // the size bookkeeping of both rounds' folds (the folds themselves ride in the next launch)
+  FoldPlan tmp;
+  if ((rc = pqx_fold_plan(ctx, *s.T, m, &tmp)) || (rc = pqx_fold_plan(ctx, *s.T, m, &tmp))) return rc;
+  return 0;
+}
+// a pair's pending folds (r1, r2) on their own launch, before a single round or the instance rounds
+int Prover::p1_fold2x(Phase1& s, int m, const Fq& r1, const Fq& r2) {
+  P1Pair pp;
+  pp.mode = m;
+  for (size_t p = 0; p < s.sc_np.size(); p++) {
+    pp.rows.push_back(s.T->num_proofs[p]);
+    pp.cols.push_back(s.T->num_inputs[p]);
+  }
+  Fq*& E = m == MODE_X ? s.Ax : s.Aq;
+  Fq*& Ealt = m == MODE_X ? s.Ax2 : s.Aq2;
+  size_t& lenE = m == MODE_X ? s.lenX : s.lenQ;
+  pp.r1 = r1;
+  pp.r2 = r2;
+  pp.side_in = E;
+  pp.side_out = Ealt;
+  pp.side_live = lenE / 4;
+  pp.B = s.T->d;
+  pp.C = s.TB;
+  pp.D = s.TC;
+  std::swap(E, Ealt);
+  lenE /= 4;
+  return phase1_fold2x(ctx, *s.T, pp);
+}
+// The launch form after round j_next - 1's challenge, `pending` folds not yet in the tables (0: the first launch; 1: a
+// single round's; 2: a pair's). A single round's fold rides in the next evaluation (fused) when one follows in mode x
+// or q on the same tables; a pair's two ride in another pair of its mode. Else the folds take a launch of their own
+// and the compaction, when the instance rounds come next, follows it. Whether the next launch is a pair (p1_pair_ok)
+// shows in the tables' sizes once a single round's fold is booked or launched: rounds = 0 until then, and the caller
+// asks again with nothing pending.
+NextLaunch Prover::p1_next_launch(const Phase1& s, size_t j_next, int pending) const {
+  if (pending == 0) return {false, j_next >= s.rounds ? 0 : (p1_pair_ok(s, j_next) ? 2 : 1)};
+  const int mode = p1_mode(j_next - 1), next_mode = p1_mode(j_next);
+  if (pending == 2) {
+    const bool again = j_next < s.rounds && next_mode == mode && p1_pair_ok(s, j_next);
+    return {again, again ? 2 : 0};
+  }
+  const bool compact_next = j_next == sh.nx + sh.nq && sh.np > 0;
+  return {s.Aq2 && mode != MODE_P && j_next < s.rounds && !compact_next && next_mode != MODE_P, 0};
+}
+// applies or books the pending folds of challenges r1 (, r2) as p1_next_launch says, then launches round j_next
+int Prover::p1_launch_next(Phase1& s, size_t j_next, int pending, const Fq& r1, const Fq& r2) {
+  const NextLaunch n = p1_next_launch(s, j_next, pending);
+  const bool ride = n.ride;
+  const int mode = pending ? p1_mode(j_next - 1) : 0;
+  FoldPlan fp;
+  int rc = 0;
+  if (pending == 1 && ride) {  // the round's eq factor is bound in the same launch as Az, Bz, Cz
+    rc = pqx_fold_plan(ctx, *s.T, mode, &fp);
+    Fq*& cur = mode == MODE_Q ? s.Aq : s.Ax;
+    Fq*& alt = mode == MODE_Q ? s.Aq2 : s.Ax2;
+    size_t& side_len = mode == MODE_Q ? s.lenQ : s.lenX;
+    fp.arg.r = r1;
+    fp.arg.fmode = mode;
+    fp.arg.side_in = cur;
+    fp.arg.side_out = alt;
+    fp.arg.side_half = (uint32_t)(side_len / 2);
+    std::swap(cur, alt);
+    side_len /= 2;
+  } else if (pending == 1) {
+    Fq* side = mode == MODE_P ? cy.Ap : (mode == MODE_Q ? s.Aq : s.Ax);
+    size_t& side_len = mode == MODE_P ? s.lenP : (mode == MODE_Q ? s.lenQ : s.lenX);
+    rc = pqx_bound(ctx, *s.T, s.TB, s.TC, r1, mode, side, side_len);
+    side_len /= 2;
+  } else if (pending == 2 && !ride) {
+    rc = p1_fold2x(s, mode, r1, r2);
+  }
+  if (!rc && pending && !ride && j_next == sh.nx + sh.nq && sh.np > 0) rc = p1_to_compact(s);
+  if (rc) return rc;
+  const int nf = ride ? pending : 0;
+  const int rounds = pending && !n.rounds ? p1_next_launch(s, j_next, 0).rounds : n.rounds;
+  s.cur_pair = rounds == 2;
+  if (rounds == 2) return p1_launch_pair(s, j_next, nf, &fp, nf ? r1 : fq_zero(), nf == 2 ? r2 : fq_zero());
+  return rounds ? p1_launch_single(s, j_next, nf ? &fp : nullptr) : 0;
+}
+// a single round in flight: its values, its challenge, the next launch, the rest of its proof
+int Prover::p1_round_single(Phase1& s, size_t j, ZFill& zf) {
+  const int mode = p1_mode(j);
+  Fq e[3];
+  int rc = eval_wait(ctx, e);
+  if (!rc && j == kn.z_after) rc = zf.queue();  // round j is done and round j + 1 not yet queued
+  if (!rc && j == 1 && failpoint(ctx, "r1cs_round")) rc = set_err(ctx, SPG_E_HIP, "failpoint r1cs_round");
+  if (!rc && mode != MODE_P) rc = sum_ranks(e);
+  if (rc) return rc;
+  lp.lap("p1_eval");
+  const Fq r_j = s.zk.begin(g, t, j, e);
+  lp.lap("p1_host");
+  if ((rc = p1_launch_next(s, j + 1, 1, r_j, fq_zero()))) return rc;
+  lp.lap("p1_fold");
+  s.zk.finish(g, t, tape, j, r_j);
+  lp.lap("p1_host");
+  s.r.push_back(r_j);
+  return 1;
+}
+// the pair arm: round j is F(X, 0) + F(X, 1) at X = 0, 2, 3; round j + 1 the cubics t -> F(t, Y) (Y = 0, 2, 3) at
+// t = r_j
+template <class Ph>
+int Prover::round_pair_arm(Ph& s, size_t j, const Fq ev[15], const char* const laps[3],
+                           int (Prover::*launch_next)(Ph&, size_t, int, const Fq&, const Fq&)) {
+  lp.lap(laps[0]);
+  Fq ej[3], ej1[3];
+  pair_round_j(ev, ej);
+  const Fq r_j = s.zk.begin(g, t, j, ej);
+  s.zk.finish(g, t, tape, j, r_j);
+  s.r.push_back(r_j);
+  pair_round_j1(ev, r_j, ej1);
+  const Fq r_j1 = s.zk.begin(g, t, j + 1, ej1);
+  lp.lap(laps[1]);
+  if (int rc = (this->*launch_next)(s, j + 2, 2, r_j, r_j1)) return rc;
+  lp.lap(laps[2]);
+  s.zk.finish(g, t, tape, j + 1, r_j1);
+  lp.lap(laps[1]);
+  s.r.push_back(r_j1);
+  return 2;
+}
+int Prover::p1_round_pair(Phase1& s, size_t j, ZFill& zf) {
+  static const char* const laps[3] = {"p1_eval", "p1_host", "p1_fold"};
+  Fq ev[15];
+  int rc = pair_wait(ctx, ev);
+  if (!rc && (j == kn.z_after || j + 1 == kn.z_after)) rc = zf.queue();
+  if (!rc && (j == 1 || j + 1 == 1) && failpoint(ctx, "r1cs_round")) rc = set_err(ctx, SPG_E_HIP, "failpoint r1cs_round");
+  if (rc) return rc;
+  return round_pair_arm(s, j, ev, laps, &Prover::p1_launch_next);
+}
+int Prover::run_phase1(ZFill& zf, FqV& r_all) {
+  const size_t nx = sh.nx, nq = sh.nq, np = sh.np;
+  Phase1 s;
+  s.rounds = nx + nq + np;
+  s.cons_len = s.lenX = (size_t)1 << nx, s.proof_len = s.lenQ = (size_t)1 << nq;
+  s.instance_len = s.lenP = (size_t)1 << np;
+  s.sc_np = sh.l_proofs, s.sc_nc = sh.l_cons;
+  s.T = &cy.Az, s.TB = cy.Bz, s.TC = cy.Cz;
+  s.Aq = cy.Aq, s.Ax = cy.Ax, s.Ap_l = cy.Ap + p0;
+  if (kn.sc_fuse) {
+    s.Aq2 = (Fq*)ws_get(ctx, WS_TQ2, (sizeof(Fq) << nq) + 64);
+    s.Ax2 = (Fq*)ws_get(ctx, WS_TX2, (sizeof(Fq) << nx) + 64);
+    if (!s.Aq2 || !s.Ax2) return set_err(ctx, SPG_E_NOMEM, "eq tables");
+  }
+  int rc = s.rounds && nx + nq == 0 ? p1_to_compact(s) : 0;
+  if (!rc) rc = p1_launch_next(s, 0, 0, fq_zero(), fq_zero());
+  if (rc) return rc;
+  s.zk.init(g, tape, s.rounds, fq_zero(), fq_zero());  // host precomputation while round 0 evaluates
+  for (size_t j = 0; j < s.rounds;) {
+    const int n = s.cur_pair ? p1_round_pair(s, j, zf) : p1_round_single(s, j, zf);
+    if (n < 0) return n;
+    j += (size_t)n;
+  }
+  Fq a[6];  // eq factors, then Az, Bz, Cz (a single instance: it sits on this (only) rank's local tables)
+  rc = np == 0 ? d2h_multi(ctx, {{cy.Ap, 1}, {s.Aq, 1}, {s.Ax, 1}, {cy.Az.d, 1}, {cy.Bz, 1}, {cy.Cz, 1}}, a)
+               : d2h_multi(ctx, {{cy.Ap, 1}, {s.Aq, 1}, {s.Ax, 1}, {s.T->d, 1}, {s.TB, 1}, {s.TC, 1}}, a);
+  if (rc) return rc;
+  cy.claims1[1] = a[3];
+  cy.claims1[2] = a[4];
+  cy.claims1[3] = a[5];
+  cy.claims1[0] = fq_mul(fq_mul(a[0], a[1]), a[2]);
+  cy.blind_post1 = s.zk.blinds_evals[s.rounds - 1];
+  pf.sc1 = std::move(s.zk.out);
+  r_all = std::move(s.r);
+  return 0;
+}
+
+// the claims' blinds and commitments, and the three sigma protocols on them
+void Prover::sigma1() {
+  const Fq tau_claim = cy.claims1[0], Az_claim = cy.claims1[1], Bz_claim = cy.claims1[2], Cz_claim = cy.claims1[3];
+  cy.Az_blind = tape.scalar("Az_blind"), cy.Bz_blind = tape.scalar("Bz_blind"), cy.Cz_blind = tape.scalar("Cz_blind");
+  const Fq prod_blind = tape.scalar("prod_Az_Bz_blind");
+  const Fq prod = fq_mul(Az_claim, Bz_claim);
+  const Fq blind_expected1 = fq_mul(tau_claim, fq_sub(prod_blind, cy.Cz_blind));
+  const Fq claim_post1 = fq_mul(fq_sub(prod, Cz_claim), tau_claim);
   Sigma1Pre sp;
-  if (sigma_ahead)
-    sigma1_points(g, g.gens_1, tape, Cz_claim, Cz_blind, Az_claim, Az_blind, Bz_claim, Bz_blind, prod, prod_blind,
-                  claim_post1, blind_expected1, claim_post1, blind_post1, &sp);
-  pf.pok = knowledge_prove(g, g.gens_1, t, tape, Cz_claim, Cz_blind, &comm_Cz, sigma_ahead ? sp.k : nullptr);
-  pf.prod = product_prove(g, g.gens_1, t, tape, Az_claim, Az_blind, Bz_claim, Bz_blind, prod, prod_blind, &comm_Az,
-                          &comm_Bz, &comm_prod, sigma_ahead ? sp.p : nullptr);
-  t.point("comm_Az_claim", comm_Az);
-  t.point("comm_Bz_claim", comm_Bz);
-  t.point("comm_Cz_claim", comm_Cz);
-  t.point("comm_prod_Az_Bz_claims", comm_prod);
-  pf.eq1 = equality_prove(g, g.gens_1, t, tape, claim_post1, blind_expected1, claim_post1, blind_post1,
-                          sigma_ahead ? sp.e : nullptr);
-  lp.lap("sigma1");
-  // ---- phase 2 inputs
-  Fq r_A = t.challenge("challenge_Az"), r_B = t.challenge("challenge_Bz"), r_C = t.challenge("challenge_Cz");
-  Fq claim2 = fq_add(fq_add(fq_mul(r_A, Az_claim), fq_mul(r_B, Bz_claim)), fq_mul(r_C, Cz_claim));
-  Fq blind2 = fq_add(fq_add(fq_mul(r_A, Az_blind), fq_mul(r_B, Bz_blind)), fq_mul(r_C, Cz_blind));
-  const bool single = inst.num_instances == 1;
+  if (kn.sigma_ahead)
+    sigma1_points(g, g.gens_1, tape, Cz_claim, cy.Cz_blind, Az_claim, cy.Az_blind, Bz_claim, cy.Bz_blind, prod,
+                  prod_blind, claim_post1, blind_expected1, claim_post1, cy.blind_post1, &sp);
+  pf.pok = knowledge_prove(g, g.gens_1, t, tape, Cz_claim, cy.Cz_blind, &cy.comm_Cz, kn.sigma_ahead ? sp.k : nullptr);
+  pf.prod = product_prove(g, g.gens_1, t, tape, Az_claim, cy.Az_blind, Bz_claim, cy.Bz_blind, prod, prod_blind,
+                          &cy.comm_Az, &cy.comm_Bz, &cy.comm_prod, kn.sigma_ahead ? sp.p : nullptr);
+  t.point("comm_Az_claim", cy.comm_Az);
+  t.point("comm_Bz_claim", cy.comm_Bz);
+  t.point("comm_Cz_claim", cy.comm_Cz);
+  t.point("comm_prod_Az_Bz_claims", cy.comm_prod);
+  pf.eq1 = equality_prove(g, g.gens_1, t, tape, claim_post1, blind_expected1, claim_post1, cy.blind_post1,
+                          kn.sigma_ahead ? sp.e : nullptr);
+}
+
+// phase 2's inputs: the claim, ABC = r_A A + r_B B + r_C C at rx (k_abc), Z joined and bound at rq_rev, eq(rp)
+int Prover::phase2_prep(ZFill& zf) {
+  const Fq r_A = t.challenge("challenge_Az"), r_B = t.challenge("challenge_Bz"), r_C = t.challenge("challenge_Cz");
+  cy.claim2 = fq_add(fq_add(fq_mul(r_A, cy.claims1[1]), fq_mul(r_B, cy.claims1[2])), fq_mul(r_C, cy.claims1[3]));
+  cy.blind2 = fq_add(fq_add(fq_mul(r_A, cy.Az_blind), fq_mul(r_B, cy.Bz_blind)), fq_mul(r_C, cy.Cz_blind));
   // ABC: the shared matrix once (every rank), or this rank's instances
-  const size_t Ab0 = single ? 0 : p0, Abn = single ? 1 : PLn;
-  PqxDev ABC;
-  ABC.zlen = Abn;
-  ABC.off.resize(Abn);
-  ABC.anp.assign(Abn, 1);
-  ABC.anw.assign(Abn, nws);
-  ABC.ani.assign(num_inputs.begin() + Ab0, num_inputs.begin() + Ab0 + Abn);
-  size_t btot = 0;
-  for (size_t p = 0; p < Abn; p++) {
-    ABC.off[p] = btot;
-    btot += nws * num_inputs[Ab0 + p];
-  }
-  ABC.total = btot;
-  ABC.num_instances = npow2(inst.num_instances);
-  ABC.max_num_proofs = 1;
-  ABC.num_witness_secs = npow2(nws);
-  ABC.max_num_inputs = Y;
+  const size_t Ab0 = sh.single ? 0 : p0, Abn = sh.single ? 1 : sh.PLn;
+  PqxDev& ABC = cy.ABC;
+  ABC = pqx_shape(std::vector<size_t>(Abn, 1), nws, {num_inputs.begin() + Ab0, num_inputs.begin() + Ab0 + Abn},
+                  npow2(inst.num_instances), 1, npow2(nws), Y);
   ABC.num_proofs.assign(P, 1);
   ABC.num_inputs.assign(num_inputs.begin() + Ab0, num_inputs.end());
+  const size_t btot = ABC.total;
   ABC.d = (Fq*)ws_get(ctx, WS_ABC, btot * sizeof(Fq) + 64);
   if (!ABC.d) return set_err(ctx, SPG_E_NOMEM, "ABC");
+  int rc = 0;
   {
     std::vector<AbcDesc> ad(Abn);
     double visits = 0;
     for (size_t p = 0; p < Abn; p++) {
+      const size_t pi = Ab0 + p;
       ad[p].dom_off = ABC.off[p];
       ad[p].out_off = ABC.off[p];
-      ad[p].pi = (uint32_t)(Ab0 + p);
-      ad[p].ni = (uint32_t)num_inputs[Ab0 + p];
-      ad[p].lg_ni = (uint32_t)lg2(num_inputs[Ab0 + p]);
-      size_t pi = Ab0 + p;
+      ad[p].pi = (uint32_t)pi;
+      ad[p].ni = (uint32_t)num_inputs[pi];
+      ad[p].lg_ni = (uint32_t)lg2(num_inputs[pi]);
       visits += inst.nnz[3 * pi] + inst.nnz[3 * pi + 1] + inst.nnz[3 * pi + 2];
     }
     AbcDesc* dad;
@@ -1242,244 +1389,347 @@ int Prover::run_inner(Laps& lp) {
     if (!rc) rc = flush_desc();
     if (rc) return rc;
     KScope ks(ctx, "eval_table_abc", 32.0 * btot + 4.0 * btot + 68.0 * visits);
-    hipLaunchKernelGGL(k_abc, dim3(blocks_for(btot)), dim3(256), 0, s, dad, (int)Abn, dmd, inst.d_colptr, inst.d_crow,
-                       inst.d_cval, eq_rx, (uint32_t)Y, r_A, r_B, r_C, ABC.d, (uint64_t)btot);
+    hipLaunchKernelGGL(k_abc, dim3(blocks_for(btot)), dim3(256), 0, ctx->stream, dad, (int)Abn, cy.dmd, inst.d_colptr,
+                       inst.d_crow, inst.d_cval, cy.eq_rx, (uint32_t)Y, r_A, r_B, r_C, ABC.d, (uint64_t)btot);
     SPG_HIP(ctx, hipGetLastError());
   }
-  rc = queue_z_fill();  // (phase 1 had no rounds)
-  if (!rc) rc = z_join.join();  // the Z table's first use
+  rc = zf.queue();  // (phase 1 had no rounds)
+  if (!rc) rc = zf.join();  // the Z table's first use
   if (rc) return rc;
-  // Z.bound_poly_vars_rq(rq_rev): every q fold in one pass over Z against eq(rq_rev) (k_pqx_bound_q; SPG_Q_BOUND_ALL=0:
-  // one fold launch per challenge, each a read-write pass over the live rows)
-  static const bool q_all = !getenv("SPG_Q_BOUND_ALL") || atoi(getenv("SPG_Q_BOUND_ALL")) != 0;
-  if (q_all && rq_rev.size() >= 2) {
+  // Z.bound_poly_vars_rq(rq_rev): every q fold in one pass over Z against eq(rq_rev), or one fold launch per
+  // challenge, each a read-write pass over the live rows
+  const FqV& rq_rev = cy.rq_rev;
+  if (kn.q_bound_all && rq_rev.size() >= 2) {
     Fq* eq_q = (Fq*)ws_get(ctx, WS_EQQ, (sizeof(Fq) << rq_rev.size()) + 64);
     if (!eq_q) return set_err(ctx, SPG_E_NOMEM, "eq(rq)");
     rc = eq_table(ctx, rq_rev, eq_q);
-    if (!rc) rc = pqx_bound_q_all(ctx, Zp, eq_q, rq_rev.size());
+    if (!rc) rc = pqx_bound_q_all(ctx, cy.Zp, eq_q, rq_rev.size());
     if (rc) return rc;
   } else {
-    for (size_t k = 0; k < rq_rev.size(); k++) {
-      rc = pqx_bound(ctx, Zp, nullptr, nullptr, rq_rev[k], MODE_Q);
-      if (rc) return rc;
-    }
+    for (size_t k = 0; k < rq_rev.size(); k++)
+      if ((rc = pqx_bound(ctx, cy.Zp, nullptr, nullptr, rq_rev[k], MODE_Q))) return rc;
   }
-  Fq* eq_p = (Fq*)ws_get(ctx, WS_EQP, (sizeof(Fq) << np) + 64);
-  if (!eq_p) return set_err(ctx, SPG_E_NOMEM, "eq(rp)");
-  rc = eq_table(ctx, rp, eq_p);
+  cy.eq_p = (Fq*)ws_get(ctx, WS_EQP, (sizeof(Fq) << sh.np) + 64);
+  if (!cy.eq_p) return set_err(ctx, SPG_E_NOMEM, "eq(rp)");
+  return eq_table(ctx, cy.rp, cy.eq_p);
+}
+
+// ---- phase 2 (sumcheck.rs:788-1065)
+int Prover::p2_launch_single(Phase2& s, size_t j, const Fold2* fold) {
+  const int mode = p2_mode(j);
+  if (s.inputs_len > 1) s.inputs_len /= 2;
+  else if (s.ws_len > 1) s.ws_len /= 2;
+  else s.instance_len /= 2;
+  if (mode == MODE_P) {
+    std::vector<size_t> ones(P, 1);
+    return phase2_eval(ctx, *s.TA, *s.TZ, mode, s.instance_len, s.ws_len, nws, sh.single, ones, cy.eq_p, cy.partials,
+                       nullptr);
+  }
+  for (size_t p = 0; p < s.sc_ni.size(); p++)
+    if (mode == MODE_X && s.sc_ni[p] > 1) s.sc_ni[p] /= 2;
+  return phase2_eval(ctx, *s.TA, *s.TZ, mode, s.instance_len, s.ws_len, nws, sh.single, s.sc_ni, s.eq_l, cy.partials,
+                     nullptr, fold);
+}
+// before the first instance round: every instance's remaining Z (and ABC) value
+int Prover::p2_to_compact(Phase2& s) {
+  const bool single = sh.single;
+  hipStream_t st = ctx->stream;
+  std::vector<std::vector<Fq>> full;
+  int rc = single ? gather_first({&cy.Zp}, full) : gather_first({&cy.Zp, &cy.ABC}, full);
   if (rc) return rc;
-
-  lp.lap("p2_prep");
-  // ---- phase 2 (sumcheck.rs:788-1065)
-  FqV ry_all;
-  Fq claims2[3], blind_post2;
-  {
-    size_t rounds = ny + nw + np;
-    ZKRounds zk;
-    size_t inputs_len = (size_t)1 << ny, ws_len = (size_t)1 << nw, instance_len = (size_t)1 << np;
-    size_t lenP = instance_len;
-    std::vector<size_t> sc_ni = l_inputs;
-    PqxDev Zc, ABCc;
-    PqxDev *TZ = &Zp, *TA = &ABC;
-    const Fq* eq_l = eq_p + p0;
-    auto launch_eval = [&](size_t j, const Fold2* fold) -> int {
-      int mode = j < ny ? MODE_X : (j < ny + nw ? MODE_W : MODE_P);
-      if (inputs_len > 1) inputs_len /= 2;
-      else if (ws_len > 1) ws_len /= 2;
-      else instance_len /= 2;
-      if (mode == MODE_P) {
-        std::vector<size_t> ones(P, 1);
-        return phase2_eval(ctx, *TA, *TZ, mode, instance_len, ws_len, nws, single, ones, eq_p, partials,
-                           nullptr);
-      }
-      for (size_t p = 0; p < sc_ni.size(); p++)
-        if (mode == MODE_X && sc_ni[p] > 1) sc_ni[p] /= 2;
-      return phase2_eval(ctx, *TA, *TZ, mode, instance_len, ws_len, nws, single, sc_ni, eq_l, partials,
-                         nullptr, fold);
-    };
-    // one ABC serving every instance is folded into this buffer by a fused round (then the two swap). The fused fold
-    // writes it from the points of local instance 0 (global p0): only when that instance spans ABC's whole width
-    // (num_inputs[0]) -- a sharded rank whose first instance is narrower takes the separate fold
-    const bool fuse2 = sc_fuse_on() && (!single || num_inputs[p0] == num_inputs[0]);
-    Fq* ABC2 = nullptr;
-    if (fuse2 && single) {
-      ABC2 = (Fq*)ws_get(ctx, WS_ABC2, btot * sizeof(Fq) + 64);
-      if (!ABC2) return set_err(ctx, SPG_E_NOMEM, "ABC");
-    }
-    auto to_compact = [&]() -> int {
-      std::vector<std::vector<Fq>> full;
-      int r2 = single ? gather_first({&Zp}, full) : gather_first({&Zp, &ABC}, full);
-      if (r2) return r2;
-      Fq* buf = (Fq*)ws_get(ctx, WS_C2, 2 * P * sizeof(Fq) + 64);
-      if (!buf) return set_err(ctx, SPG_E_NOMEM, "compact tables");
-      SPG_HIP(ctx, hipMemcpyAsync(buf, full[0].data(), P * sizeof(Fq), hipMemcpyHostToDevice, s));
-      if (single) {  // the shared ABC keeps its single (0,0,0,0) element
-        SPG_HIP(ctx, hipMemcpyAsync(buf + P, ABC.d, sizeof(Fq), hipMemcpyDeviceToDevice, s));
-      } else {
-        SPG_HIP(ctx, hipMemcpyAsync(buf + P, full[1].data(), P * sizeof(Fq), hipMemcpyHostToDevice, s));
-      }
-      SPG_HIP(ctx, hipStreamSynchronize(s));
-      Zc = compact_table(buf, P, P);
-      ABCc = compact_table(buf + P, single ? 1 : P, P);
-      TZ = &Zc;
-      TA = &ABCc;
-      return 0;
-    };
-    // ---- two y rounds per launch (sumcheck.hip k_phase2_pair; SPG_P2_PAIR=0: one per launch): rounds j, j + 1 both y
-    // rounds, ABC per instance, every instance's live y size >= 4 (the same in ABC and Z), at most SPG_P2_PAIR_MAX
-    // (default 8192) elements, unsharded. A run of pairs starts with no fold pending (a single round's fold before it is
-    // launched on its own) and ends with k_phase2_fold2x.
-    static const bool p2_pair_on = !getenv("SPG_P2_PAIR") || atoi(getenv("SPG_P2_PAIR")) != 0;
-    static const size_t p2_pair_max = std::min<size_t>(
-        kP1PairMax, getenv("SPG_P2_PAIR_MAX") ? (size_t)atol(getenv("SPG_P2_PAIR_MAX")) : (size_t)8192);
-    const size_t W2 = std::min(ws_len, nws);
-    // (fold_pending: round j - 1's fold is not yet in the tables' sizes; the caller launches it first)
-    auto p2_pair_ok = [&](size_t j, bool fold_pending) -> bool {
-      // (one ABC shared by every instance folds through its ping-pong buffer, as the fused single rounds do)
-      if (!p2_pair_on || (single && !ABC2) || nranks != 1 || j + 1 >= ny || TA != &ABC || TZ != &Zp ||
-          ABC.zlen != (single ? 1 : Zp.zlen))
-        return false;
-      auto live = [&](size_t n) { return fold_pending && n > 1 ? n / 2 : n; };
-      size_t dom = 0;
-      for (size_t p = 0; p < sc_ni.size(); p++) {
-        const size_t N = live(Zp.num_inputs[p]);
-        if (N < 4 || live(ABC.num_inputs[single ? 0 : p]) != N || sc_ni[p] != N) return false;
-        dom += W2 * (N / 4);
-      }
-      return dom > 0 && dom <= p2_pair_max;
-    };
-    // rounds j, j + 1 in one launch; nf = 2: the previous pair's folds (r1, r2) ride in it
-    auto launch_p2pair = [&](int nf, const Fq& r1, const Fq& r2) -> int {
-      for (int k = 0; k < 2; k++) {  // launch_eval's size bookkeeping for both y rounds
-        if (inputs_len > 1) inputs_len /= 2;
-        for (size_t p = 0; p < sc_ni.size(); p++)
-          if (sc_ni[p] > 1) sc_ni[p] /= 2;
-      }
-      P2Pair pp;
-      pp.nf = nf;
-      pp.r1 = r1;
-      pp.r2 = r2;
-      pp.W = W2;
-      pp.eq = eq_l;
-      pp.B_out = single ? ABC2 : nullptr;
-      int r = phase2_pair(ctx, ABC, Zp, pp, partials);
-      if (r) return r;
-      if (single && nf == 2) std::swap(ABC.d, ABC2);  // the folded shared ABC is in the other buffer now
-      FoldPlan tmp;  // the table bookkeeping of both rounds' folds (the folds ride in the next launch)
-      for (int k = 0; k < 2 && !r; k++) {
-        r = pqx_fold_plan(ctx, ABC, MODE_X, &tmp);
-        if (!r) r = pqx_fold_plan(ctx, Zp, MODE_X, &tmp);
-      }
-      return r;
-    };
-    auto p2_fold2x = [&](const Fq& r1, const Fq& r2) -> int {
-      P2Pair pp;
-      pp.nf = 2;
-      pp.r1 = r1;
-      pp.r2 = r2;
-      pp.W = W2;
-      pp.B_out = single ? ABC2 : nullptr;
-      const int r = phase2_fold2x(ctx, ABC, Zp, pp);
-      if (!r && single) std::swap(ABC.d, ABC2);
-      return r;
-    };
-    bool cur_pair = false;  // the launch in flight evaluates rounds j, j + 1
-    if (rounds && ny + nw == 0) rc = to_compact();
-    if (!rc && rounds) {
-      cur_pair = p2_pair_ok(0, false);
-      rc = cur_pair ? launch_p2pair(0, fq_zero(), fq_zero()) : launch_eval(0, nullptr);
-    }
-    if (rc) return rc;
-    zk.init(g, tape, rounds, claim2, blind2);  // host precomputation while round 0 evaluates
-    for (size_t j = 0; j < rounds;) {
-      if (cur_pair) {
-        Fq ev[15], ej[3], ej1[3];
-        rc = pair_wait(ctx, ev);
-        if (rc) return rc;
-        lp.lap("p2_eval");
-        pair_round_j(ev, ej);
-        const Fq r_j = zk.begin(g, t, j, ej);
-        zk.finish(g, t, tape, j, r_j);
-        ry_all.push_back(r_j);
-        pair_round_j1(ev, r_j, ej1);
-        const Fq r_j1 = zk.begin(g, t, j + 1, ej1);
-        lp.lap("p2_host");
-        if (j + 2 < ny && p2_pair_ok(j + 2, false)) {
-          rc = launch_p2pair(2, r_j, r_j1);
-        } else {
-          cur_pair = false;
-          rc = p2_fold2x(r_j, r_j1);
-          if (!rc && j + 2 == ny + nw && np > 0) rc = to_compact();
-          if (!rc && j + 2 < rounds) rc = launch_eval(j + 2, nullptr);
-        }
-        if (rc) return rc;
-        lp.lap("p2_fold");
-        zk.finish(g, t, tape, j + 1, r_j1);
-        lp.lap("p2_host");
-        ry_all.push_back(r_j1);
-        j += 2;
-        continue;
-      }
-      int mode = j < ny ? MODE_X : (j < ny + nw ? MODE_W : MODE_P);
-      Fq e[3];
-      rc = eval_wait(ctx, e);
-      if (!rc && mode != MODE_P) rc = sum_ranks(e);
-      if (rc) return rc;
-      lp.lap("p2_eval");
-      Fq r_j = zk.begin(g, t, j, e);
-      lp.lap("p2_host");
-      const bool compact_next = j + 1 == ny + nw && np > 0;
-      const int next_mode = j + 1 < ny ? MODE_X : (j + 1 < ny + nw ? MODE_W : MODE_P);
-      if (mode == MODE_X && p2_pair_ok(j + 1, true)) {
-        // a run of pairs starts here: this round's fold on its own launch, then the pair (no fold pending in it)
-        rc = pqx_bound2(ctx, *TA, *TZ, r_j, mode);
-        if (!rc) rc = launch_p2pair(0, fq_zero(), fq_zero());
-        cur_pair = true;
-      } else if (fuse2 && mode != MODE_P && j + 1 < rounds && !compact_next && next_mode != MODE_P) {
-        // the fold rides in the next round's evaluation (k_phase2_eval<true>)
-        Fold2 f;
-        rc = pqx_fold_plan(ctx, *TA, mode, &f.a);
-        if (!rc) rc = pqx_fold_plan(ctx, *TZ, mode, &f.z);
-        f.arg.r = r_j;
-        f.arg.fmode = mode;
-        f.arg.fw = f.z.fw;
-        f.arg.ping = single ? 1 : 0;
-        f.arg.b_out = single ? ABC2 : TA->d;
-        if (!rc) rc = launch_eval(j + 1, &f);
-        if (!rc && single) std::swap(TA->d, ABC2);
-      } else {
-        if (mode == MODE_P) { rc = dev_fold_top(ctx, eq_p, lenP, r_j); lenP /= 2; }
-        if (!rc && (mode != MODE_P || !single)) rc = pqx_bound2(ctx, *TA, *TZ, r_j, mode);
-        else if (!rc) rc = pqx_bound(ctx, *TZ, nullptr, nullptr, r_j, mode);
-        if (!rc && compact_next) rc = to_compact();
-        if (!rc && j + 1 < rounds) rc = launch_eval(j + 1, nullptr);
-      }
-      if (rc) return rc;
-      lp.lap("p2_fold");
-      zk.finish(g, t, tape, j, r_j);
-      lp.lap("p2_host");
-      ry_all.push_back(r_j);
-      j++;
-    }
-    rc = d2h_multi(ctx, {{eq_p, 1}, {TA->d, 1}, {TZ->d, 1}}, claims2);
-    if (rc) return rc;
-    blind_post2 = zk.blinds_evals[rounds - 1];
-    pf.sc2 = std::move(zk.out);
+  Fq* buf = (Fq*)ws_get(ctx, WS_C2, 2 * P * sizeof(Fq) + 64);
+  if (!buf) return set_err(ctx, SPG_E_NOMEM, "compact tables");
+  SPG_HIP(ctx, hipMemcpyAsync(buf, full[0].data(), P * sizeof(Fq), hipMemcpyHostToDevice, st));
+  if (single) {  // the shared ABC keeps its single (0,0,0,0) element
+    SPG_HIP(ctx, hipMemcpyAsync(buf + P, cy.ABC.d, sizeof(Fq), hipMemcpyDeviceToDevice, st));
+  } else {
+    SPG_HIP(ctx, hipMemcpyAsync(buf + P, full[1].data(), P * sizeof(Fq), hipMemcpyHostToDevice, st));
   }
-  FqV ry_rev(ry_all.begin(), ry_all.begin() + ny), rw(ry_all.begin() + ny, ry_all.begin() + ny + nw),
-      rp2(ry_all.begin() + ny + nw, ry_all.end());
-  FqV ry(ry_rev.rbegin(), ry_rev.rend());
+  SPG_HIP(ctx, hipStreamSynchronize(st));
+  s.Zc = compact_table(buf, P, P);
+  s.ABCc = compact_table(buf + P, single ? 1 : P, P);
+  s.TZ = &s.Zc;
+  s.TA = &s.ABCc;
+  return 0;
+}
+// Two y rounds per launch (sumcheck.hip k_phase2_pair; SPG_P2_PAIR=0: one per launch): rounds j, j + 1 both y rounds,
+// ABC per instance, every instance's live y size >= 4 (the same in ABC and Z), at most SPG_P2_PAIR_MAX (default 8192)
+// elements, unsharded. A run of pairs starts with no fold pending (a single round's fold before it is launched on its
+// own) and ends with k_phase2_fold2x.
+// (fold_pending: round j - 1's fold is not yet in the tables' sizes; the caller launches it first)
+bool Prover::p2_pair_ok(const Phase2& s, size_t j, bool fold_pending) const {
+  const bool single = sh.single;
+  const PqxDev &ABC = cy.ABC, &Zp = cy.Zp;
+  // (one ABC shared by every instance folds through its ping-pong buffer, as the fused single rounds do)
+  if (!kn.p2_pair || (single && !s.ABC2) || nranks != 1 || j + 1 >= sh.ny || s.TA != &ABC || s.TZ != &Zp ||
+      ABC.zlen != (single ? 1 : Zp.zlen))
+    return false;
+  auto live = [&](size_t n) { return fold_pending && n > 1 ? n / 2 : n; };
+  size_t dom = 0;
+  for (size_t p = 0; p < s.sc_ni.size(); p++) {
+    const size_t N = live(Zp.num_inputs[p]);
+    if (N < 4 || live(ABC.num_inputs[single ? 0 : p]) != N || s.sc_ni[p] != N) return false;
+    dom += s.W2 * (N / 4);
+  }
+  return dom > 0 && dom <= kn.p2_pair_max;
+}
+// y rounds j, j + 1 in one launch; nf = 2: the previous pair's folds (r1, r2) ride in it
+int Prover::p2_launch_pair(Phase2& s, int nf, const Fq& r1, const Fq& r2) {
+  for (int k = 0; k < 2; k++) {  // p2_launch_single's size bookkeeping for both y rounds
+    if (s.inputs_len > 1) s.inputs_len /= 2;
+    for (size_t p = 0; p < s.sc_ni.size(); p++)
+      if (s.sc_ni[p] > 1) s.sc_ni[p] /= 2;
+  }
+  P2Pair pp;
+  pp.nf = nf;
+  pp.r1 = r1;
+  pp.r2 = r2;
+  pp.W = s.W2;
+  pp.eq = s.eq_l;
+  pp.B_out = sh.single ? s.ABC2 : nullptr;
+  int rc = phase2_pair(ctx, cy.ABC, cy.Zp, pp, cy.partials);
+  if (rc) return rc;
+  if (sh.single && nf == 2) std::swap(cy.ABC.d, s.ABC2);  // the folded shared ABC is in the other buffer now
+  FoldPlan tmp;  // the table bookkeeping of both rounds' folds (the folds ride in the next launch)
+  for (int k = 0; k < 2 && !rc; k++) {
+    rc = pqx_fold_plan(ctx, cy.ABC, MODE_X, &tmp);
+    if (!rc) rc = pqx_fold_plan(ctx, cy.Zp, MODE_X, &tmp);
+  }
+  return rc;
+}
+int Prover::p2_fold2x(Phase2& s, const Fq& r1, const Fq& r2) {
+  P2Pair pp;
+  pp.nf = 2;
+  pp.r1 = r1;
+  pp.r2 = r2;
+  pp.W = s.W2;
+  pp.B_out = sh.single ? s.ABC2 : nullptr;
+  const int rc = phase2_fold2x(ctx, cy.ABC, cy.Zp, pp);
+  if (!rc && sh.single) std::swap(cy.ABC.d, s.ABC2);
+  return rc;
+}
+// The launch form after round j_next - 1's challenge, `pending` folds not yet in the tables (as p1_next_launch). A
+// pair's two folds ride in another pair; a single y round before a run of pairs folds on its own launch (the pair
+// starts with nothing pending); else a single round's fold rides in the next evaluation (k_phase2_eval<true>) when
+// one follows in mode y or w on the same tables.
+NextLaunch Prover::p2_next_launch(const Phase2& s, size_t j_next, int pending) const {
+  const int left = j_next < s.rounds ? 1 : 0;
+  if (pending == 0) return {false, left && p2_pair_ok(s, j_next, false) ? 2 : left};
+  if (pending == 2) {
+    const bool again = j_next < sh.ny && p2_pair_ok(s, j_next, false);
+    return {again, again ? 2 : left};
+  }
+  const int mode = p2_mode(j_next - 1);
+  if (mode == MODE_X && p2_pair_ok(s, j_next, true)) return {false, 2};
+  const bool compact_next = j_next == sh.ny + sh.nw && sh.np > 0;
+  return {s.fuse2 && mode != MODE_P && left && !compact_next && p2_mode(j_next) != MODE_P, left};
+}
+// applies or books the pending folds of challenges r1 (, r2) as p2_next_launch says, then launches round j_next
+int Prover::p2_launch_next(Phase2& s, size_t j_next, int pending, const Fq& r1, const Fq& r2) {
+  const NextLaunch n = p2_next_launch(s, j_next, pending);
+  const int mode = pending ? p2_mode(j_next - 1) : 0;
+  const bool single = sh.single;
+  s.cur_pair = n.rounds == 2;
+  if (pending == 2 && n.ride) return p2_launch_pair(s, 2, r1, r2);
+  int rc = 0;
+  if (pending == 1 && n.ride) {
+    Fold2 f;
+    rc = pqx_fold_plan(ctx, *s.TA, mode, &f.a);
+    if (!rc) rc = pqx_fold_plan(ctx, *s.TZ, mode, &f.z);
+    f.arg.r = r1;
+    f.arg.fmode = mode;
+    f.arg.fw = f.z.fw;
+    f.arg.ping = single ? 1 : 0;
+    f.arg.b_out = single ? s.ABC2 : s.TA->d;
+    if (!rc) rc = p2_launch_single(s, j_next, &f);
+    if (!rc && single) std::swap(s.TA->d, s.ABC2);
+    return rc;
+  }
+  if (pending == 2) {
+    rc = p2_fold2x(s, r1, r2);
+  } else if (pending == 1) {
+    if (mode == MODE_P) {
+      rc = dev_fold_top(ctx, cy.eq_p, s.lenP, r1);
+      s.lenP /= 2;
+    }
+    if (!rc && (mode != MODE_P || !single)) rc = pqx_bound2(ctx, *s.TA, *s.TZ, r1, mode);
+    else if (!rc) rc = pqx_bound(ctx, *s.TZ, nullptr, nullptr, r1, mode);
+  }
+  if (!rc && pending && j_next == sh.ny + sh.nw && sh.np > 0) rc = p2_to_compact(s);
+  if (rc) return rc;
+  if (n.rounds == 2) return p2_launch_pair(s, 0, fq_zero(), fq_zero());
+  return n.rounds ? p2_launch_single(s, j_next, nullptr) : 0;
+}
+int Prover::p2_round_single(Phase2& s, size_t j) {
+  Fq e[3];
+  int rc = eval_wait(ctx, e);
+  if (!rc && p2_mode(j) != MODE_P) rc = sum_ranks(e);
+  if (rc) return rc;
+  lp.lap("p2_eval");
+  const Fq r_j = s.zk.begin(g, t, j, e);
+  lp.lap("p2_host");
+  if ((rc = p2_launch_next(s, j + 1, 1, r_j, fq_zero()))) return rc;
+  lp.lap("p2_fold");
+  s.zk.finish(g, t, tape, j, r_j);
+  lp.lap("p2_host");
+  s.r.push_back(r_j);
+  return 1;
+}
+int Prover::p2_round_pair(Phase2& s, size_t j) {
+  static const char* const laps[3] = {"p2_eval", "p2_host", "p2_fold"};
+  Fq ev[15];
+  if (int rc = pair_wait(ctx, ev)) return rc;
+  return round_pair_arm(s, j, ev, laps, &Prover::p2_launch_next);
+}
+int Prover::run_phase2() {
+  const size_t ny = sh.ny, nw = sh.nw, np = sh.np;
+  Phase2 s;
+  s.rounds = ny + nw + np;
+  s.inputs_len = (size_t)1 << ny, s.ws_len = (size_t)1 << nw, s.instance_len = s.lenP = (size_t)1 << np;
+  s.sc_ni = sh.l_inputs;
+  s.TZ = &cy.Zp, s.TA = &cy.ABC;
+  s.eq_l = cy.eq_p + p0;
+  s.W2 = std::min(s.ws_len, nws);
+  // one ABC serving every instance is folded into ABC2 by a fused round (then the two swap). The fused fold writes it
+  // from the points of local instance 0 (global p0): only when that instance spans ABC's whole width (num_inputs[0])
+  // -- a sharded rank whose first instance is narrower takes the separate fold
+  s.fuse2 = kn.sc_fuse && (!sh.single || num_inputs[p0] == num_inputs[0]);
+  if (s.fuse2 && sh.single) {
+    s.ABC2 = (Fq*)ws_get(ctx, WS_ABC2, cy.ABC.total * sizeof(Fq) + 64);
+    if (!s.ABC2) return set_err(ctx, SPG_E_NOMEM, "ABC");
+  }
+  int rc = s.rounds && ny + nw == 0 ? p2_to_compact(s) : 0;
+  if (!rc) rc = p2_launch_next(s, 0, 0, fq_zero(), fq_zero());
+  if (rc) return rc;
+  s.zk.init(g, tape, s.rounds, cy.claim2, cy.blind2);  // host precomputation while round 0 evaluates
+  for (size_t j = 0; j < s.rounds;) {
+    const int n = s.cur_pair ? p2_round_pair(s, j) : p2_round_single(s, j);
+    if (n < 0) return n;
+    j += (size_t)n;
+  }
+  rc = d2h_multi(ctx, {{cy.eq_p, 1}, {s.TA->d, 1}, {s.TZ->d, 1}}, cy.claims2);
+  if (rc) return rc;
+  cy.blind_post2 = s.zk.blinds_evals[s.rounds - 1];
+  pf.sc2 = std::move(s.zk.out);
+  cy.ry.assign(s.r.rbegin() + (nw + np), s.r.rend());  // the y challenges, reversed
+  cy.rw.assign(s.r.begin() + ny, s.r.begin() + ny + nw);
+  cy.rp2.assign(s.r.begin() + ny + nw, s.r.end());
+  return 0;
+}
 
-  // ---- witness-section evaluations and their batched opening (r1csproof.rs:518-639)
-  FqV ry_factors(ny + 1, fq_one());
-  for (size_t i = 0; i < ny; i++) ry_factors[i + 1] = fq_mul(ry_factors[i], fq_sub(fq_one(), ry[i]));
-  struct PolyRef {
-    size_t w, p, np, ni, Rs;
-    bool mine;
-    FqV LZ, R;
-    Fq ev;
+// ---- witness-section evaluations and their batched opening (r1csproof.rs:518-639)
+// R = eq(rr) of every polynomial, once per distinct right point (instances of one shape share theirs), on the pool
+static void right_tables(std::vector<PolyRef>& polys, const std::vector<FqV>& rr_of) {
+  std::vector<size_t> uniq, at(polys.size());
+  for (size_t k = 0; k < polys.size(); k++) {
+    size_t u = 0;
+    while (u < uniq.size() && !(rr_of[uniq[u]].size() == rr_of[k].size() &&
+                                memcmp(rr_of[uniq[u]].data(), rr_of[k].data(), rr_of[k].size() * sizeof(Fq)) == 0))
+      u++;
+    if (u == uniq.size()) uniq.push_back(k);
+    at[k] = u;
+  }
+  std::vector<FqV> tabs(uniq.size());
+  pool().parallel_for((int)uniq.size(), [&](int u) { tabs[u] = eq_evals_host(rr_of[uniq[u]]); });
+  for (size_t k = 0; k < polys.size(); k++) polys[k].R = tabs[at[k]];
+}
+// LZ = bound(L) of each owned polynomial on this rank's device (lz_mine, zero elsewhere). Every polynomial's eq(rl),
+// partial column sums and LZ are queued back to back into disjoint workspace ranges and the LZ of all of them come
+// back in one download (one host wait instead of one per polynomial). The host eq tables of the right points are
+// computed while the device works (queued first; d2h_fq waits for it).
+int Prover::lz_bound(std::vector<PolyRef>& polys, size_t lz_total, std::vector<Fq>& lz_mine) {
+  const size_t nq = sh.nq, ny = sh.ny;
+  hipStream_t st = ctx->stream;
+  struct BoundJob {
+    FqV rl;
+    size_t Ls, Rs, S, chunk, offL, offP, o;
   };
-  std::vector<PolyRef> polys;
+  std::vector<BoundJob> jobs;
+  size_t o = 0, totL = 0, totP = 0;
+  bool all_mine = true;
+  std::vector<FqV> rr_of(polys.size());  // each polynomial's right point
+  size_t pk = 0;
+  for (auto& pr : polys) {
+    size_t lnp = lg2(pr.np), lni = lg2(pr.ni);
+    FqV r(cy.rq.begin() + (nq - lnp), cy.rq.end());
+    if (pr.ni >= Y) {
+      r.insert(r.end(), lni - ny, fq_zero());
+      r.insert(r.end(), cy.ry.begin(), cy.ry.end());
+    } else {
+      r.insert(r.end(), cy.ry.begin() + (ny - lni), cy.ry.end());
+    }
+    size_t nv = r.size(), ln = nv / 2;
+    FqV rl(r.begin(), r.begin() + ln), rr(r.begin() + ln, r.end());
+    size_t Ls = (size_t)1 << ln, Rs = (size_t)1 << (nv - ln);
+    rr_of[pk++] = std::move(rr);
+    if (pr.mine) {
+      size_t S = std::min<size_t>(Ls, 32);  // 32 partial rows: short column sums
+      const size_t chunk = (Ls + S - 1) / S;
+      S = (Ls + chunk - 1) / chunk;
+      jobs.push_back({std::move(rl), Ls, Rs, S, chunk, totL, totP, o});
+      totL += Ls;
+      totP += S * Rs;
+    } else {
+      all_mine = false;
+    }
+    o += Rs;
+  }
+  if (jobs.empty()) {
+    right_tables(polys, rr_of);
+    return 0;
+  }
+  Fq* dL = (Fq*)ws_get(ctx, WS_L, totL * sizeof(Fq) + 64);
+  Fq* dpart = (Fq*)ws_get(ctx, WS_BPART, totP * sizeof(Fq) + 64);
+  Fq* dout = (Fq*)ws_get(ctx, WS_BOUT, lz_total * sizeof(Fq) + 64);
+  if (!dL || !dpart || !dout) return set_err(ctx, SPG_E_NOMEM, "bound");
+  if (!all_mine) SPG_HIP(ctx, hipMemsetAsync(dout, 0, lz_total * sizeof(Fq), st));  // other ranks' ranges
+  // one eq table per distinct rl (polynomials of one shape share it)
+  std::vector<size_t> eq_at(jobs.size());
+  std::vector<EqJob> eqs;
+  for (size_t k = 0; k < jobs.size(); k++) {
+    size_t same = k;
+    for (size_t m = 0; m < k; m++)
+      if (jobs[m].rl.size() == jobs[k].rl.size() &&
+          memcmp(jobs[m].rl.data(), jobs[k].rl.data(), jobs[k].rl.size() * sizeof(Fq)) == 0) {
+        same = m;
+        break;
+      }
+    eq_at[k] = same == k ? jobs[k].offL : eq_at[same];
+    if (same == k) eqs.push_back({jobs[k].rl.data(), (int)jobs[k].rl.size(), dL + jobs[k].offL});
+  }
+  int rc = dev_eq_tables(ctx, eqs.data(), (int)eqs.size());
+  if (rc) return rc;
+  std::vector<const PolyRef*> mine;
+  for (auto& pr : polys)
+    if (pr.mine) mine.push_back(&pr);
+  double bytes = 0;
+  for (const BoundJob& j : jobs) bytes += 32.0 * j.Ls * j.Rs + 32.0 * j.Ls + 64.0 * j.S * j.Rs;
+  KScope ks(ctx, "poly_bound", bytes);
+  for (size_t k0 = 0; k0 < jobs.size(); k0 += kBoundMax) {  // two launches per kBoundMax polynomials
+    BoundJobs bj;
+    bj.n = (int)std::min<size_t>(kBoundMax, jobs.size() - k0);
+    uint32_t nb = 0, nc = 0;
+    for (int q = 0; q < bj.n; q++) {
+      const BoundJob& j = jobs[k0 + q];
+      const PolyRef& pr = *mine[k0 + q];
+      const uint32_t nbx = (uint32_t)((j.Rs + 255) / 256);
+      bj.d[q] = {wit.ptr[pr.w][pr.p], (uint32_t)eq_at[k0 + q], (uint32_t)j.Ls, (uint32_t)j.Rs,
+                 (uint32_t)j.chunk, (uint32_t)j.S, (uint32_t)j.offP, (uint32_t)j.o, nb, nc};
+      nb += nbx * (uint32_t)j.S;
+      nc += (uint32_t)((j.Rs + kSumCols - 1) / kSumCols);
+    }
+    hipLaunchKernelGGL(k_bound_part_multi, dim3(nb), dim3(256), 0, st, bj, dL, dpart);
+    hipLaunchKernelGGL(k_sum_cols_multi, dim3(nc), dim3(256), 0, st, bj, dpart, dout);
+  }
+  SPG_HIP(ctx, hipGetLastError());
+  right_tables(polys, rr_of);
+  return d2h_fq(ctx, dout, lz_mine.data(), lz_total);
+}
+// every witness polynomial's evaluation at (rq, ry): LZ from its owner shared with every rank, <LZ, R>, commitments
+int Prover::witness_evals(std::vector<PolyRef>& polys, std::vector<FqV>& eval_list) {
+  const size_t ny = sh.ny;
+  FqV ry_factors(ny + 1, fq_one());
+  for (size_t i = 0; i < ny; i++) ry_factors[i + 1] = fq_mul(ry_factors[i], fq_sub(fq_one(), cy.ry[i]));
   size_t lz_total = 0;
   for (size_t i = 0; i < nws; i++) {
     for (size_t p = 0; p < wit.num_proofs[i].size(); p++) {
@@ -1488,123 +1738,18 @@ int Prover::run_inner(Laps& lp) {
       pr.p = p;
       pr.np = wit.num_proofs[i][p];
       pr.ni = wit.num_inputs[i][p];
-      size_t lnp = lg2(pr.np), lni = lg2(pr.ni);
-      size_t nv = lnp + (pr.ni >= Y ? lni : lni);
-      pr.Rs = (size_t)1 << (nv - nv / 2);
+      pr.Rs = lz_width(pr.np, pr.ni);
       pr.mine = wit.num_proofs[i].size() == 1 ? rank == 0 : (p >= p0 && p < p1);
       lz_total += pr.Rs;
       polys.push_back(std::move(pr));
     }
   }
-  // LZ = bound(L) of each owned polynomial on this rank's device, then shared with every rank. Every
-  // polynomial's eq(rl), partial column sums and LZ are queued back to back into disjoint workspace ranges and
-  // the LZ of all of them come back in one download (one host wait instead of one per polynomial).
   std::vector<Fq> lz_mine(lz_total, fq_zero());
-  {
-    struct BoundJob {
-      FqV rl;
-      size_t Ls, Rs, S, chunk, offL, offP, o;
-    };
-    std::vector<BoundJob> jobs;
-    size_t o = 0, totL = 0, totP = 0;
-    bool all_mine = true;
-    std::vector<FqV> rr_of(polys.size());  // each polynomial's right point; R = eq(rr) once per distinct point, below
-    size_t pk = 0;
-    for (auto& pr : polys) {
-      size_t lnp = lg2(pr.np), lni = lg2(pr.ni);
-      FqV r(rq.begin() + (nq - lnp), rq.end());
-      if (pr.ni >= Y) {
-        r.insert(r.end(), lni - ny, fq_zero());
-        r.insert(r.end(), ry.begin(), ry.end());
-      } else {
-        r.insert(r.end(), ry.begin() + (ny - lni), ry.end());
-      }
-      size_t nv = r.size(), ln = nv / 2;
-      FqV rl(r.begin(), r.begin() + ln), rr(r.begin() + ln, r.end());
-      size_t Ls = (size_t)1 << ln, Rs = (size_t)1 << (nv - ln);
-      rr_of[pk++] = std::move(rr);
-      if (pr.mine) {
-        size_t S = std::min<size_t>(Ls, 32);  // 32 partial rows: short column sums
-        const size_t chunk = (Ls + S - 1) / S;
-        S = (Ls + chunk - 1) / chunk;
-        jobs.push_back({std::move(rl), Ls, Rs, S, chunk, totL, totP, o});
-        totL += Ls;
-        totP += S * Rs;
-      } else {
-        all_mine = false;
-      }
-      o += Rs;
-    }
-    // the host eq tables of the distinct right points (instances of one shape share theirs), on the pool, while the
-    // device computes the LZ (queued first; d2h_fq below waits for them)
-    auto right_tables = [&]() {
-      std::vector<size_t> uniq, at(polys.size());
-      for (size_t k = 0; k < polys.size(); k++) {
-        size_t u = 0;
-        while (u < uniq.size() && !(rr_of[uniq[u]].size() == rr_of[k].size() &&
-                                    memcmp(rr_of[uniq[u]].data(), rr_of[k].data(), rr_of[k].size() * sizeof(Fq)) == 0))
-          u++;
-        if (u == uniq.size()) uniq.push_back(k);
-        at[k] = u;
-      }
-      std::vector<FqV> tabs(uniq.size());
-      pool().parallel_for((int)uniq.size(), [&](int u) { tabs[u] = eq_evals_host(rr_of[uniq[u]]); });
-      for (size_t k = 0; k < polys.size(); k++) polys[k].R = tabs[at[k]];
-    };
-    if (jobs.empty()) right_tables();
-    if (!jobs.empty()) {
-      Fq* dL = (Fq*)ws_get(ctx, WS_L, totL * sizeof(Fq) + 64);
-      Fq* dpart = (Fq*)ws_get(ctx, WS_BPART, totP * sizeof(Fq) + 64);
-      Fq* dout = (Fq*)ws_get(ctx, WS_BOUT, lz_total * sizeof(Fq) + 64);
-      if (!dL || !dpart || !dout) return set_err(ctx, SPG_E_NOMEM, "bound");
-      if (!all_mine) SPG_HIP(ctx, hipMemsetAsync(dout, 0, lz_total * sizeof(Fq), s));  // other ranks' ranges
-      // one eq table per distinct rl (polynomials of one shape share it)
-      std::vector<size_t> eq_at(jobs.size());
-      std::vector<EqJob> eqs;
-      for (size_t k = 0; k < jobs.size(); k++) {
-        size_t same = k;
-        for (size_t m = 0; m < k; m++)
-          if (jobs[m].rl.size() == jobs[k].rl.size() &&
-              memcmp(jobs[m].rl.data(), jobs[k].rl.data(), jobs[k].rl.size() * sizeof(Fq)) == 0) {
-            same = m;
-            break;
-          }
-        eq_at[k] = same == k ? jobs[k].offL : eq_at[same];
-        if (same == k) eqs.push_back({jobs[k].rl.data(), (int)jobs[k].rl.size(), dL + jobs[k].offL});
-      }
-      rc = dev_eq_tables(ctx, eqs.data(), (int)eqs.size());
-      if (rc) return rc;
-      std::vector<const PolyRef*> mine;
-      for (auto& pr : polys)
-        if (pr.mine) mine.push_back(&pr);
-      double bytes = 0;
-      for (const BoundJob& j : jobs) bytes += 32.0 * j.Ls * j.Rs + 32.0 * j.Ls + 64.0 * j.S * j.Rs;
-      KScope ks(ctx, "poly_bound", bytes);
-      for (size_t k0 = 0; k0 < jobs.size(); k0 += kBoundMax) {  // two launches per kBoundMax polynomials
-        BoundJobs bj;
-        bj.n = (int)std::min<size_t>(kBoundMax, jobs.size() - k0);
-        uint32_t nb = 0, nc = 0;
-        for (int q = 0; q < bj.n; q++) {
-          const BoundJob& j = jobs[k0 + q];
-          const PolyRef& pr = *mine[k0 + q];
-          const uint32_t nbx = (uint32_t)((j.Rs + 255) / 256);
-          bj.d[q] = {wit.ptr[pr.w][pr.p], (uint32_t)eq_at[k0 + q], (uint32_t)j.Ls, (uint32_t)j.Rs,
-                     (uint32_t)j.chunk, (uint32_t)j.S, (uint32_t)j.offP, (uint32_t)j.o, nb, nc};
-          nb += nbx * (uint32_t)j.S;
-          nc += (uint32_t)((j.Rs + kSumCols - 1) / kSumCols);
-        }
-        hipLaunchKernelGGL(k_bound_part_multi, dim3(nb), dim3(256), 0, s, bj, dL, dpart);
-        hipLaunchKernelGGL(k_sum_cols_multi, dim3(nc), dim3(256), 0, s, bj, dpart, dout);
-      }
-      SPG_HIP(ctx, hipGetLastError());
-      right_tables();
-      rc = d2h_fq(ctx, dout, lz_mine.data(), lz_total);
-      if (rc) return rc;
-    }
-  }
+  int rc = lz_bound(polys, lz_total, lz_mine);
+  if (rc) return rc;
   {
     std::vector<uint8_t> r;
-    rc = allgather(lz_mine.data(), lz_total * sizeof(Fq), r);
+    rc = exchange(lz_mine.data(), lz_total * sizeof(Fq), r);
     if (rc) return rc;
     const Fq* v = (const Fq*)r.data();
     size_t o = 0;
@@ -1615,80 +1760,82 @@ int Prover::run_inner(Laps& lp) {
       o += pr.Rs;
     }
   }
-  std::vector<FqV> eval_list(nws);
+  // (both lists end with nws trailing empty lists, as the reference's do: verify.hip relies on it)
+  eval_list.assign(nws, {});
   pf.comm_vars_at_ry_list.assign(nws, {});
-  {
-    size_t k = 0;
-    std::vector<CJob> cj;  // every evaluation's commitment in one host burst
-    // <LZ, R> of every polynomial, one pool task each
-    pool().parallel_for((int)polys.size(), [&](int q) {
-      PolyRef& pr = polys[q];
-      Fq ev = fq_zero();
-      for (size_t m = 0; m < pr.Rs; m++) ev = fq_add(ev, fq_mul(pr.LZ[m], pr.R[m]));
-      pr.ev = ev;
-    });
-    for (size_t i = 0; i < nws; i++) {
-      eval_list.push_back({});
-      for (size_t p = 0; p < wit.num_proofs[i].size(); p++, k++) {
-        PolyRef& pr = polys[k];
-        const Fq ev = pr.ev;
-        size_t lni = lg2(pr.ni);
-        eval_list[i].push_back(pr.ni >= Y ? ev : fq_mul(ev, ry_factors[ny - lni]));
-        cj.push_back(CJob(g.gens_1, {ev}, fq_zero()));
-      }
-    }
-    const std::vector<Pt> cv = commit_batch(g, cj);
-    k = 0;
-    for (size_t i = 0; i < nws; i++) {
-      pf.comm_vars_at_ry_list.push_back({});
-      for (size_t p = 0; p < wit.num_proofs[i].size(); p++) pf.comm_vars_at_ry_list[i].push_back(cv[k++]);
+  size_t k = 0;
+  std::vector<CJob> cj;  // every evaluation's commitment in one host burst
+  // <LZ, R> of every polynomial, one pool task each
+  pool().parallel_for((int)polys.size(), [&](int q) {
+    PolyRef& pr = polys[q];
+    Fq ev = fq_zero();
+    for (size_t m = 0; m < pr.Rs; m++) ev = fq_add(ev, fq_mul(pr.LZ[m], pr.R[m]));
+    pr.ev = ev;
+  });
+  for (size_t i = 0; i < nws; i++) {
+    eval_list.push_back({});
+    for (size_t p = 0; p < wit.num_proofs[i].size(); p++, k++) {
+      PolyRef& pr = polys[k];
+      const Fq ev = pr.ev;
+      size_t lni = lg2(pr.ni);
+      eval_list[i].push_back(pr.ni >= Y ? ev : fq_mul(ev, ry_factors[ny - lni]));
+      cj.push_back(CJob(g.gens_1, {ev}, fq_zero()));
     }
   }
-  lp.lap("polyeval_bound");
-  // PolyEvalProof::prove_batched_instances_disjoint_rounds (dense_mlpoly.rs:861-960)
-  {
-    t.protocol("polynomial evaluation proof");
-    std::vector<std::pair<size_t, size_t>> keys;
-    std::vector<FqV> LZ_list, R_list;
-    FqV Zc;
-    Fq c_base = t.challenge("challenge_c");
-    Fq c = fq_one();
-    // the coefficients in the reference's order (c advances once per polynomial joining an earlier shape), then every
-    // LZ_list[idx] += c LZ over the pool (axpy_pool; config 4 adds 7 x 1024 products here, ~170 us on one thread)
-    std::vector<int> into(polys.size(), -1);
-    std::vector<Fq> coef(polys.size());
-    for (size_t q = 0; q < polys.size(); q++) {
-      const PolyRef& pr = polys[q];
-      std::pair<size_t, size_t> key = {pr.np, pr.ni};
-      size_t idx = keys.size();
-      for (size_t k = 0; k < keys.size(); k++)
-        if (keys[k] == key) { idx = k; break; }
-      if (idx < keys.size()) {
-        c = fq_mul(c, c_base);
-        into[q] = (int)idx;
-        coef[q] = c;
-        Zc[idx] = fq_add(Zc[idx], fq_mul(c, pr.ev));
-      } else {
-        keys.push_back(key);
-        Zc.push_back(pr.ev);
-        LZ_list.push_back(pr.LZ);
-        R_list.push_back(pr.R);
-      }
-    }
-    std::vector<Axpy> ax;  // (LZ_list no longer grows: its element addresses are stable)
-    for (size_t q = 0; q < polys.size(); q++)
-      if (into[q] >= 0) ax.push_back({&LZ_list[into[q]], coef[q], &polys[q].LZ});
-    axpy_pool(ax);
-    for (size_t k = 0; k < LZ_list.size(); k++) {
-      DotProductProofLogP dp;
-      Pt cy;
-      rc = dotproduct_log_prove(ctx, g, t, tape, LZ_list[k], fq_zero(), R_list[k], Zc[k], fq_zero(), &dp, &cy);
-      if (rc) return rc;
-      pf.evals.push_back(std::move(dp));
+  const std::vector<Pt> cv = commit_batch(g, cj);
+  k = 0;
+  for (size_t i = 0; i < nws; i++) {
+    pf.comm_vars_at_ry_list.push_back({});
+    for (size_t p = 0; p < wit.num_proofs[i].size(); p++) pf.comm_vars_at_ry_list[i].push_back(cv[k++]);
+  }
+  return 0;
+}
+// PolyEvalProof::prove_batched_instances_disjoint_rounds (dense_mlpoly.rs:861-960)
+int Prover::polyeval_batched(std::vector<PolyRef>& polys) {
+  t.protocol("polynomial evaluation proof");
+  std::vector<std::pair<size_t, size_t>> keys;
+  std::vector<FqV> LZ_list, R_list;
+  FqV Zc;
+  Fq c_base = t.challenge("challenge_c");
+  Fq c = fq_one();
+  // the coefficients in the reference's order (c advances once per polynomial joining an earlier shape), then every
+  // LZ_list[idx] += c LZ over the pool (axpy_pool; config 4 adds 7 x 1024 products here, ~170 us on one thread)
+  std::vector<int> into(polys.size(), -1);
+  std::vector<Fq> coef(polys.size());
+  for (size_t q = 0; q < polys.size(); q++) {
+    const PolyRef& pr = polys[q];
+    std::pair<size_t, size_t> key = {pr.np, pr.ni};
+    size_t idx = keys.size();
+    for (size_t k = 0; k < keys.size(); k++)
+      if (keys[k] == key) { idx = k; break; }
+    if (idx < keys.size()) {
+      c = fq_mul(c, c_base);
+      into[q] = (int)idx;
+      coef[q] = c;
+      Zc[idx] = fq_add(Zc[idx], fq_mul(c, pr.ev));
+    } else {
+      keys.push_back(key);
+      Zc.push_back(pr.ev);
+      LZ_list.push_back(pr.LZ);
+      R_list.push_back(pr.R);
     }
   }
-  lp.lap("polyeval_dotlog");
-  // prefix_list (r1csproof.rs:577-606) and the combined evaluation
+  std::vector<Axpy> ax;  // (LZ_list no longer grows: its element addresses are stable)
+  for (size_t q = 0; q < polys.size(); q++)
+    if (into[q] >= 0) ax.push_back({&LZ_list[into[q]], coef[q], &polys[q].LZ});
+  axpy_pool(ax);
+  for (size_t k = 0; k < LZ_list.size(); k++) {
+    DotProductProofLogP dp;
+    Pt comm;
+    int rc = dotproduct_log_prove(ctx, g, t, tape, LZ_list[k], fq_zero(), R_list[k], Zc[k], fq_zero(), &dp, &comm);
+    if (rc) return rc;
+    pf.evals.push_back(std::move(dp));
+  }
+  return 0;
+}
+// prefix_list (r1csproof.rs:577-606), the combined evaluation, the last equality proof and the returned challenges
+void Prover::final_claims(const std::vector<FqV>& eval_list) {
+  const FqV& rw = cy.rw;
   FqV prefix;
   {
     Fq one = fq_one();
@@ -1713,22 +1860,20 @@ int Prover::run_inner(Laps& lp) {
       size_t pw = wit.num_proofs[i].size() == 1 ? 0 : p;
       comb = fq_add(comb, fq_mul(prefix[i], eval_list[i][pw]));
     }
-    for (size_t q = 0; q < nq - lg2(num_proofs[p]); q++) comb = fq_mul(comb, fq_sub(fq_one(), rq[q]));
+    for (size_t q = 0; q < sh.nq - lg2(num_proofs[p]); q++) comb = fq_mul(comb, fq_sub(fq_one(), cy.rq[q]));
     comb_list.push_back(comb);
   }
-  Fq eval_vars_at_ry = dense_eval_host(comb_list, rp2);
+  Fq eval_vars_at_ry = dense_eval_host(comb_list, cy.rp2);
   pf.comm_vars_at_ry = commit_batch(g, {CJob(g.gens_1, {eval_vars_at_ry}, fq_zero())})[0];
-  Fq claim_post2 = fq_mul(fq_mul(claims2[0], claims2[1]), claims2[2]);
-  pf.eq2 = equality_prove(g, g.gens_1, t, tape, claim_post2, fq_zero(), claim_post2, blind_post2);
-  pf.claims_phase2[0] = comm_Az;
-  pf.claims_phase2[1] = comm_Bz;
-  pf.claims_phase2[2] = comm_Cz;
-  pf.claims_phase2[3] = comm_prod;
+  Fq claim_post2 = fq_mul(fq_mul(cy.claims2[0], cy.claims2[1]), cy.claims2[2]);
+  pf.eq2 = equality_prove(g, g.gens_1, t, tape, claim_post2, fq_zero(), claim_post2, cy.blind_post2);
+  pf.claims_phase2[0] = cy.comm_Az;
+  pf.claims_phase2[1] = cy.comm_Bz;
+  pf.claims_phase2[2] = cy.comm_Cz;
+  pf.claims_phase2[3] = cy.comm_prod;
   FqV rwry(rw);
-  rwry.insert(rwry.end(), ry.begin(), ry.end());
-  challenges = {rp2, rq_rev, rx, rwry};
-  lp.lap("final");
-  return 0;
+  rwry.insert(rwry.end(), cy.ry.begin(), cy.ry.end());
+  challenges = {cy.rp2, cy.rq_rev, cy.rx, rwry};
 }
 
 
@@ -2017,7 +2162,7 @@ int witness_from_parts(spg_ctx* ctx, const std::vector<WPart>& secs, spg_r1cs_wi
     }
     return a.type == hipMemoryTypeDevice && a.device == ctx->device;
   };
-  static const bool in_place = !getenv("SPG_WIT_IN_PLACE") || atoi(getenv("SPG_WIT_IN_PLACE")) != 0;
+  const bool in_place = r1cs_knobs().wit_in_place;
   std::vector<std::vector<char>> dev(secs.size());
   size_t host_total = 0;
   for (size_t w = 0; w < secs.size(); w++)

@@ -154,6 +154,8 @@ def test_r1cs_verify(ctx, r1cs_gens, case):
     ("p2_x1024_q64", {"SPG_P2_PAIR": "0"}),                           # phase 2 one y round per launch throughout
     ("p2_x256_2secs", {"SPG_P2_PAIR_MAX": "32"}),                     # phase-2 pairs only after single y rounds
     ("p2_x1024_q64", {"SPG_P1_PAIR_MAX": "32768", "SPG_P2_PAIR_MAX": "32768"}),  # pairs at their largest
+    ("p3_ragged_3secs", {"SPG_TAPE_AHEAD": "0"}),                     # every sumcheck round commits its own points
+    ("p3_ragged_3secs", {"SPG_SIGMA_AHEAD": "0"}),                    # each sigma protocol commits on its own
 ])
 def test_r1cs_thread_form_rounds(oracle, case, env):
     """the thread-per-point phase-1 evaluations (k_phase1_eval, and k_phase1_eval_x's row-factored x rounds: one eq
