@@ -253,6 +253,41 @@ int spg_msm_buf(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const spg_bu
  * encoded as a 32-byte CompressedRistretto (RFC 9496 ENCODE). */
 int spg_points_sum_compress(const uint8_t* parts, size_t k, uint8_t out[32]);
 
+/* ---- variable-base MSM over caller-supplied points (csrc/msm_var.hip) -------------------------
+ * GroupElement::vartime_multiscalar_mul (src/group.rs:98-116) over points that are no resident generator set: proof
+ * points (the verifier's sum_i L_i C_i over Hyrax row commitments, comm_vars_at_ry, Bullet's Gamma_hat) or someone
+ * else's generators met once. No 2^k P rows or comb tables are built: a handle costs 96 B per point and one
+ * decompression each. These calls are single-rank (like the prodc seams): spg_set_comm does not shard them. */
+typedef struct spg_points spg_points;
+/* n CompressedRistretto encodings -> n points resident in HBM as affine Niels (96 B each). Any encoding that
+ * CompressedRistretto::decompress rejects: SPG_E_POINT, spg_last_error names the lowest such index, *out untouched,
+ * nothing stays allocated. n >= 1, n < 2^31. */
+int spg_points_upload(spg_ctx* ctx, const uint8_t* compressed, size_t n, spg_points** out);
+size_t spg_points_n(const spg_points* p);
+/* the n x 32 bytes given (host copy) */
+int spg_points_download(spg_ctx* ctx, const spg_points* p, uint8_t* out);
+int spg_points_free(spg_ctx* ctx, spg_points* p);
+/* sum_{i<n} s_i * P[offset+i], compressed. n = 0 gives the identity (32 zero bytes), as the reference's empty sum.
+ * offset + n past the points: SPG_E_ARG, before anything is launched (so for every call below). */
+int spg_msm_var(spg_ctx* ctx, const spg_points* p, size_t offset, const uint64_t* scalars_mont, size_t n,
+                uint8_t out[32]);
+/* the same with scalars resident: s = buf[s_offset .. s_offset+n) */
+int spg_msm_var_buf(spg_ctx* ctx, const spg_points* p, size_t offset, const spg_buf* s, size_t s_offset, size_t n,
+                    uint8_t out[32]);
+/* B independent MSMs in one pipeline: MSM b sums lens[b] points from offsets[b]; scalars concatenated in b order;
+ * out = B x 32. Ranges may overlap or coincide (several L vectors against one commitment). lens[b] = 0 allowed. */
+int spg_msm_var_batch(spg_ctx* ctx, const spg_points* p, const size_t* offsets, const size_t* lens, size_t B,
+                      const uint64_t* scalars_mont, uint8_t* out);
+/* vartime_multiscalar_mul(scalars, points) in one call: upload, sum, free. */
+int spg_msm_points(spg_ctx* ctx, const uint8_t* compressed, const uint64_t* scalars_mont, size_t n, uint8_t out[32]);
+/* Size limit of the four calls above: with N the points of one call in all, B its MSMs and c the window width (4..14,
+ * chosen from N / B; W = 253 / c + 1 windows), N * W, B * W * 2^(c-1) and the sort's histogram matrix
+ * (about W * max(N, B * 2^(c-1))) must each stay below 2^31: about 2^26 points in one call at the widest window, fewer
+ * MSMs in a batch the wider the window. Past it: SPG_E_ARG ("variable-base MSM too large"), nothing launched.
+ * MSMs of fewer than n points run on the host pool instead of the kernels, for this context; n < 0 restores the process
+ * default (SPG_VMSM_HOST_MAX, else 64, the measured crossover). Results are identical either way. */
+int spg_set_vmsm_host_max(spg_ctx* ctx, long n);
+
 /* ---- R1CS data-parallel satisfiability proof --------------------------------------------------
  * Flat C views of the reference's R1CSInstance (src/r1csinstance.rs:19-31) and
  * ProverWitnessSecInfo (src/lib.rs:508-527). Entries are the reference's SparseMatEntry

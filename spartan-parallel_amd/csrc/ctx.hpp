@@ -21,6 +21,9 @@ struct spg_ctx {
   // spg_set_comb(ctx, 0): this context's MSMs skip the comb tables (comb.hip) and run the bucket pipelines, for an
   // A/B against the fixed-base precomputation (bench.py config 2's no-table leg)
   bool comb_off = false;
+  // spg_set_vmsm_host_max: this context's variable-base MSMs below that many points run on the host pool
+  // (msm_var.hip); -1: the process default (SPG_VMSM_HOST_MAX, read once, else the measured crossover)
+  long vmsm_host_max = -1;
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t ev_cx = nullptr;  // DotProductProofLog: the Cx MSM's completion, ahead of Bullet round 0 on the stream

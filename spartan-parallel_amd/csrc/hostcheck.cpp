@@ -16,6 +16,7 @@
 #include "hostmath.hpp"
 #include "hpool.hpp"
 #include "keccak.hpp"
+#include "vmsm.hpp"
 
 using namespace spg;
 
@@ -316,6 +317,42 @@ long spgh_pool_stress(int workers, int bursts, int max_n, int delay_us, unsigned
     for (int i = 0; i < n; i++) bad.fetch_add(cnt[i].load() != 1);
   }
   return bad.load();
+}
+
+// The variable-base MSM (msm_var.hip) without a device: sum_i s_i P_i of n compressed points with window width c, from
+// the kernels' recode and key function (vmsm.hpp), the buckets filled on the host from the (key, entry) pairs in the
+// device's group layout, and the device path's host finish. Returns 0 with out32 set, -1 for bad arguments
+// (n = 0 is the identity), or -4 (SPG_E_POINT) with *bad_index = the lowest index whose encoding does not decode.
+int spgh_vmsm_emulate(const uint8_t* compressed, const uint64_t* scalars_mont, size_t n, int c, uint8_t* out32,
+                      long* bad_index) {
+  if (!out32 || c < kVmsmCMin || c > kVmsmCMax || (n && (!compressed || !scalars_mont))) return -1;
+  if (n == 0) {
+    memset(out32, 0, 32);
+    return 0;
+  }
+  std::vector<Niels> pts(n);
+  for (size_t i = 0; i < n; i++) {
+    Ext P;
+    if (!ext_decompress(compressed + 32 * i, P)) {
+      if (bad_index) *bad_index = (long)i;
+      return -4;
+    }
+    pts[i] = vmsm_niels_affine(P);
+  }
+  std::vector<Fq> s(n);
+  for (size_t i = 0; i < n; i++) s[i] = ldq(scalars_mont + 4 * i);
+  const size_t off = 0;
+  vmsm_host(pts.data(), &off, &n, 1, s.data(), c, out32);
+  return 0;
+}
+// the signed c-bit digits of one Montgomery scalar (vmsm_digit), 253 / c + 1 of them; returns their number
+int spgh_vmsm_digits(const uint64_t* scalar_mont, int c, int* out) {
+  if (c < kVmsmCMin || c > kVmsmCMax) return -1;
+  const Fq k = fq_from_mont(ldq(scalar_mont));
+  int carry = 0;
+  const int W = vmsm_windows(c);
+  for (int w = 0; w < W; w++) out[w] = vmsm_digit(k.l, c, w, carry);
+  return W;
 }
 
 }  // extern "C"

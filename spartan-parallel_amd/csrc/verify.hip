@@ -327,6 +327,38 @@ struct V {
     return dec(out[0]);
   }
 
+  // ---- row-commitment MSMs sum_i L_i C_i (PolyEvalProof::verify*): the host Pippenger above, or with
+  // SPG_VERIFY_VMSM=1 (read once; default off) the variable-base pipeline of msm_var.hip -- a polynomial's
+  // commitments upload once and the L vectors of one batch go through spg_msm_var_batch
+  static bool vmsm_on() {
+    static const bool on = getenv("SPG_VERIFY_VMSM") && atoi(getenv("SPG_VERIFY_VMSM")) != 0;
+    return on;
+  }
+  std::vector<HExt> row_msms_dev(const std::vector<const FqV*>& Ls, const PolyComm& comm) {
+    std::vector<HExt> out(Ls.size(), h::hext_identity());
+    if (comm.empty() || Ls.empty()) return out;
+    spg_points* P = nullptr;
+    const int urc = spg_points_upload(ctx, comm[0].b, comm.size(), &P);
+    if (urc == SPG_E_POINT) throw Fail{"point decompression"};
+    if (urc) throw Fail{"device MSM"};
+    std::vector<size_t> offs(Ls.size(), 0), lens(Ls.size());
+    FqV s;
+    for (size_t i = 0; i < Ls.size(); i++) {
+      lens[i] = std::min(Ls[i]->size(), comm.size());
+      s.insert(s.end(), Ls[i]->begin(), Ls[i]->begin() + lens[i]);
+    }
+    std::vector<Pt> enc(Ls.size());
+    const int rc = spg_msm_var_batch(ctx, P, offs.data(), lens.data(), Ls.size(), (const uint64_t*)s.data(), enc[0].b);
+    spg_points_free(ctx, P);
+    if (rc) throw Fail{"device MSM"};
+    for (size_t i = 0; i < Ls.size(); i++) out[i] = dec(enc[i]);
+    return out;
+  }
+  HExt row_msm(const FqV& L, const PolyComm& comm) {
+    if (!vmsm_on()) return msm_var(L, decs(comm));
+    return row_msms_dev({&L}, comm)[0];
+  }
+
   // ---- sigma protocols (src/nizk/mod.rs)
   bool knowledge(ProverGens& g, const KeyView& k, const KnowledgeProofP& p, const Pt& C) {
     t.protocol("knowledge proof");
@@ -495,7 +527,7 @@ struct V {
     FqV L, R;
     factored(r, &L, &R);
     if (comm.size() != L.size()) return fail("PolyEvalProof commitment size");
-    return dotlog(g, R.size(), p, R, msm_var(L, decs(comm)), C_Zr);
+    return dotlog(g, R.size(), p, R, row_msm(L, comm), C_Zr);
   }
   bool pe_verify_plain(ProverGens& g, const DotProductProofLogP& p, const FqV& r, const Fq& Zr, const PolyComm& comm) {
     return pe_verify(g, p, r, commit1(g, g.gens_1, Zr, fq_zero()), comm);
@@ -525,7 +557,7 @@ struct V {
       if (idx < keys.size()) {
         c = fq_mul(c, c_base);
         if (comms[i]->size() != L_list[idx].size()) return fail("PolyEvalProof commitment size");
-        LZ_list[idx] = addP(LZ_list[idx], mulP(msm_var(L_list[idx], decs(*comms[i])), c));
+        LZ_list[idx] = addP(LZ_list[idx], mulP(row_msm(L_list[idx], *comms[i]), c));
         Zc[idx] = addP(Zc[idx], mulP(Zr_list[i], c));
       } else {
         keys.push_back(key);
@@ -538,7 +570,7 @@ struct V {
         FqV L, R;
         factored(r, &L, &R);
         if (comms[i]->size() != L.size()) return fail("PolyEvalProof commitment size");
-        LZ_list.push_back(msm_var(L, decs(*comms[i])));
+        LZ_list.push_back(row_msm(L, *comms[i]));
         L_list.push_back(L);
         R_list.push_back(R);
       }
@@ -578,6 +610,18 @@ struct V {
       }
     }
     if (L_list.size() != proofs.size()) return fail("PolyEvalProof count");
+    if (vmsm_on()) {  // one upload of the commitments, every L of the batch in one spg_msm_var_batch
+      std::vector<const FqV*> Ls;
+      for (auto& L : L_list) {
+        if (comm.size() != L.size()) return fail("PolyEvalProof commitment size");
+        Ls.push_back(&L);
+      }
+      const std::vector<HExt> LZ = row_msms_dev(Ls, comm);
+      for (size_t i = 0; i < L_list.size(); i++)
+        if (!dotlog(g, R_list[i].size(), proofs[i], R_list[i], LZ[i], commit1(g, g.gens_1, Zc[i], fq_zero())))
+          return false;
+      return true;
+    }
     const std::vector<HExt> C = decs(comm);
     for (size_t i = 0; i < L_list.size(); i++) {
       if (C.size() != L_list[i].size()) return fail("PolyEvalProof commitment size");
@@ -602,7 +646,7 @@ struct V {
       FqV L, R;
       factored(fit(r_list[i], nv_list[i]), &L, &R);
       if (comms[i]->size() != L.size()) return fail("PolyEvalProof commitment size");
-      const HExt LZ = msm_var(L, decs(*comms[i]));
+      const HExt LZ = row_msm(L, *comms[i]);
       size_t idx = keys.size();
       for (size_t k = 0; k < keys.size(); k++)
         if (keys[k].first == nv_list[i] && same(keys[k].second, R)) {
@@ -661,7 +705,7 @@ struct V {
         L = &Lmap.back().second;
       }
       if (comms[i]->size() != L->size()) return fail("PolyEvalProof commitment size");
-      LZc = addP(LZc, mulP(msm_var(*L, decs(*comms[i])), c));
+      LZc = addP(LZc, mulP(row_msm(*L, *comms[i]), c));
       Zrc = addP(Zrc, mulP(C_Zr[i], c));
       c = fq_mul(c, c_base);
     }

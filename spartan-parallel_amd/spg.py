@@ -31,6 +31,8 @@ def lib():
         _lib.spg_last_error.restype = ctypes.c_char_p
         _lib.spg_last_kernel_us.restype = ctypes.c_double
         _lib.spg_gens_n.restype = ctypes.c_size_t
+        _lib.spg_points_n.restype = ctypes.c_size_t
+        _lib.spg_points_n.argtypes = [ctypes.c_void_p]
     return _lib
 
 
@@ -166,6 +168,11 @@ class Context:
     def set_comb(self, on=True):
         """spg_set_comb: off -> this context's MSMs skip the comb tables (bucket Pippenger pipelines only)"""
         self.check(lib().spg_set_comb(self._h, ctypes.c_int(1 if on else 0)), "spg_set_comb")
+
+    def set_vmsm_host_max(self, n=-1):
+        """spg_set_vmsm_host_max: this context's variable-base MSMs of fewer than n points run on the host pool (0:
+        every size through the kernels; negative: the process default)"""
+        self.check(lib().spg_set_vmsm_host_max(self._h, ctypes.c_long(n)), "spg_set_vmsm_host_max")
 
     def last_kernel_us(self):
         return lib().spg_last_kernel_us(self._h)
@@ -436,6 +443,78 @@ class Gens:
             self.free()
         except Exception:
             pass
+
+
+class Points:
+    """Device-resident points a caller supplies (spg_points): n CompressedRistretto encodings kept as affine Niels, for
+    GroupElement::vartime_multiscalar_mul over points that are no generator set (src/group.rs:98-116). An encoding
+    that does not decompress raises SpgError (SPG_E_POINT, naming the lowest such index)."""
+
+    def __init__(self, ctx, compressed):
+        self.ctx = ctx
+        self._h = ctypes.c_void_p()
+        comp = np.ascontiguousarray(compressed, dtype=np.uint8).reshape(-1, 32)
+        rc = lib().spg_points_upload(ctx.handle, _p(comp), ctypes.c_size_t(comp.shape[0]), ctypes.byref(self._h))
+        ctx.check(rc, "spg_points_upload")
+        self.n = int(lib().spg_points_n(self._h))
+
+    def compressed(self):
+        out = np.zeros((self.n, 32), dtype=np.uint8)
+        self.ctx.check(lib().spg_points_download(self.ctx.handle, self._h, _p(out)), "spg_points_download")
+        return out
+
+    def msm(self, scalars, offset=0):
+        """spg_msm_var: sum_i scalars[i] * P[offset + i], 32-byte compression"""
+        s = _scalars(scalars)
+        out = np.zeros(32, dtype=np.uint8)
+        rc = lib().spg_msm_var(self.ctx.handle, self._h, ctypes.c_size_t(offset), _p(s), ctypes.c_size_t(s.shape[0]),
+                               _p(out))
+        self.ctx.check(rc, "spg_msm_var")
+        return out.tobytes()
+
+    def msm_buf(self, buf, offset=0, s_offset=0, n=None):
+        """spg_msm_var_buf: the same over scalars resident in HBM (a Buf)"""
+        n = buf.n - s_offset if n is None else n
+        out = np.zeros(32, dtype=np.uint8)
+        rc = lib().spg_msm_var_buf(self.ctx.handle, self._h, ctypes.c_size_t(offset), buf.handle,
+                                   ctypes.c_size_t(s_offset), ctypes.c_size_t(n), _p(out))
+        self.ctx.check(rc, "spg_msm_var_buf")
+        return out.tobytes()
+
+    def msm_batch(self, offsets, lens, scalars):
+        """spg_msm_var_batch: MSM b sums lens[b] points from offsets[b]; scalars concatenated in b order; (B, 32)"""
+        offs = np.ascontiguousarray(offsets, dtype=np.uint64)
+        ln = np.ascontiguousarray(lens, dtype=np.uint64)
+        assert offs.shape == ln.shape and offs.ndim == 1
+        s = _scalars(scalars) if int(ln.sum()) else np.zeros((1, 4), dtype=np.uint64)
+        assert int(ln.sum()) == 0 or s.shape[0] == int(ln.sum())
+        out = np.zeros((offs.shape[0], 32), dtype=np.uint8)
+        rc = lib().spg_msm_var_batch(self.ctx.handle, self._h, _p(offs), _p(ln), ctypes.c_size_t(offs.shape[0]), _p(s),
+                                     _p(out))
+        self.ctx.check(rc, "spg_msm_var_batch")
+        return out
+
+    def free(self):
+        if self._h:
+            lib().spg_points_free(self.ctx.handle, self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def msm_points(ctx, compressed, scalars):
+    """spg_msm_points: vartime_multiscalar_mul(scalars, points) in one call (upload, sum, free)"""
+    comp = np.ascontiguousarray(compressed, dtype=np.uint8).reshape(-1, 32)
+    s = _scalars(scalars) if comp.shape[0] else np.zeros((0, 4), dtype=np.uint64)
+    assert s.shape[0] == comp.shape[0]
+    out = np.zeros(32, dtype=np.uint8)
+    rc = lib().spg_msm_points(ctx.handle, _p(comp), _p(s), ctypes.c_size_t(comp.shape[0]), _p(out))
+    ctx.check(rc, "spg_msm_points")
+    return out.tobytes()
 
 
 # ---------------------------------------------------------------- Fiat-Shamir objects
