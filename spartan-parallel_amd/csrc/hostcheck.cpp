@@ -16,6 +16,7 @@
 #include "hostmath.hpp"
 #include "hpool.hpp"
 #include "keccak.hpp"
+#include "snark_shape.hpp"
 #include "vmsm.hpp"
 
 using namespace spg;
@@ -353,6 +354,49 @@ int spgh_vmsm_digits(const uint64_t* scalar_mont, int c, int* out) {
   const int W = vmsm_windows(c);
   for (int w = 0; w < W; w++) out[w] = vmsm_digit(k.l, c, w, carry);
   return W;
+}
+
+// merge_order (snark_shape.hpp), the section merge of SNARK::prove and SNARK::verify: sizes = the components'
+// num_proofs lists back to back, lens[c] = the length of component c's list. Writes the component of every merged
+// instance (at most sum(lens)) and returns their number, or -1 when the sizes give no order
+long spgh_merge_order(const size_t* sizes, const size_t* lens, size_t ncomp, size_t* inst_map) {
+  std::vector<std::vector<size_t>> comps(ncomp);
+  std::vector<const std::vector<size_t>*> ptrs;
+  for (size_t c = 0, o = 0; c < ncomp; o += lens[c++]) comps[c].assign(sizes + o, sizes + o + lens[c]);
+  for (auto& c : comps) ptrs.push_back(&c);
+  std::vector<size_t> map;
+  if (!merge_order(ptrs, &map)) return -1;
+  for (size_t i = 0; i < map.size(); i++) inst_map[i] = map[i];
+  return (long)map.size();
+}
+// SnarkShape (snark_shape.hpp) of a program with Bb blocks. scalars = (num_inputs_unpadded, block_max_num_proofs,
+// consis_num_proofs, total init phy / init vir / phy / vir accesses, mem_addr_ts_bits_size). head[14] = (P, bmax,
+// consis, t_iphy, t_ivir, t_phy, t_vir, pairwise_size, perm_size, pw_nv, |pw_order|, pw_order padded to 3);
+// per_block[7][Bb] = the first P entries of (order, bnp, bnp_pad, bnv, bphy, bvir, w2_size). Returns P
+long spgh_snark_shape(size_t Bb, const size_t* nproofs, const size_t* nvars, const size_t* phy_ops, const size_t* vir_ops,
+                      const size_t* scalars, size_t* head, size_t* per_block) {
+  spg_snark_inputs a;
+  memset(&a, 0, sizeof(a));
+  a.block_num_instances_bound = Bb;
+  a.num_inputs_unpadded = scalars[0];
+  a.block_max_num_proofs = scalars[1];
+  a.consis_num_proofs = scalars[2];
+  a.total_num_init_phy_mem_accesses = scalars[3];
+  a.total_num_init_vir_mem_accesses = scalars[4];
+  a.total_num_phy_mem_accesses = scalars[5];
+  a.total_num_vir_mem_accesses = scalars[6];
+  a.mem_addr_ts_bits_size = scalars[7];
+  const SnarkShape s(a, nproofs, nvars, phy_ops, vir_ops);
+  const size_t h[11] = {s.P, s.bmax, s.consis, s.t_iphy, s.t_ivir, s.t_phy, s.t_vir, s.pairwise_size, s.perm_size,
+                        s.pw_nv, s.pw_order.size()};
+  memcpy(head, h, sizeof(h));
+  for (size_t i = 0; i < 3; i++) head[11 + i] = i < s.pw_order.size() ? s.pw_order[i] : 0;
+  const std::vector<size_t>* rows[6] = {&s.order, &s.bnp, &s.bnp_pad, &s.bnv, &s.bphy, &s.bvir};
+  for (size_t p = 0; p < s.P; p++) {
+    for (size_t k = 0; k < 6; k++) per_block[k * Bb + p] = (*rows[k])[p];
+    per_block[6 * Bb + p] = s.w2_size(p);
+  }
+  return (long)s.P;
 }
 
 }  // extern "C"

@@ -10,7 +10,8 @@
 //     three R1CSProof::prove + multi_evaluate + R1CSEvalProof                             r1cs.hip / spark.hip
 //     perm product, shift and IO PolyEvalProofs            lib.rs:2534-2693, 187-446    host bound + device Bullet
 // The host side is the transcript, the small witness recurrences and the bincode writer; every O(N) table
-// (block_vars, Az/Bz/Cz, SPARK dense representations) lives in HBM.
+// (block_vars, Az/Bz/Cz, SPARK dense representations) lives in HBM. SnarkProver::run calls one stage per section
+// of the reference; what the verifier derives from the same public sizes is in snark_shape.hpp.
 #include <stdio.h>
 #include <stdlib.h>
 
@@ -18,12 +19,11 @@
 
 #include "hostpoly.hpp"
 #include "proto.hpp"
+#include "snark_shape.hpp"
 
 using namespace spg;
 
 namespace {
-
-const size_t INIT_PHY_MEM_WIDTH = 4, INIT_VIR_MEM_WIDTH = 4, PHY_MEM_WIDTH = 4, VIR_MEM_WIDTH = 8, W3_WIDTH = 8;
 
 typedef std::vector<FqV> Rows;  // w_mat of one instance: rows (executions) of scalars
 
@@ -392,65 +392,52 @@ int prove_uni_batched(spg_ctx* ctx, ProverGens& g, const std::vector<const FqV*>
   return 0;
 }
 
-// one host witness section (ProverWitnessSecInfo): rows per instance and their flattened polynomials
-struct HSec {
-  std::vector<Rows> w;
-  std::vector<FqV> poly;   // flattened, padded (DensePolynomial)
-  std::vector<const Fq*> dev;  // device copies when resident (block_vars, exec inputs)
-  size_t n() const { return w.size() ? w.size() : dev.size(); }
+int env_int(const char* name, int dflt) {
+  const char* s = getenv(name);
+  return s ? atoi(s) : dflt;
+}
+struct SnarkKnobs {  // the environment switches of SNARK::prove, read once per prove
+  const bool debug_snark = getenv("SPG_DEBUG_SNARK") != nullptr, debug_tr = getenv("SPG_DEBUG_TR") != nullptr;
+  const int trace = env_int("SPG_TRACE", 0);
+  const bool copy_trace = env_int("SPG_COPY_TRACE", 0) != 0;
+  const bool halved_enc = env_int("SPG_HALVED_ENC", 1) != 0;  // early comb rows encoded on the host from halved points
+  const bool cq_side = env_int("SPG_CQ_SIDE", 1) != 0;        // the commit queue's other rows on the second stream
 };
 
 struct SecInfo {  // sizes + data pointers for merges (ProverWitnessSecInfo::merge / concat, lib.rs:546-604)
   std::vector<size_t> num_proofs, num_inputs;
   std::vector<const Fq*> src;  // host or device data of each instance
   std::vector<const FqV*> poly;  // host polynomial (nullptr for device-only data)
-};
-SecInfo merge(const std::vector<const SecInfo*>& comps, std::vector<size_t>* inst_map) {
-  std::vector<size_t> ptr(comps.size(), 0);
-  size_t total = 0;
-  for (auto c : comps) total += c->num_proofs.size();
-  SecInfo s;
-  inst_map->clear();
-  while (inst_map->size() < total) {
-    size_t best = 0, nc = 0;
-    for (size_t i = 0; i < comps.size(); i++)
-      if (ptr[i] < comps[i]->num_proofs.size() && comps[i]->num_proofs[ptr[i]] > best) {
-        best = comps[i]->num_proofs[ptr[i]];
-        nc = i;
-      }
-    inst_map->push_back(nc);
-    s.num_proofs.push_back(comps[nc]->num_proofs[ptr[nc]]);
-    s.num_inputs.push_back(comps[nc]->num_inputs[ptr[nc]]);
-    s.src.push_back(comps[nc]->src[ptr[nc]]);
-    s.poly.push_back(comps[nc]->poly[ptr[nc]]);
-    ptr[nc]++;
+  void push(size_t np, size_t ni, const Fq* data, const FqV* p) {
+    num_proofs.push_back(np);
+    num_inputs.push_back(ni);
+    src.push_back(data);
+    poly.push_back(p);
   }
-  return s;
+};
+// im (optional): the component each merged instance came from
+int merge(spg_ctx* ctx, const std::vector<const SecInfo*>& comps, SecInfo* s, std::vector<size_t>* im = nullptr) {
+  std::vector<const std::vector<size_t>*> sizes;
+  for (auto c : comps) sizes.push_back(&c->num_proofs);
+  std::vector<size_t> map;
+  if (!merge_order(sizes, &map)) return set_err(ctx, SPG_E_ARG, "witness section sizes: an instance without proofs");
+  *s = SecInfo();
+  std::vector<size_t> ptr(comps.size(), 0);
+  for (size_t c : map) {
+    const size_t k = ptr[c]++;
+    s->push(comps[c]->num_proofs[k], comps[c]->num_inputs[k], comps[c]->src[k], comps[c]->poly[k]);
+  }
+  if (im) *im = map;
+  return 0;
 }
 SecInfo concat(const std::vector<const SecInfo*>& comps) {
   SecInfo s;
-  for (auto c : comps) {
-    s.num_proofs.insert(s.num_proofs.end(), c->num_proofs.begin(), c->num_proofs.end());
-    s.num_inputs.insert(s.num_inputs.end(), c->num_inputs.begin(), c->num_inputs.end());
-    s.src.insert(s.src.end(), c->src.begin(), c->src.end());
-    s.poly.insert(s.poly.end(), c->poly.begin(), c->poly.end());
-  }
+  for (auto c : comps)
+    for (size_t k = 0; k < c->num_proofs.size(); k++) s.push(c->num_proofs[k], c->num_inputs[k], c->src[k], c->poly[k]);
   return s;
 }
 WPart wpart(const SecInfo& s) { return {s.num_proofs, s.num_inputs, s.src}; }
-// a host section of one instance per rows block
-SecInfo host_sec(const std::vector<Rows>& w, const std::vector<FqV>& poly) {
-  SecInfo s;
-  for (size_t p = 0; p < w.size(); p++) {
-    s.num_proofs.push_back(w[p].size());
-    s.num_inputs.push_back(w[p][0].size());
-    s.src.push_back(poly[p].data());
-    s.poly.push_back(&poly[p]);
-  }
-  return s;
-}
 
-// Hyrax commitment of a host polynomial (uploads into a staging slot, device MSMs)
 // Hyrax commitments of the witness polynomials of SNARK::prove, deferred so that all rows of one width go to
 // the device in one MSM launch; flush() appends them to the transcript in the order they were added (every
 // commitment between challenge_r and the block R1CSProof depends only on the witness and tau, r).
@@ -461,21 +448,43 @@ struct CQ {
     size_t len;
     std::vector<Pt>* out;
   };
+  const SnarkKnobs& kn;
   std::vector<Item> items;
   // Early group: device-resident polynomials (the block witnesses) whose rows are committed by one batch MSM
   // launched before the host builds the permutation witnesses, so the device works while the host does;
   // flush() only downloads those rows. Their commitments depend on the witness alone, never on the
   // transcript, and they are recomputed in every prove.
   std::vector<const Fq*> early_dev;
-  size_t early_R = 0, early_L = 0;
+  size_t early_L = 0;
   uint8_t* early_out = nullptr;
   const Ext* early_ext = nullptr;  // halved comb points (encoded on the host at flush), else early_out's encodings
+  // the rows of every item outside the early group: launched (uploads and points), then finished (encodings; the
+  // host may encode the early group in between)
+  std::vector<std::vector<Pt>> rows;
+  std::vector<RowJob> jobs;
+  RowsPending pend;
+  explicit CQ(const SnarkKnobs& k) : kn(k) {}
+
+  // the Hyrax row width of a polynomial of `len` scalars: 2^(nv - nv / 2)
+  static size_t row_width(size_t len) { return (size_t)1 << (lg2(len) - lg2(len) / 2); }
+  // ctx->stream is `s` until the scope ends, on every path out of it
+  struct StreamScope {
+    spg_ctx* c;
+    hipStream_t prev;
+    StreamScope(spg_ctx* ctx, hipStream_t s) : c(ctx), prev(ctx->stream) { c->stream = s; }
+    ~StreamScope() { c->stream = prev; }
+  };
+  bool is_early(const Item& it) const {
+    return it.dev && std::find(early_dev.begin(), early_dev.end(), it.dev) != early_dev.end();
+  }
+  void add(const FqV& v, std::vector<Pt>* out) { items.push_back({&v, nullptr, v.size(), out}); }
+  void add_dev(const Fq* d, size_t len, std::vector<Pt>* out) { items.push_back({nullptr, d, len, out}); }
+
   int launch_early(spg_ctx* ctx, ProverGens& g, const std::vector<std::pair<const Fq*, size_t>>& its) {
     size_t R = 0, total = 0;
     for (auto& it : its) {
-      const size_t nv = lg2(it.second), r = (size_t)1 << (nv - nv / 2);
-      if (R && r != R) return 0;  // one width only; otherwise flush() groups them as usual
-      R = r;
+      if (R && row_width(it.second) != R) return 0;  // one width only; otherwise flush() groups them as usual
+      R = row_width(it.second);
       total += it.second;
     }
     // the one-launch batch path of commit_rows only (rows wider than the latency path, one chunk)
@@ -491,9 +500,8 @@ struct CQ {
     }
     // the comb rows with halved scalars: flush() encodes the points' doubles on the host in one batch (~50 us on the
     // pool for 1024 rows) instead of a k_compress_ext launch (~140 us of dependent squarings per lane)
-    static const bool halve = !getenv("SPG_HALVED_ENC") || atoi(getenv("SPG_HALVED_ENC")) != 0;
     // slot 95 (94 is unused)
-    Ext* ext = halve && total / R >= 384 ? (Ext*)ws_get(ctx, 95, sizeof(Ext) * (total / R) + 64) : nullptr;
+    Ext* ext = kn.halved_enc && total / R >= kHalvedMin ? (Ext*)ws_get(ctx, 95, sizeof(Ext) * (total / R) + 64) : nullptr;
     int rc = ext ? msm_comb(ctx, g.dev, 0, d, R, total / R, nullptr, nullptr, -1, ext, true) : kCombSkip;
     if (rc == kCombSkip) {
       ext = nullptr;
@@ -502,100 +510,12 @@ struct CQ {
     if (rc) return rc;
     early_ext = ext;
     for (auto& it : its) early_dev.push_back(it.first);
-    early_R = R;
     early_L = total / R;
     early_out = out;
     return 0;
   }
-  bool is_early(const Item& it) const {
-    return it.dev && std::find(early_dev.begin(), early_dev.end(), it.dev) != early_dev.end();
-  }
-  void add(const FqV& v, std::vector<Pt>* out) { items.push_back({&v, nullptr, v.size(), out}); }
-  void add_dev(const Fq* d, size_t len, std::vector<Pt>* out) { items.push_back({nullptr, d, len, out}); }
-  int flush(spg_ctx* ctx, ProverGens& g, Tr& t) {
-    std::vector<size_t> widths;
-    for (auto& it : items) {
-      const size_t nv = lg2(it.len), R = (size_t)1 << (nv - nv / 2);
-      it.out->assign((size_t)1 << (nv / 2), Pt());
-      if (!is_early(it) && std::find(widths.begin(), widths.end(), R) == widths.end()) widths.push_back(R);
-    }
-    // While the early MSM runs, the other rows go to the device on the second stream: their uploads and
-    // latency-path MSMs then overlap it instead of queueing behind it. Rows of at most kSideMaxR scalars take
-    // commit_rows' latency path, whose workspace slots, mapped buckets and staging the batch pipeline of the early
-    // MSM never touches; wider rows stay on the main stream.
-    static const size_t kSideMaxR = 256;
-    static const bool side_on = !getenv("SPG_CQ_SIDE") || atoi(getenv("SPG_CQ_SIDE")) != 0;
-    bool side = side_on && early_L > 0;
-    for (size_t R : widths) side = side && R <= kSideMaxR;
-    Laps lp;
-    lp.title = "commit queue flush";
-    lp.on = lp.on && getenv("SPG_TRACE") && atoi(getenv("SPG_TRACE")) >= 2;
-    const hipStream_t main_stream = ctx->stream;
-    if (side) {
-      SPG_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_pre, 0));
-      ctx->stream = ctx->stream2;
-    }
-    int rc = flush_rows_launch(ctx, g, widths);
-    ctx->stream = main_stream;
-    if (rc) return rc;
-    lp.lap(side ? "rows_side_launch" : "rows_launch");
-    // the early group's encodings while the other rows' points are computed
-    if (early_L) {
-      std::vector<Pt> rows(early_L);
-      if (early_ext) {
-        Ext* h = (Ext*)enc_stage_get(ctx, early_L * sizeof(Ext));
-        if (!h) return set_err(ctx, SPG_E_NOMEM, "encoding staging");
-        SPG_HIP(ctx, hipMemcpyAsync(h, early_ext, early_L * sizeof(Ext), hipMemcpyDeviceToHost, ctx->stream));
-        SPG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        encode_halved_host(h, early_L, rows.data());
-        early_ext = nullptr;
-      } else {
-        SPG_HIP(ctx, hipMemcpyAsync(rows.data(), early_out, 32 * early_L, hipMemcpyDeviceToHost, ctx->stream));
-        SPG_HIP(ctx, hipStreamSynchronize(ctx->stream));
-      }
-      size_t o = 0;
-      for (const Fq* d : early_dev)  // rows in launch order
-        for (auto& it : items)
-          if (it.dev == d) {
-            std::copy(rows.begin() + o, rows.begin() + o + it.out->size(), it.out->begin());
-            o += it.out->size();
-          }
-      early_dev.clear();
-      early_L = 0;
-    }
-    lp.lap("early_wait");
-    if (side) ctx->stream = ctx->stream2;
-    rc = flush_rows_finish(ctx, g, widths);
-    ctx->stream = main_stream;
-    if (rc) return rc;
-    lp.lap(side ? "rows_side_finish" : "rows_finish");
-    for (auto& it : items) append_polycomm(t, "poly_commitment", *it.out);
-    items.clear();
-    lp.lap("append");
-    lp.print();
-    return 0;
-  }
-  // the rows of every item outside the early group, on ctx->stream: launched (uploads and points), then finished
-  // (encodings; the host may encode the early group in between)
-  std::vector<std::vector<Pt>> rows;
-  std::vector<RowJob> jobs;
-  RowsPending pend;
-  int flush_rows_finish(spg_ctx* ctx, ProverGens& g, const std::vector<size_t>& widths) {
-    int rc = commit_rows_many_finish(ctx, g, jobs, pend);
-    if (rc) return rc;
-    for (size_t w = 0; w < widths.size(); w++) {
-      size_t ro = 0;
-      for (auto& it : items) {
-        if (is_early(it) || ((size_t)1 << (lg2(it.len) - lg2(it.len) / 2)) != widths[w]) continue;
-        std::copy(rows[w].begin() + ro, rows[w].begin() + ro + it.out->size(), it.out->begin());
-        ro += it.out->size();
-      }
-    }
-    rows.clear();
-    jobs.clear();
-    return 0;
-  }
-  int flush_rows_launch(spg_ctx* ctx, ProverGens& g, const std::vector<size_t>& widths) {
+
+  int rows_launch(spg_ctx* ctx, ProverGens& g, const std::vector<size_t>& widths) {
     // one staging range per width, every width's rows committed together (the latency-path widths share one
     // encoding launch and one download)
     size_t total = 0;
@@ -609,7 +529,7 @@ struct CQ {
     for (size_t w = 0; w < widths.size(); w++) {
       const size_t R = widths[w], o0 = o;
       for (auto& it : items) {
-        if (is_early(it) || ((size_t)1 << (lg2(it.len) - lg2(it.len) / 2)) != R) continue;
+        if (is_early(it) || row_width(it.len) != R) continue;
         if (it.host)
           SPG_HIP(ctx, hipMemcpyAsync(d + o, it.host->data(), it.len * sizeof(Fq), hipMemcpyHostToDevice, ctx->stream));
         else
@@ -621,8 +541,120 @@ struct CQ {
     }
     return commit_rows_many_launch(ctx, g, jobs, &pend);
   }
+  int rows_finish(spg_ctx* ctx, ProverGens& g, const std::vector<size_t>& widths) {
+    int rc = commit_rows_many_finish(ctx, g, jobs, pend);
+    if (rc) return rc;
+    for (size_t w = 0; w < widths.size(); w++) {
+      size_t ro = 0;
+      for (auto& it : items) {
+        if (is_early(it) || row_width(it.len) != widths[w]) continue;
+        std::copy(rows[w].begin() + ro, rows[w].begin() + ro + it.out->size(), it.out->begin());
+        ro += it.out->size();
+      }
+    }
+    rows.clear();
+    jobs.clear();
+    return 0;
+  }
+  // the early group's encodings, downloaded (or encoded on the host from the halved points) into its items
+  int early_collect(spg_ctx* ctx) {
+    std::vector<Pt> enc(early_L);
+    if (early_ext) {
+      Ext* h = (Ext*)enc_stage_get(ctx, early_L * sizeof(Ext));
+      if (!h) return set_err(ctx, SPG_E_NOMEM, "encoding staging");
+      SPG_HIP(ctx, hipMemcpyAsync(h, early_ext, early_L * sizeof(Ext), hipMemcpyDeviceToHost, ctx->stream));
+      SPG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+      encode_halved_host(h, early_L, enc.data());
+      early_ext = nullptr;
+    } else {
+      SPG_HIP(ctx, hipMemcpyAsync(enc.data(), early_out, 32 * early_L, hipMemcpyDeviceToHost, ctx->stream));
+      SPG_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    size_t o = 0;
+    for (const Fq* d : early_dev)  // rows in launch order
+      for (auto& it : items)
+        if (it.dev == d) {
+          std::copy(enc.begin() + o, enc.begin() + o + it.out->size(), it.out->begin());
+          o += it.out->size();
+        }
+    early_dev.clear();
+    early_L = 0;
+    return 0;
+  }
+
+  int flush(spg_ctx* ctx, ProverGens& g, Tr& t) {
+    std::vector<size_t> widths;
+    for (auto& it : items) {
+      const size_t R = row_width(it.len);
+      it.out->assign((size_t)1 << (lg2(it.len) / 2), Pt());
+      if (!is_early(it) && std::find(widths.begin(), widths.end(), R) == widths.end()) widths.push_back(R);
+    }
+    // While the early MSM runs, the other rows go to the device on the second stream: their uploads and
+    // latency-path MSMs then overlap it instead of queueing behind it. Rows of at most kSideMaxR scalars take
+    // commit_rows' latency path, whose workspace slots, mapped buckets and staging the batch pipeline of the early
+    // MSM never touches; wider rows stay on the main stream.
+    static const size_t kSideMaxR = 256;
+    bool side = kn.cq_side && early_L > 0;
+    for (size_t R : widths) side = side && R <= kSideMaxR;
+    Laps lp;
+    lp.title = "commit queue flush";
+    lp.on = lp.on && kn.trace >= 2;
+    if (side) SPG_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_pre, 0));
+    const hipStream_t rows_stream = side ? ctx->stream2 : ctx->stream;
+    int rc;
+    {
+      StreamScope on(ctx, rows_stream);
+      rc = rows_launch(ctx, g, widths);
+    }
+    if (rc) return rc;
+    lp.lap(side ? "rows_side_launch" : "rows_launch");
+    // the early group's encodings while the other rows' points are computed
+    if (early_L && (rc = early_collect(ctx))) return rc;
+    lp.lap("early_wait");
+    {
+      StreamScope on(ctx, rows_stream);
+      rc = rows_finish(ctx, g, widths);
+    }
+    if (rc) return rc;
+    lp.lap(side ? "rows_side_finish" : "rows_finish");
+    for (auto& it : items) append_polycomm(t, "poly_commitment", *it.out);
+    items.clear();
+    lp.lap("append");
+    lp.print();
+    return 0;
+  }
 };
 
+// the host witness polynomials of one section, one per instance: rows, DensePolynomial (flattened, padded), Hyrax
+// commitment and the section's view for the R1CS witness
+struct HostSec {
+  std::vector<Rows> rows;
+  std::vector<FqV> poly;
+  std::vector<std::vector<Pt>> comm;
+  SecInfo s;  // filled by queue(); empty for a memory list the program does not use
+  explicit HostSec(size_t n = 1) : rows(n), poly(n), comm(n) {}
+  // instance p's polynomial into the commit queue (the queue keeps pointers: this object stays where it is)
+  void queue(CQ& q, size_t p = 0) {
+    poly[p] = pad_pow2(flatten(rows[p]));
+    q.add(poly[p], &comm[p]);
+    s.push(rows[p].size(), rows[p][0].size(), poly[p].data(), &poly[p]);
+  }
+};
+// (w2, w3, w3_shifted) of a permutation argument: perm-exec, the blocks, and each memory list (SNARK::mem_gen)
+struct PermWit {
+  HostSec w2, w3, w3s;
+  explicit PermWit(size_t n = 1) : w2(n), w3(n), w3s(n) {}
+  void set(size_t p, Rows r2, Rows r3) {
+    w3s.rows[p] = shift_rows(r3, W3_WIDTH);
+    w2.rows[p] = std::move(r2);
+    w3.rows[p] = std::move(r3);
+  }
+  void queue(CQ& q) {  // a single instance's three commitments, in transcript order
+    w2.queue(q);
+    w3.queue(q);
+    w3s.queue(q);
+  }
+};
 }  // namespace
 
 // ------------------------------------------------------------------------------------ C-ABI
@@ -835,95 +867,168 @@ extern "C" int spg_snark_witness_free(spg_ctx* ctx, spg_snark_wit* W) {
 
 namespace {
 
-struct MemGen {  // SNARK::mem_gen output (lib.rs:831-968)
-  std::vector<Rows> w2, w3, w3s;
-  std::vector<FqV> p2, p3, p3s;
-  std::vector<Pt> c2, c3, c3s;
-  SecInfo s2, s3, s3s;
-};
-int mem_gen(size_t width, Rows mems, size_t total, const Fq& r, const Fq& tau, bool vir, CQ& q, MemGen* o) {
-  if (total == 0) return 0;
-  Rows w2(total, FqV(width, fq_zero())), w3(total, FqV(W3_WIDTH, fq_zero()));
-  const Fq r2 = fq_mul(r, r), r3 = fq_mul(r2, r);
-  for (size_t q = 0; q < total; q++) {
-    w2[q][3] = fq_mul(r, mems[q][3]);
-    if (vir) {
-      w2[q][4] = fq_mul(r2, mems[q][4]);
-      w2[q][5] = fq_mul(r3, mems[q][5]);
-    }
-  }
-  for (size_t q = total; q-- > 0;) {
-    Fq rest = w2[q][3];
-    if (vir) rest = fq_add(fq_add(rest, w2[q][4]), w2[q][5]);
-    w3[q][0] = mems[q][0];
-    w3[q][1] = fq_mul(mems[q][0], fq_sub(fq_sub(tau, mems[q][2]), rest));
-    w3[q][3] = q != total - 1 ? fq_mul(w3[q][1], fq_sub(fq_add(w3[q + 1][2], fq_one()), w3[q + 1][0])) : w3[q][1];
-    w3[q][2] = fq_mul(w3[q][0], w3[q][3]);
-    w3[q][4] = fq_mul(mems[q][0], fq_add(fq_add(mems[q][0], mems[q][2]), rest));
-    w3[q][5] = mems[q][0];
-  }
-  o->w2 = {w2};
-  o->w3 = {w3};
-  o->w3s = {shift_rows(w3, W3_WIDTH)};
-  o->p2 = {pad_pow2(flatten(o->w2[0]))};
-  o->p3 = {pad_pow2(flatten(o->w3[0]))};
-  o->p3s = {pad_pow2(flatten(o->w3s[0]))};
-  q.add(o->p2[0], &o->c2);
-  q.add(o->p3[0], &o->c3);
-  q.add(o->p3s[0], &o->c3s);
-  o->s2 = host_sec(o->w2, o->p2);
-  o->s3 = host_sec(o->w3, o->p3);
-  o->s3s = host_sec(o->w3s, o->p3s);
-  return 0;
+// rows are independent except their reverse-q recurrences (perm_chain): the per-row work runs on the host pool in
+// chunks, the recurrences (2 products per row) afterwards in order
+void par_rows(size_t n, const std::function<void(size_t)>& f) {
+  const int C = n >= 64 ? 8 : 1;
+  pool().parallel_for(C, [&](int c) {
+    for (size_t q = n * c / C; q < n * (c + 1) / C; q++) f(q);
+  });
+}
+Rows pad_rows(Rows m, size_t n, size_t w) {
+  m.resize(n, FqV(w, fq_zero()));
+  return m;
+}
+FqV column(const Rows& m, size_t c) {
+  FqV v;
+  for (auto& r : m) v.push_back(r[c]);
+  return v;
 }
 
-}  // namespace
+// The reverse-q recurrence of one permutation product chain over the w3 rows (lib.rs:855-864, 1539-1611), from the
+// chain's per-row ends:
+//   w3[q][col + 1] = ends[q] * (w3[q + 1][col] + 1 - w3[q + 1][0])   (ends[q] itself on the last row)
+//   w3[q][col]     = w3[q][0] * w3[q][col + 1]
+void perm_chain(Rows& w3, size_t col, const FqV& ends) {
+  for (size_t q = w3.size(); q-- > 0;) {
+    FqV& w = w3[q];
+    w[col + 1] = q + 1 != w3.size() ? fq_mul(ends[q], fq_sub(fq_add(w3[q + 1][col], fq_one()), w3[q + 1][0])) : ends[q];
+    w[col] = fq_mul(w[0], w[col + 1]);
+  }
+}
 
-static int spg_snark_prove_impl(spg_ctx* ctx, spg_snark_comp* block, spg_snark_comp* pairwise, spg_snark_comp* perm_root,
-                               const spg_snark_wit* W, spg_r1cs_gens* vars_gens, spg_transcript* transcript,
-                               spg_random_tape* tape_h, uint8_t* proof, size_t proof_cap, size_t* proof_len) {
-  if (!ctx || !block || !pairwise || !perm_root || !W || !vars_gens || !transcript || !tape_h || !proof_len)
-    return SPG_E_ARG;
-  Tr& t = transcript->t;
-  Tape& tape = tape_h->t;
-  ProverGens& g = vars_gens->g;
-  const spg_snark_inputs& a = W->a;
-  const size_t niu = a.num_inputs_unpadded, num_ios = a.num_ios, io_width = 2 * niu;
-  const size_t Bb = a.block_num_instances_bound;
-  if (2 * niu > num_ios) return set_err(ctx, SPG_E_ARG, "num_ios < 2 * num_inputs_unpadded");
+// What a first-section row (valid, _, inputs, outputs) gives on its own, for perm-exec and block rows alike
+// (lib.rs:1322-1366, 1420-1470): w2[0..2], the perm_w0 products w2[3 .. 2 niu), w3[0] = valid and
+// w3[1] = valid * (tau - sum_{k >= 3} w2[k] - row[2])
+void row_prelude(const FqV& row, const FqV& perm_w0, const Fq& tau, size_t niu, size_t w2_size, FqV* w2_out,
+                 FqV* w3_out) {
+  FqV w2(w2_size, fq_zero()), w3(W3_WIDTH, fq_zero());
+  for (size_t i = 1; i < 2 * (niu - 1); i++) w2[2 + i] = fq_mul(perm_w0[i], row[i + 2]);
+  Fq rest = fq_zero();
+  for (size_t k = 3; k < w2.size(); k++) rest = fq_add(rest, w2[k]);
+  w2[0] = row[0];
+  w2[1] = row[0];
+  for (size_t i = 0; i + 1 < niu; i++) {
+    const Fq perm = i == 0 ? fq_one() : perm_w0[i];
+    w2[0] = fq_add(w2[0], fq_mul(perm, row[2 + i]));
+    w2[2] = fq_add(w2[2], fq_mul(perm, row[2 + (niu - 1) + i]));
+  }
+  w2[0] = fq_mul(w2[0], row[0]);
+  w2[1] = fq_mul(fq_add(w2[1], w2[2]), row[0]);
+  w3[0] = row[0];
+  w3[1] = fq_mul(w3[0], fq_sub(fq_sub(tau, rest), row[2]));
+  *w2_out = std::move(w2);
+  *w3_out = std::move(w3);
+}
+
+// SNARK::prove (lib.rs:971-2746) as stages over named state; run() calls them in the reference's section order
+struct SnarkProver {
+  spg_ctx* ctx;
+  spg_snark_comp *block, *pairwise, *perm_root;
+  const spg_snark_wit* W;
+  spg_r1cs_gens* vars_gens;
+  spg_transcript* transcript;
+  spg_random_tape* tape_h;
+  Tr& t;
+  Tape& tape;
+  ProverGens& g;
+  const spg_snark_inputs& a;
+  const size_t niu, num_ios;
+  const SnarkKnobs kn;
+  const SnarkShape sh;
   Laps lp;
-  lp.title = "SNARK::prove";
-  t.protocol("Spartan SNARK proof");
-  const bool dbg0 = getenv("SPG_DEBUG_SNARK") != nullptr;
-  auto fp = [&](const char* where) {
-    if (!dbg0 || t.cb) return;  // (a fork of a caller-backed transcript cannot be taken)
+  CQ cq;
+  Writer w;  // bincode(SNARK) in declaration order (lib.rs:701-756)
+
+  Fq tau, r;
+  FqV perm_w0;
+  HostSec w0;                    // perm_w0 as the one-row section every instance shares
+  PermWit pe, bw, mem[4];        // perm-exec, the blocks, SNARK::mem_gen of init phy / init vir / phy / vir
+  HostSec iphy, ivir, aphy, aphys, avir, avirs, ts;  // the memory lists as given (padded), addr lists also shifted
+  std::vector<std::vector<Pt>> c_bv;  // block_vars and exec inputs: committed from HBM
+  std::vector<Pt> c_exec;
+  SecInfo s_bvars, s_exec;
+  spg_r1cs_witness* Wt;  // the context's cached R1CS witness, refilled in place by every sat_prove
+  SatOut so;
+
+  SnarkProver(spg_ctx* c, spg_snark_comp* b, spg_snark_comp* pw, spg_snark_comp* pr, const spg_snark_wit* wit,
+              spg_r1cs_gens* vg, spg_transcript* tr, spg_random_tape* tp)
+      : ctx(c), block(b), pairwise(pw), perm_root(pr), W(wit), vars_gens(vg), transcript(tr), tape_h(tp), t(tr->t),
+        tape(tp->t), g(vg->g), a(wit->a), niu(a.num_inputs_unpadded), num_ios(a.num_ios),
+        sh(a, wit->nproofs.data(), wit->nvars.data(), wit->phy_ops.data(), wit->vir_ops.data()), cq(kn), bw(sh.P),
+        c_bv(sh.P), Wt(c->wt_cache) {
+    lp.title = "SNARK::prove";
+    ctx->wt_cache = nullptr;
+  }
+  ~SnarkProver() {  // the witness goes back to the context on every exit path
+    if (!ctx->wt_cache) ctx->wt_cache = Wt;
+    else spg_r1cs_witness_free(ctx, Wt);
+  }
+
+  void fp(const char* where) {  // SPG_DEBUG_SNARK: a fingerprint of the transcript's state
+    if (!kn.debug_snark || t.cb) return;  // (a fork of a caller-backed transcript cannot be taken)
     Tr c = t;
     Fq x = c.challenge("dbg");
     fprintf(stderr, "fp %s %08x\n", where, x.l[0]);
-  };
-  // ---- INSTANCE COMMITMENTS (lib.rs:1086-1153)
-  auto app = [&](const char* l, size_t v) { t.scalar(l, fq_from_u64(v)); };
-  app("func_input_width", a.func_input_width);
-  app("input_offset", a.input_offset);
-  app("output_offset", a.output_offset);
-  app("output_exec_num", a.output_exec_num);
-  app("num_ios", num_ios);
-  for (size_t b = 0; b < Bb; b++) app("block_num_vars", W->nvars[b]);
-  app("mem_addr_ts_bits_size", a.mem_addr_ts_bits_size);
-  app("num_inputs_unpadded", niu);
-  app("block_num_instances_bound", Bb);
-  app("block_max_num_proofs", a.block_max_num_proofs);
-  for (size_t b = 0; b < Bb; b++) app("block_num_phy_ops", W->phy_ops[b]);
-  for (size_t b = 0; b < Bb; b++) app("block_num_vir_ops", W->vir_ops[b]);
-  app("total_num_init_phy_mem_accesses", a.total_num_init_phy_mem_accesses);
-  app("total_num_init_vir_mem_accesses", a.total_num_init_vir_mem_accesses);
-  app("total_num_phy_mem_accesses", a.total_num_phy_mem_accesses);
-  app("total_num_vir_mem_accesses", a.total_num_vir_mem_accesses);
-  app("block_max_num_proofs", a.block_max_num_proofs);
-  for (size_t b = 0; b < Bb; b++) app("block_num_proofs", W->nproofs[b]);
+  }
+
+  int run();
+  int append_instance();
+  int launch_early_commits();
+  void draw_challenges();
+  void gen_perm_exec();
+  void gen_block();
+  void gen_mem(size_t width, const Rows& mems, bool vir, PermWit* o);
+  int queue_input_commits();
+  void write_commitments();
+  int sat_then_evals(spg_snark_comp* C, const std::vector<size_t>& order, bool as_list);
+  int prove_block();
+  int prove_pairwise();
+  int prove_perm_root();
+  int prove_perm_product();
+  int prove_shift();
+  int prove_io();
+  int finish(uint8_t* proof, size_t proof_cap, size_t* proof_len);
+};
+
+int SnarkProver::run() {
+  int rc;
+  t.protocol("Spartan SNARK proof");
+  if ((rc = append_instance())) return rc;
+  lp.lap("inst_commit+sort");
+  if ((rc = launch_early_commits())) return rc;
+  draw_challenges();
+  gen_perm_exec();
+  gen_block();
+  gen_mem(INIT_PHY_MEM_WIDTH, iphy.rows[0], false, &mem[0]);
+  gen_mem(INIT_VIR_MEM_WIDTH, ivir.rows[0], false, &mem[1]);
+  gen_mem(PHY_MEM_WIDTH, aphy.rows[0], false, &mem[2]);
+  gen_mem(VIR_MEM_WIDTH, avir.rows[0], true, &mem[3]);
+  lp.lap("mem_gen");
+  if ((rc = queue_input_commits())) return rc;
+  lp.lap("input_commit");
+  write_commitments();
+  if ((rc = prove_block())) return rc;
+  lp.lap("block_eval");
+  if ((rc = prove_pairwise())) return rc;
+  lp.lap("pairwise");
+  if ((rc = prove_perm_root())) return rc;
+  lp.lap("perm_root");
+  if ((rc = prove_perm_product())) return rc;
+  lp.lap("perm_product");
+  if ((rc = prove_shift())) return rc;
+  lp.lap("shift");
+  if ((rc = prove_io())) return rc;
+  lp.lap("io");
+  return 0;
+}
+
+// INSTANCE COMMITMENTS (lib.rs:1086-1153), then the block and pairwise sort and the padded memory lists
+// (lib.rs:1155-1296; the sizes are SnarkShape's)
+int SnarkProver::append_instance() {
+  append_snark_params(t, a, W->nproofs.data(), W->nvars.data(), W->phy_ops.data(), W->vir_ops.data());
   fp("params");
-  for (auto& lm : block->label_map)
-    for (auto l : lm) app("block_comm_map", l);
+  append_comm_map(t, block->label_map);
   fp("map");
   for (size_t gi = 0; gi < block->sparks.size(); gi++) append_r1cs_comm(block, gi, t);
   fp("block");
@@ -931,526 +1036,346 @@ static int spg_snark_prove_impl(spg_ctx* ctx, spg_snark_comp* block, spg_snark_c
   fp("pairwise");
   append_r1cs_comm(perm_root, 0, t);
   fp("perm_root");
-  const Fq input_block_num = fq_from_u64(a.input_block_num), output_block_num = fq_from_u64(a.output_block_num);
-  t.scalar("input_block_num", input_block_num);
-  t.scalar("output_block_num", output_block_num);
-  t.scalars("input_list", W->input);
-  t.scalar("output_list", W->output);
-
-  // ---- BLOCK SORT + PADDING (lib.rs:1155-1273)
-  size_t P = 0;
-  for (auto n : W->nproofs)
-    if (n > 0) P++;
-  std::vector<size_t> order(Bb);
-  for (size_t i = 0; i < Bb; i++) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](size_t x, size_t y) { return W->nproofs[x] > W->nproofs[y]; });
-  order.resize(P);
+  append_snark_io(t, a, W->input, W->output);
+  iphy.rows[0] = pad_rows(W->init_phy, sh.t_iphy, INIT_PHY_MEM_WIDTH);
+  ivir.rows[0] = pad_rows(W->init_vir, sh.t_ivir, INIT_VIR_MEM_WIDTH);
+  aphy.rows[0] = pad_rows(W->addr_phy, sh.t_phy, PHY_MEM_WIDTH);
+  avir.rows[0] = pad_rows(W->addr_vir, sh.t_vir, VIR_MEM_WIDTH);
+  ts.rows[0] = pad_rows(W->ts_bits, sh.t_vir, a.mem_addr_ts_bits_size);
   // block_vars_mat[i] pairs with sorted instance i (the reference never permutes the witness list)
-  std::vector<size_t> bnp(P), bnv(P), bphy(P), bvir(P);
-  for (size_t i = 0; i < P; i++) {
-    bnp[i] = W->nproofs[order[i]];
-    bnv[i] = W->nvars[order[i]];
-    bphy[i] = W->phy_ops[order[i]];
-    bvir[i] = W->vir_ops[order[i]];
-  }
-  const size_t bmax = npow2(a.block_max_num_proofs);
-  std::vector<size_t> bnp_pad(P);
-  for (size_t i = 0; i < P; i++) bnp_pad[i] = npow2(bnp[i]);
-  const size_t consis = npow2(a.consis_num_proofs);
-  auto padded = [](size_t n) { return n ? npow2(n) : 0; };
-  const size_t t_iphy = padded(a.total_num_init_phy_mem_accesses), t_ivir = padded(a.total_num_init_vir_mem_accesses),
-               t_phy = padded(a.total_num_phy_mem_accesses), t_vir = padded(a.total_num_vir_mem_accesses);
-  auto pad_rows = [](Rows m, size_t n, size_t w) {
-    m.resize(n, FqV(w, fq_zero()));
-    return m;
-  };
-  Rows init_phy = pad_rows(W->init_phy, t_iphy, INIT_PHY_MEM_WIDTH), init_vir = pad_rows(W->init_vir, t_ivir, INIT_VIR_MEM_WIDTH),
-       addr_phy = pad_rows(W->addr_phy, t_phy, PHY_MEM_WIDTH), addr_vir = pad_rows(W->addr_vir, t_vir, VIR_MEM_WIDTH),
-       ts_bits = pad_rows(W->ts_bits, t_vir, a.mem_addr_ts_bits_size);
-  int rc = ensure_sorted(ctx, block, order);
+  int rc = ensure_sorted(ctx, block, sh.order);
   if (rc) return rc;
-  // PAIRWISE SORT (lib.rs:1275-1296)
-  std::vector<std::pair<size_t, size_t>> ps = {{consis, 0}, {t_phy, 1}, {t_vir, 2}};
-  std::stable_sort(ps.begin(), ps.end(), [](const std::pair<size_t, size_t>& x, const std::pair<size_t, size_t>& y) {
-    return x.first > y.first;
-  });
-  const size_t pw_inst = 1 + (t_phy > 0) + (t_vir > 0);
-  std::vector<size_t> pw_order;
-  for (size_t i = 0; i < pw_inst; i++) pw_order.push_back(ps[i].second);
-  rc = ensure_sorted(ctx, pairwise, pw_order);
-  if (rc) return rc;
+  return ensure_sorted(ctx, pairwise, sh.pw_order);
+}
 
-  lp.lap("inst_commit+sort");
-  CQ cq;
-  {  // block_vars commitments: on the device now, read back when the queue is flushed
-    std::vector<std::pair<const Fq*, size_t>> bv;
-    for (size_t p = 0; p < P; p++) bv.push_back({W->d_block_vars[p], bnp_pad[p] * bnv[p]});
-    if ((rc = cq.launch_early(ctx, g, bv))) return rc;
-  }
-  // ---- WITNESS GEN: block (lib.rs:1299-1741)
-  const Fq tau = t.challenge("challenge_tau"), r = t.challenge("challenge_r");
-  if (getenv("SPG_DEBUG_TR")) fprintf(stderr, "[prove] tau %08x r %08x\n", tau.l[0], r.l[0]);
-  const bool dbg = getenv("SPG_DEBUG_SNARK") != nullptr;
-  if (dbg) fprintf(stderr, "snark tau %08x %08x r %08x\n", tau.l[0], tau.l[1], r.l[0]);
-  FqV perm_w0 = {tau};
-  {
-    Fq rt = r;
-    for (size_t i = 1; i < 2 * niu; i++) {
-      perm_w0.push_back(rt);
-      rt = fq_mul(rt, r);
-    }
-    perm_w0.resize(num_ios, fq_zero());
-  }
-  std::vector<Pt> c_w0;
-  cq.add(perm_w0, &c_w0);
-  const Rows& exec = W->exec;
-  Rows pe_w2(consis), pe_w3(consis);
-  // rows are independent except the reverse-q recurrence of w3[3] (and w3[2]): the per-row work runs on the
-  // host pool in chunks, the recurrence (2 products per row) afterwards in order
-  auto par_rows = [](size_t n, const std::function<void(size_t)>& f) {
-    const int C = n >= 64 ? 8 : 1;
-    pool().parallel_for(C, [&](int c) {
-      for (size_t q = n * c / C; q < n * (c + 1) / C; q++) f(q);
-    });
-  };
-  par_rows(consis, [&](size_t q) {
-    FqV v(3, fq_zero());
-    for (size_t j = 1; j < 2 * niu - 2; j++) v.push_back(fq_mul(perm_w0[j], exec[q][j + 2]));
-    v.resize(num_ios, fq_zero());
-    v[0] = exec[q][0];
-    v[1] = exec[q][0];
-    for (size_t i = 0; i + 1 < niu; i++) {
-      const Fq perm = i == 0 ? fq_one() : perm_w0[i];
-      v[0] = fq_add(v[0], fq_mul(perm, exec[q][2 + i]));
-      v[2] = fq_add(v[2], fq_mul(perm, exec[q][2 + (niu - 1) + i]));
-    }
-    v[0] = fq_mul(v[0], exec[q][0]);
-    v[1] = fq_mul(fq_add(v[1], v[2]), exec[q][0]);
-    FqV w(8, fq_zero());
-    w[0] = exec[q][0];
-    Fq sacc = fq_zero();
-    for (size_t k = 3; k < v.size(); k++) sacc = fq_add(sacc, v[k]);
-    w[1] = fq_mul(w[0], fq_sub(fq_sub(tau, sacc), exec[q][2]));
-    w[4] = v[0];
-    w[5] = v[1];
-    pe_w2[q] = std::move(v);
-    pe_w3[q] = std::move(w);
+// block_vars commitments: on the device now, read back when the queue is flushed
+int SnarkProver::launch_early_commits() {
+  std::vector<std::pair<const Fq*, size_t>> bv;
+  for (size_t p = 0; p < sh.P; p++) bv.push_back({W->d_block_vars[p], sh.bnp_pad[p] * sh.bnv[p]});
+  return cq.launch_early(ctx, g, bv);
+}
+
+void SnarkProver::draw_challenges() {
+  tau = t.challenge("challenge_tau");
+  r = t.challenge("challenge_r");
+  if (kn.debug_tr) fprintf(stderr, "[prove] tau %08x r %08x\n", tau.l[0], r.l[0]);
+  if (kn.debug_snark) fprintf(stderr, "snark tau %08x %08x r %08x\n", tau.l[0], tau.l[1], r.l[0]);
+  perm_w0 = spg::perm_w0(tau, r, niu, num_ios);
+  w0.rows[0] = {perm_w0};
+  w0.queue(cq);
+}
+
+// WITNESS GEN, perm-exec (lib.rs:1299-1418)
+void SnarkProver::gen_perm_exec() {
+  Rows w2(sh.consis), w3(sh.consis);
+  par_rows(sh.consis, [&](size_t q) {
+    row_prelude(W->exec[q], perm_w0, tau, niu, num_ios, &w2[q], &w3[q]);
+    w3[q][4] = w2[q][0];
+    w3[q][5] = w2[q][1];
   });
-  for (size_t q = consis; q-- > 0;) {
-    FqV& w = pe_w3[q];
-    w[3] = q != consis - 1 ? fq_mul(w[1], fq_sub(fq_add(pe_w3[q + 1][2], fq_one()), pe_w3[q + 1][0])) : w[1];
-    w[2] = fq_mul(w[0], w[3]);
-  }
-  std::vector<Rows> pe_w2v = {pe_w2}, pe_w3v = {pe_w3}, pe_w3sv = {shift_rows(pe_w3, 8)};
-  std::vector<FqV> pe_p2 = {pad_pow2(flatten(pe_w2))}, pe_p3 = {pad_pow2(flatten(pe_w3))},
-                   pe_p3s = {pad_pow2(flatten(pe_w3sv[0]))};
-  if (dbg)
+  perm_chain(w3, 2, column(w3, 1));
+  if (kn.debug_snark)
     for (size_t q = 0; q < 2; q++)
-      for (size_t i = 0; i < num_ios; i++) fprintf(stderr, "pe_w2[%zu][%zu] %08x\n", q, i, pe_w2[q][i].l[0]);
+      for (size_t i = 0; i < num_ios; i++) fprintf(stderr, "pe_w2[%zu][%zu] %08x\n", q, i, w2[q][i].l[0]);
+  pe.set(0, std::move(w2), std::move(w3));
   lp.lap("perm_exec_witness");
-  std::vector<Pt> c_pe2, c_pe3, c_pe3s;
-  cq.add(pe_p2[0], &c_pe2);
-  cq.add(pe_p3[0], &c_pe3);
-  cq.add(pe_p3s[0], &c_pe3s);
-
+  pe.queue(cq);
   lp.lap("perm_exec_commit");
-  std::vector<Rows> b_w2(P), b_w3(P), b_w3s(P);
+}
+
+// WITNESS GEN, blocks (lib.rs:1420-1741): after the row prelude, the physical (addr, data) and virtual
+// (addr, data, ls, ts) memory operations of the row, each a product chain along the row whose end feeds a reverse-q
+// chain of w3 (columns 4-5 physical, 6-7 virtual)
+void SnarkProver::gen_block() {
   const Fq r2 = fq_mul(r, r), r3 = fq_mul(r2, r);
-  for (size_t p = 0; p < P; p++) {
-    const size_t np_ = bphy[p], nv_ = bvir[p], Q = bnp_pad[p];
-    const size_t w2_size = npow2(2 * niu + 2 * np_ + 4 * nv_);
+  const size_t io_width = 2 * niu;
+  for (size_t p = 0; p < sh.P; p++) {
+    const size_t np_ = sh.bphy[p], nv_ = sh.bvir[p], Q = sh.bnp_pad[p], w2_size = sh.w2_size(p);
     const Rows& bio = W->block_io[p];
-    const size_t keep = bio.empty() ? 0 : bio[0].size();
-    b_w2[p].assign(Q, FqV());
-    b_w3[p].assign(Q, FqV());
-    FqV zero_row(keep, fq_zero());
-    std::vector<Fq> pxs(Q), vxs(Q);  // the chain ends read by the reverse-q recurrences
+    const FqV zero_row(bio.empty() ? 0 : bio[0].size(), fq_zero());
+    Rows w2(Q), w3(Q);
+    FqV pxs(Q), vxs(Q);  // the ends of the row's memory chains
     par_rows(Q, [&](size_t q) {  // everything of row q that does not depend on row q + 1
       const FqV& bv = q < bio.size() ? bio[q] : zero_row;
-      const Fq V_CNST = bv[0];
-      FqV w2(w2_size, fq_zero());
-      w2[0] = bv[0];
-      w2[1] = bv[0];
-      for (size_t i = 1; i < 2 * (niu - 1); i++) w2[2 + i] = fq_add(w2[2 + i], fq_mul(perm_w0[i], bv[i + 2]));
-      for (size_t i = 0; i + 1 < niu; i++) {
-        const Fq perm = i == 0 ? fq_one() : perm_w0[i];
-        w2[0] = fq_add(w2[0], fq_mul(perm, bv[2 + i]));
-        w2[2] = fq_add(w2[2], fq_mul(perm, bv[2 + (niu - 1) + i]));
-      }
-      w2[0] = fq_mul(w2[0], bv[0]);
-      w2[1] = fq_mul(fq_add(w2[1], w2[2]), bv[0]);
-      FqV w3(8, fq_zero());
-      w3[0] = bv[0];
-      Fq sacc = fq_zero();
-      for (size_t k = 3; k < w2.size(); k++) sacc = fq_add(sacc, w2[k]);
-      w3[1] = fq_mul(w3[0], fq_sub(fq_sub(tau, sacc), bv[2]));
+      FqV& x = w2[q];
+      row_prelude(bv, perm_w0, tau, niu, w2_size, &x, &w3[q]);
+      const Fq valid = bv[0];
       for (size_t i = 0; i < np_; i++) {
-        const size_t PMR = 2 * niu + 2 * i, PMC = PMR + 1;
-        w2[PMR] = fq_mul(r, bv[io_width + 2 * i + 1]);
-        const Fq tt = i == 0 ? V_CNST : w2[PMC - 2];
-        w2[PMC] = fq_mul(tt, fq_sub(fq_sub(tau, bv[io_width + 2 * i]), w2[PMR]));
+        const size_t PMR = io_width + 2 * i, PMC = PMR + 1;
+        x[PMR] = fq_mul(r, bv[PMR + 1]);
+        const Fq tt = i == 0 ? valid : x[PMC - 2];
+        x[PMC] = fq_mul(tt, fq_sub(fq_sub(tau, bv[PMR]), x[PMR]));
       }
-      pxs[q] = np_ == 0 ? V_CNST : w2[2 * niu + 2 * (np_ - 1) + 1];
+      pxs[q] = np_ == 0 ? valid : x[io_width + 2 * (np_ - 1) + 1];
       for (size_t i = 0; i < nv_; i++) {
-        const size_t base = 2 * niu + 2 * np_ + 4 * i, vb = io_width + 2 * np_ + 4 * i;
-        w2[base] = fq_mul(r, bv[vb + 1]);
-        w2[base + 1] = fq_mul(r2, bv[vb + 2]);
-        w2[base + 2] = fq_mul(r3, bv[vb + 3]);
-        const Fq tt = i == 0 ? V_CNST : w2[base - 1];
-        w2[base + 3] = fq_mul(tt, fq_sub(fq_sub(fq_sub(fq_sub(tau, bv[vb]), w2[base]), w2[base + 1]), w2[base + 2]));
+        const size_t base = io_width + 2 * np_ + 4 * i;
+        x[base] = fq_mul(r, bv[base + 1]);
+        x[base + 1] = fq_mul(r2, bv[base + 2]);
+        x[base + 2] = fq_mul(r3, bv[base + 3]);
+        const Fq tt = i == 0 ? valid : x[base - 1];
+        x[base + 3] = fq_mul(tt, fq_sub(fq_sub(fq_sub(fq_sub(tau, bv[base]), x[base]), x[base + 1]), x[base + 2]));
       }
-      vxs[q] = nv_ == 0 ? V_CNST : w2[2 * niu + 2 * np_ + 4 * (nv_ - 1) + 3];
-      b_w2[p][q] = std::move(w2);
-      b_w3[p][q] = std::move(w3);
+      vxs[q] = nv_ == 0 ? valid : x[io_width + 2 * np_ + 4 * (nv_ - 1) + 3];
     });
-    for (size_t q = Q; q-- > 0;) {  // the reverse-q recurrences (src/lib.rs:1539-1611)
-      FqV& w3 = b_w3[p][q];
-      const Fq V_CNST = w3[0];
-      const FqV* nx = q != Q - 1 ? &b_w3[p][q + 1] : nullptr;
-      w3[3] = nx ? fq_mul(w3[1], fq_sub(fq_add((*nx)[2], fq_one()), (*nx)[0])) : w3[1];
-      w3[2] = fq_mul(w3[0], w3[3]);
-      w3[5] = nx ? fq_mul(pxs[q], fq_sub(fq_add((*nx)[4], fq_one()), (*nx)[0])) : pxs[q];
-      w3[4] = fq_mul(V_CNST, w3[5]);
-      w3[7] = nx ? fq_mul(vxs[q], fq_sub(fq_add((*nx)[6], fq_one()), (*nx)[0])) : vxs[q];
-      w3[6] = fq_mul(V_CNST, w3[7]);
-    }
-    b_w3s[p] = shift_rows(b_w3[p], 8);
+    perm_chain(w3, 2, column(w3, 1));
+    perm_chain(w3, 4, pxs);
+    perm_chain(w3, 6, vxs);
+    bw.set(p, std::move(w2), std::move(w3));
   }
   lp.lap("block_witness");
-  std::vector<FqV> b_p2(P), b_p3(P), b_p3s(P);
-  std::vector<std::vector<Pt>> c_b2(P), c_b3(P), c_b3s(P), c_bv(P);
-  for (size_t p = 0; p < P; p++) {
-    b_p2[p] = pad_pow2(flatten(b_w2[p]));
-    cq.add(b_p2[p], &c_b2[p]);
-  }
-  for (size_t p = 0; p < P; p++) {
-    b_p3[p] = pad_pow2(flatten(b_w3[p]));
-    b_p3s[p] = pad_pow2(flatten(b_w3s[p]));
-    cq.add(b_p3[p], &c_b3[p]);
-    cq.add(b_p3s[p], &c_b3s[p]);
+  for (size_t p = 0; p < sh.P; p++) bw.w2.queue(cq, p);
+  for (size_t p = 0; p < sh.P; p++) {
+    bw.w3.queue(cq, p);
+    bw.w3s.queue(cq, p);
   }
   lp.lap("block_w_commit");
-  // ---- memory witnesses (lib.rs:1742-1955)
-  MemGen m_iphy, m_ivir, m_phy, m_vir;
-  mem_gen(INIT_PHY_MEM_WIDTH, init_phy, t_iphy, r, tau, false, cq, &m_iphy);
-  mem_gen(INIT_VIR_MEM_WIDTH, init_vir, t_ivir, r, tau, false, cq, &m_ivir);
-  mem_gen(PHY_MEM_WIDTH, addr_phy, t_phy, r, tau, false, cq, &m_phy);
-  mem_gen(VIR_MEM_WIDTH, addr_vir, t_vir, r, tau, true, cq, &m_vir);
-  lp.lap("mem_gen");
-  // ---- WITNESS COMMITMENTS (lib.rs:1957-2221): block_vars and exec inputs from HBM
-  for (size_t p = 0; p < P; p++) cq.add_dev(W->d_block_vars[p], bnp_pad[p] * bnv[p], &c_bv[p]);
-  std::vector<Pt> c_exec;
-  cq.add_dev(W->d_exec, consis * num_ios, &c_exec);
-  std::vector<FqV> p_iphy, p_ivir, p_aphy, p_aphys, p_avir, p_avirs, p_ts;
-  std::vector<Rows> r_aphys, r_avirs;
-  std::vector<Pt> c_aphy, c_aphys, c_avir, c_avirs, c_ts, c_iphy_in, c_ivir_in;
-  if (t_iphy) {
-    p_iphy = {pad_pow2(flatten(init_phy))};
-    cq.add(p_iphy[0], &c_iphy_in);
-  }
-  if (t_ivir) {
-    p_ivir = {pad_pow2(flatten(init_vir))};
-    cq.add(p_ivir[0], &c_ivir_in);
-  }
-  if (t_phy) {
-    p_aphy = {pad_pow2(flatten(addr_phy))};
-    cq.add(p_aphy[0], &c_aphy);
-    r_aphys = {shift_rows(addr_phy, PHY_MEM_WIDTH)};
-    p_aphys = {pad_pow2(flatten(r_aphys[0]))};
-    cq.add(p_aphys[0], &c_aphys);
-  }
-  if (t_vir) {
-    p_avir = {pad_pow2(flatten(addr_vir))};
-    cq.add(p_avir[0], &c_avir);
-    r_avirs = {shift_rows(addr_vir, VIR_MEM_WIDTH)};
-    p_avirs = {pad_pow2(flatten(r_avirs[0]))};
-    cq.add(p_avirs[0], &c_avirs);
-    p_ts = {pad_pow2(flatten(ts_bits))};
-    cq.add(p_ts[0], &c_ts);
-  }
-  if ((rc = cq.flush(ctx, g, t))) return rc;
-  lp.lap("input_commit");
-  // witness sections
-  std::vector<FqV> w0v = {perm_w0};
-  SecInfo s_w0 = host_sec({{perm_w0}}, w0v);
-  SecInfo s_bvars;
-  for (size_t p = 0; p < P; p++) {
-    s_bvars.num_proofs.push_back(bnp_pad[p]);
-    s_bvars.num_inputs.push_back(bnv[p]);
-    s_bvars.src.push_back(W->d_block_vars[p]);
-    s_bvars.poly.push_back(nullptr);
-  }
-  SecInfo s_bw2 = host_sec(b_w2, b_p2), s_bw3 = host_sec(b_w3, b_p3), s_bw3s = host_sec(b_w3s, b_p3s);
-  SecInfo s_pe2 = host_sec(pe_w2v, pe_p2), s_pe3 = host_sec(pe_w3v, pe_p3), s_pe3s = host_sec(pe_w3sv, pe_p3s);
-  SecInfo s_exec;
-  s_exec.num_proofs = {consis};
-  s_exec.num_inputs = {num_ios};
-  s_exec.src = {W->d_exec};
-  s_exec.poly = {nullptr};
-  SecInfo s_none, s_iphy, s_ivir, s_aphy, s_aphys, s_avir, s_avirs, s_ts;
-  if (t_iphy) s_iphy = host_sec({init_phy}, p_iphy);
-  if (t_ivir) s_ivir = host_sec({init_vir}, p_ivir);
-  if (t_phy) {
-    s_aphy = host_sec({addr_phy}, p_aphy);
-    s_aphys = host_sec(r_aphys, p_aphys);
-  }
-  if (t_vir) {
-    s_avir = host_sec({addr_vir}, p_avir);
-    s_avirs = host_sec(r_avirs, p_avirs);
-    s_ts = host_sec({ts_bits}, p_ts);
-  }
-  spg_r1cs_witness* Wt = ctx->wt_cache;  // refilled in place (witness_from_parts) when large enough
-  ctx->wt_cache = nullptr;
-  struct WGuard {
-    spg_ctx* c;
-    spg_r1cs_witness** w;
-    ~WGuard() {
-      if (!c->wt_cache) c->wt_cache = *w;
-      else spg_r1cs_witness_free(c, *w);
-    }
-  } guard{ctx, &Wt};
+}
 
-  Writer w;  // bincode(SNARK) in declaration order (lib.rs:701-756)
-  w.u64(P);
+// SNARK::mem_gen (lib.rs:831-968) of one padded memory list (nothing for a list the program does not use)
+void SnarkProver::gen_mem(size_t width, const Rows& mems, bool vir, PermWit* o) {
+  const size_t total = mems.size();
+  if (total == 0) return;
+  Rows w2(total, FqV(width, fq_zero())), w3(total, FqV(W3_WIDTH, fq_zero()));
+  const Fq r2 = fq_mul(r, r), r3 = fq_mul(r2, r);
+  for (size_t q = 0; q < total; q++) {
+    const FqV& m = mems[q];
+    Fq rest = w2[q][3] = fq_mul(r, m[3]);
+    if (vir) {
+      w2[q][4] = fq_mul(r2, m[4]);
+      w2[q][5] = fq_mul(r3, m[5]);
+      rest = fq_add(fq_add(rest, w2[q][4]), w2[q][5]);
+    }
+    w3[q][0] = m[0];
+    w3[q][1] = fq_mul(m[0], fq_sub(fq_sub(tau, m[2]), rest));
+    w3[q][4] = fq_mul(m[0], fq_add(fq_add(m[0], m[2]), rest));
+    w3[q][5] = m[0];
+  }
+  perm_chain(w3, 2, column(w3, 1));
+  o->set(0, std::move(w2), std::move(w3));
+  o->queue(cq);
+}
+
+// WITNESS COMMITMENTS (lib.rs:1957-2221): block_vars and exec inputs from HBM, the memory lists, then every queued
+// commitment computed and appended to the transcript in the order it was queued
+int SnarkProver::queue_input_commits() {
+  for (size_t p = 0; p < sh.P; p++) {
+    cq.add_dev(W->d_block_vars[p], sh.bnp_pad[p] * sh.bnv[p], &c_bv[p]);
+    s_bvars.push(sh.bnp_pad[p], sh.bnv[p], W->d_block_vars[p], nullptr);
+  }
+  cq.add_dev(W->d_exec, sh.consis * num_ios, &c_exec);
+  s_exec.push(sh.consis, num_ios, W->d_exec, nullptr);
+  if (sh.t_iphy) iphy.queue(cq);
+  if (sh.t_ivir) ivir.queue(cq);
+  if (sh.t_phy) {
+    aphy.queue(cq);
+    aphys.rows[0] = shift_rows(aphy.rows[0], PHY_MEM_WIDTH);
+    aphys.queue(cq);
+  }
+  if (sh.t_vir) {
+    avir.queue(cq);
+    avirs.rows[0] = shift_rows(avir.rows[0], VIR_MEM_WIDTH);
+    avirs.queue(cq);
+    ts.queue(cq);
+  }
+  return cq.flush(ctx, g, t);
+}
+
+// the commitments of bincode(SNARK), ahead of the proofs
+void SnarkProver::write_commitments() {
+  w.u64(sh.P);
   for (auto& c : c_bv) w.pts(c);
   w.u64(1);
   w.pts(c_exec);
-  w.pts(c_aphy);
-  w.pts(c_aphys);
-  w.pts(c_avir);
-  w.pts(c_avirs);
-  w.pts(c_ts);
-  w.pts(c_pe2);
-  w.pts(c_pe3);
-  w.pts(c_pe3s);
-  for (auto* L : {&c_b2, &c_b3, &c_b3s}) {
-    w.u64(P);
-    for (auto& c : *L) w.pts(c);
+  for (HostSec* s : {&aphy, &aphys, &avir, &avirs, &ts}) w.pts(s->comm[0]);
+  for (HostSec* s : {&pe.w2, &pe.w3, &pe.w3s}) w.pts(s->comm[0]);
+  for (HostSec* s : {&bw.w2, &bw.w3, &bw.w3s}) {
+    w.u64(sh.P);
+    for (auto& c : s->comm) w.pts(c);
   }
-  for (auto* M : {&m_iphy, &m_ivir, &m_phy, &m_vir}) {
-    w.pts(M->c2);
-    w.pts(M->c3);
-    w.pts(M->c3s);
-  }
+  for (PermWit& m : mem)
+    for (HostSec* s : {&m.w2, &m.w3, &m.w3s}) w.pts(s->comm[0]);
+}
 
-  // ---- BLOCK_CORRECTNESS_EXTRACT (lib.rs:2223-2309)
-  SatOut so;
-  rc = sat_prove(ctx, vars_gens, block->dev_sorted, P, bmax, bnp_pad, a.num_vars, bnv,
-                 {wpart(s_bvars), wpart(s_w0), wpart(s_bw2), wpart(s_bw3), wpart(s_bw3s)}, &Wt, transcript, tape_h, &so);
+// After an R1CSProof over the instances of C: its bytes, R1CSInstance::multi_evaluate at (rx, ry) with the rp-bound
+// evaluations in the sorted `order`, the claims into the transcript, then a counted list of one R1CSEvalProof per
+// commitment (as_list: the multi-commitment block instance) or the one proof over all evaluations
+int SnarkProver::sat_then_evals(spg_snark_comp* C, const std::vector<size_t>& order, bool as_list) {
+  w.out.insert(w.out.end(), so.bytes.begin(), so.bytes.end());
+  FqV list;
+  Fq brp[3];
+  int rc = multi_eval(ctx, C, so.ch[2], so.ch[3], &list);
+  if (rc) return rc;
+  bound_rp(list, order, so.ch[0], brp);
+  for (auto& e : list) t.scalar("ABCr_claim", e);
+  t.challenge("challenge_c0");
+  t.challenge("challenge_c1");
+  t.challenge("challenge_c2");
+  for (int k = 0; k < 3; k++) w.fq(brp[k]);
+  w.fqs(list);
+  if (!as_list) return spark_prove_core(ctx, C->sparks[0], so.ch[2], so.ch[3], list, t, tape, w);
+  w.u64(C->sparks.size());
+  for (size_t gi = 0; gi < C->sparks.size(); gi++) {
+    FqV ev;
+    for (auto l : C->label_map[gi]) ev.push_back(list[l]);
+    if ((rc = spark_prove_core(ctx, C->sparks[gi], so.ch[2], so.ch[3], ev, t, tape, w))) return rc;
+  }
+  return 0;
+}
+
+// BLOCK_CORRECTNESS_EXTRACT (lib.rs:2223-2309)
+int SnarkProver::prove_block() {
+  int rc = sat_prove(ctx, vars_gens, block->dev_sorted, sh.P, sh.bmax, sh.bnp_pad, a.num_vars, sh.bnv,
+                     {wpart(s_bvars), wpart(w0.s), wpart(bw.w2.s), wpart(bw.w3.s), wpart(bw.w3s.s)}, &Wt, transcript,
+                     tape_h, &so);
   if (rc) return rc;
   lp.lap("block_sat");
+  return sat_then_evals(block, sh.order, true);
+}
+
+// PAIRWISE_CHECK (lib.rs:2311-2424)
+int SnarkProver::prove_pairwise() {
+  SecInfo pw, pws;
+  std::vector<size_t> im;
+  int rc;
+  if ((rc = merge(ctx, {&pe.w3.s, &aphy.s, &avir.s}, &pw, &im))) return rc;
+  if ((rc = merge(ctx, {&pe.w3s.s, &aphys.s, &avirs.s}, &pws))) return rc;
+  std::vector<const SecInfo*> comps(im.size(), &w0.s);
+  for (size_t i = 0; i < im.size(); i++)
+    if (im[i] == 2) comps[i] = &ts.s;
+  const SecInfo tsb = concat(comps);
+  const size_t n = pw.num_proofs.size();
+  rc = sat_prove(ctx, vars_gens, pairwise->dev_sorted, n, sh.pairwise_size, pw.num_proofs, sh.pw_nv,
+                 std::vector<size_t>(n, sh.pw_nv), {wpart(pw), wpart(pws), wpart(tsb)}, &Wt, transcript, tape_h, &so);
+  if (rc) return rc;
+  return sat_then_evals(pairwise, sh.pw_order, false);
+}
+
+// PERM_ROOT (lib.rs:2426-2532)
+int SnarkProver::prove_perm_root() {
+  SecInfo w1, w2s, w3s, w4;
+  int rc;
+  if ((rc = merge(ctx, {&s_exec, &iphy.s, &ivir.s, &aphy.s, &avir.s}, &w1))) return rc;
+  if ((rc = merge(ctx, {&pe.w2.s, &mem[0].w2.s, &mem[1].w2.s, &mem[2].w2.s, &mem[3].w2.s}, &w2s))) return rc;
+  if ((rc = merge(ctx, {&pe.w3.s, &mem[0].w3.s, &mem[1].w3.s, &mem[2].w3.s, &mem[3].w3.s}, &w3s))) return rc;
+  if ((rc = merge(ctx, {&pe.w3s.s, &mem[0].w3s.s, &mem[1].w3s.s, &mem[2].w3s.s, &mem[3].w3s.s}, &w4))) return rc;
+  const size_t n = w1.num_proofs.size();
+  rc = sat_prove(ctx, vars_gens, perm_root->dev, n, sh.perm_size, w1.num_proofs, num_ios, std::vector<size_t>(n, num_ios),
+                 {wpart(w0.s), wpart(w1), wpart(w2s), wpart(w3s), wpart(w4)}, &Wt, transcript, tape_h, &so);
+  if (rc) return rc;
   w.out.insert(w.out.end(), so.bytes.begin(), so.bytes.end());
-  {
-    FqV list;
-    Fq brp[3];
-    if ((rc = multi_eval(ctx, block, so.ch[2], so.ch[3], &list))) return rc;
-    bound_rp(list, order, so.ch[0], brp);
-    for (auto& e : list) t.scalar("ABCr_claim", e);
-    t.challenge("challenge_c0");
-    t.challenge("challenge_c1");
-    t.challenge("challenge_c2");
-    for (int k = 0; k < 3; k++) w.fq(brp[k]);
-    w.fqs(list);
-    w.u64(block->sparks.size());
-    for (size_t gi = 0; gi < block->sparks.size(); gi++) {
-      FqV ev;
-      for (auto l : block->label_map[gi]) ev.push_back(list[l]);
-      if ((rc = spark_prove_core(ctx, block->sparks[gi], so.ch[2], so.ch[3], ev, t, tape, w))) return rc;
+  FqV e;
+  if ((rc = multi_eval(ctx, perm_root, so.ch[2], so.ch[3], &e))) return rc;
+  t.scalar("Ar_claim", e[0]);
+  t.scalar("Br_claim", e[1]);
+  t.scalar("Cr_claim", e[2]);
+  for (int k = 0; k < 3; k++) w.fq(e[k]);
+  return spark_prove_core(ctx, perm_root->sparks[0], so.ch[2], so.ch[3], FqV(e.begin(), e.begin() + 3), t, tape, w);
+}
+
+// PERM_PRODUCT_PROOF (lib.rs:2534-2609): every w3 polynomial's product entry opened in one batched proof; the block
+// w3 polynomials appear once per chain they carry (exec, then physical, then virtual memory)
+int SnarkProver::prove_perm_product() {
+  std::vector<const SecInfo*> comps = {&pe.w3.s, &mem[0].w3.s, &mem[1].w3.s, &mem[2].w3.s, &mem[3].w3.s, &bw.w3.s};
+  if (a.max_block_num_phy_ops > 0) comps.push_back(&bw.w3.s);
+  if (a.max_block_num_vir_ops > 0) comps.push_back(&bw.w3.s);
+  std::vector<size_t> im;
+  SecInfo pw3;
+  int rc = merge(ctx, comps, &pw3, &im);
+  if (rc) return rc;
+  const size_t pm_bl_id = 6, vm_bl_id = a.max_block_num_phy_ops > 0 ? 7 : 6;
+  FqV prod;
+  std::vector<FqV> r_list;
+  for (size_t i = 0; i < im.size(); i++) {
+    const FqV& p = *pw3.poly[i];
+    if (im[i] == vm_bl_id) {
+      prod.push_back(p[6]);
+      r_list.push_back({fq_one(), fq_one(), fq_zero()});
+    } else if (im[i] == pm_bl_id) {
+      prod.push_back(p[4]);
+      r_list.push_back({fq_one(), fq_zero(), fq_zero()});
+    } else {
+      prod.push_back(p[2]);
+      r_list.push_back({fq_one(), fq_zero()});
     }
   }
-  lp.lap("block_eval");
-  // ---- PAIRWISE_CHECK (lib.rs:2311-2424)
-  {
-    const size_t pairwise_size = std::max({consis, t_phy, t_vir});
-    std::vector<size_t> im, im2;
-    SecInfo pw = merge({&s_pe3, &s_aphy, &s_avir}, &im);
-    SecInfo pws = merge({&s_pe3s, &s_aphys, &s_avirs}, &im2);
-    std::vector<const SecInfo*> comps(im.size(), &s_w0);
-    for (size_t i = 0; i < im.size(); i++)
-      if (im[i] == 2) comps[i] = &s_ts;
-    SecInfo tsb = concat(comps);
-    const size_t pw_nv = std::max<size_t>(8, a.mem_addr_ts_bits_size);
-    rc = sat_prove(ctx, vars_gens, pairwise->dev_sorted, pw.num_proofs.size(), pairwise_size, pw.num_proofs, pw_nv,
-                   std::vector<size_t>(pw.num_proofs.size(), pw_nv), {wpart(pw), wpart(pws), wpart(tsb)}, &Wt,
-                   transcript, tape_h, &so);
-    if (rc) return rc;
-    w.out.insert(w.out.end(), so.bytes.begin(), so.bytes.end());
-    FqV list;
-    Fq brp[3];
-    if ((rc = multi_eval(ctx, pairwise, so.ch[2], so.ch[3], &list))) return rc;
-    bound_rp(list, pw_order, so.ch[0], brp);
-    for (auto& e : list) t.scalar("ABCr_claim", e);
-    t.challenge("challenge_c0");
-    t.challenge("challenge_c1");
-    t.challenge("challenge_c2");
-    for (int k = 0; k < 3; k++) w.fq(brp[k]);
-    w.fqs(list);
-    if ((rc = spark_prove_core(ctx, pairwise->sparks[0], so.ch[2], so.ch[3], list, t, tape, w))) return rc;
+  w.fqs(prod);
+  return prove_batched_instances(ctx, g, pw3.poly, r_list, prod, t, tape, w);
+}
+
+// SHIFT_PROOFS (lib.rs:2611-2668)
+int SnarkProver::prove_shift() {
+  std::vector<const FqV*> orig, shifted;
+  std::vector<size_t> hl;
+  for (const ShiftPair& sp : shift_pairs(sh)) {
+    const HostSec *o = nullptr, *s = nullptr;
+    switch (sp.kind) {
+      case ShiftPair::kPermExecW3: o = &pe.w3, s = &pe.w3s; break;
+      case ShiftPair::kBlockW3: o = &bw.w3, s = &bw.w3s; break;
+      case ShiftPair::kMemW3: o = &mem[sp.idx].w3, s = &mem[sp.idx].w3s; break;
+      case ShiftPair::kAddrPhy: o = &aphy, s = &aphys; break;
+      case ShiftPair::kAddrVir: o = &avir, s = &avirs; break;
+    }
+    const size_t p = sp.kind == ShiftPair::kBlockW3 ? sp.idx : 0;
+    orig.push_back(&o->poly[p]);
+    shifted.push_back(&s->poly[p]);
+    hl.push_back(sp.header);
   }
-  lp.lap("pairwise");
-  // ---- PERM_ROOT (lib.rs:2426-2532)
+  const size_t n = orig.size();
+  std::vector<std::vector<Pt>> openings(n);
   {
-    const size_t perm_size = std::max({consis, t_iphy, t_ivir, t_phy, t_vir});
-    std::vector<size_t> m1, m2, m3, m4;
-    SecInfo w1 = merge({&s_exec, &s_iphy, &s_ivir, &s_aphy, &s_avir}, &m1);
-    SecInfo w2s = merge({&s_pe2, &m_iphy.s2, &m_ivir.s2, &m_phy.s2, &m_vir.s2}, &m2);
-    SecInfo w3s_ = merge({&s_pe3, &m_iphy.s3, &m_ivir.s3, &m_phy.s3, &m_vir.s3}, &m3);
-    SecInfo w4 = merge({&s_pe3s, &m_iphy.s3s, &m_ivir.s3s, &m_phy.s3s, &m_vir.s3s}, &m4);
-    std::vector<size_t> pr_np = w1.num_proofs;
-    rc = sat_prove(ctx, vars_gens, perm_root->dev, pr_np.size(), perm_size, pr_np, num_ios,
-                   std::vector<size_t>(pr_np.size(), num_ios), {wpart(s_w0), wpart(w1), wpart(w2s), wpart(w3s_), wpart(w4)},
-                   &Wt, transcript, tape_h, &so);
-    if (rc) return rc;
-    w.out.insert(w.out.end(), so.bytes.begin(), so.bytes.end());
-    FqV e;
-    if ((rc = multi_eval(ctx, perm_root, so.ch[2], so.ch[3], &e))) return rc;
-    t.scalar("Ar_claim", e[0]);
-    t.scalar("Br_claim", e[1]);
-    t.scalar("Cr_claim", e[2]);
-    for (int k = 0; k < 3; k++) w.fq(e[k]);
-    if ((rc = spark_prove_core(ctx, perm_root->sparks[0], so.ch[2], so.ch[3], FqV(e.begin(), e.begin() + 3), t, tape,
-                               w)))
-      return rc;
-  }
-  lp.lap("perm_root");
-  // ---- PERM_PRODUCT_PROOF (lib.rs:2534-2609)
-  {
-    std::vector<const SecInfo*> comps = {&s_pe3, &m_iphy.s3, &m_ivir.s3, &m_phy.s3, &m_vir.s3, &s_bw3};
-    if (a.max_block_num_phy_ops > 0) comps.push_back(&s_bw3);
-    if (a.max_block_num_vir_ops > 0) comps.push_back(&s_bw3);
-    std::vector<size_t> im;
-    SecInfo pw3 = merge(comps, &im);
-    const size_t pm_bl_id = 6, vm_bl_id = a.max_block_num_phy_ops > 0 ? 7 : 6;
-    FqV prod;
-    std::vector<FqV> r_list;
-    for (size_t i = 0; i < im.size(); i++) {
-      const FqV& p = *pw3.poly[i];
-      if (im[i] == vm_bl_id) {
-        prod.push_back(p[6]);
-        r_list.push_back({fq_one(), fq_one(), fq_zero()});
-      } else if (im[i] == pm_bl_id) {
-        prod.push_back(p[4]);
-        r_list.push_back({fq_one(), fq_zero(), fq_zero()});
-      } else {
-        prod.push_back(p[2]);
-        r_list.push_back({fq_one(), fq_zero()});
-      }
-    }
-    w.fqs(prod);
-    if ((rc = prove_batched_instances(ctx, g, pw3.poly, r_list, prod, t, tape, w))) return rc;
-  }
-  lp.lap("perm_product");
-  // ---- SHIFT_PROOFS (lib.rs:2611-2668)
-  {
-    std::vector<const FqV*> orig = {&pe_p3[0]}, shifted = {&pe_p3s[0]};
-    std::vector<size_t> hl = {6};
-    for (size_t p = 0; p < P; p++) {
-      orig.push_back(&b_p3[p]);
-      shifted.push_back(&b_p3s[p]);
-      hl.push_back(8);
-    }
-    if (t_iphy) {
-      orig.push_back(&m_iphy.p3[0]);
-      shifted.push_back(&m_iphy.p3s[0]);
-      hl.push_back(6);
-    }
-    if (t_ivir) {
-      orig.push_back(&m_ivir.p3[0]);
-      shifted.push_back(&m_ivir.p3s[0]);
-      hl.push_back(6);
-    }
-    if (t_phy) {
-      orig.push_back(&p_aphy[0]);
-      shifted.push_back(&p_aphys[0]);
-      hl.push_back(4);
-      orig.push_back(&m_phy.p3[0]);
-      shifted.push_back(&m_phy.p3s[0]);
-      hl.push_back(6);
-    }
-    if (t_vir) {
-      orig.push_back(&p_avir[0]);
-      shifted.push_back(&p_avirs[0]);
-      hl.push_back(6);
-      orig.push_back(&m_vir.p3[0]);
-      shifted.push_back(&m_vir.p3s[0]);
-      hl.push_back(6);
-    }
-    const size_t n = orig.size();
-    std::vector<std::vector<Pt>> openings(n);
-    {
-      std::vector<CJob> jobs;
-      for (size_t p = 0; p < n; p++)
-        for (size_t i = 0; i < hl[p]; i++) jobs.push_back(CJob(g.gens_1, {(*orig[p])[i]}, fq_zero()));
-      std::vector<Pt> pts = commit_batch(g, jobs);
-      size_t k = 0;
-      for (size_t p = 0; p < n; p++)
-        for (size_t i = 0; i < hl[p]; i++) {
-          t.point("shift_header_entry", pts[k]);
-          openings[p].push_back(pts[k++]);
-        }
-    }
-    const Fq c = t.challenge("challenge_c");
-    // the evaluations sum_k poly[k] c^k (lib.rs:2640-2655) from the uni-batched proof's L.Z bounds, computed once
-    // over the pool: sum_k LZ[k] c^k, LZ[k] = sum_j c^(Rs j) poly[j Rs + k]
-    std::vector<const FqV*> all(orig);
-    all.insert(all.end(), shifted.begin(), shifted.end());
-    const std::vector<FqV> LZs = uni_bounds(all, c);
-    size_t rs_max = 0;
-    for (auto& v : LZs) rs_max = std::max(rs_max, v.size());
-    FqV rc_pow(rs_max);
-    {
-      Fq nc = fq_one();
-      for (size_t i = 0; i < rs_max; i++) {
-        rc_pow[i] = nc;
-        nc = fq_mul(nc, c);
-      }
-    }
-    FqV ev(2 * n);
-    for (size_t p = 0; p < 2 * n; p++) {
-      Fq x = fq_zero();
-      for (size_t k = 0; k < LZs[p].size(); k++) x = fq_add(x, fq_mul(LZs[p][k], rc_pow[k]));
-      ev[p] = x;
-    }
     std::vector<CJob> jobs;
-    for (auto& x : ev) jobs.push_back(CJob(g.gens_1, {x}, fq_zero()));
-    std::vector<Pt> ce = commit_batch(g, jobs);
-    if ((rc = prove_uni_batched(ctx, g, all, LZs, c, ev, t, tape, w))) return rc;
-    w.pts(std::vector<Pt>(ce.begin(), ce.begin() + n));
-    w.pts(std::vector<Pt>(ce.begin() + n, ce.end()));
-    w.u64(n);
-    for (auto& o : openings) w.pts(o);
+    for (size_t p = 0; p < n; p++)
+      for (size_t i = 0; i < hl[p]; i++) jobs.push_back(CJob(g.gens_1, {(*orig[p])[i]}, fq_zero()));
+    std::vector<Pt> pts = commit_batch(g, jobs);
+    size_t k = 0;
+    for (size_t p = 0; p < n; p++)
+      for (size_t i = 0; i < hl[p]; i++) {
+        t.point("shift_header_entry", pts[k]);
+        openings[p].push_back(pts[k++]);
+      }
   }
-  lp.lap("shift");
-  // ---- IO_PROOFS (lib.rs:194-272)
-  {
-    const size_t r_len = lg2(consis * num_ios);
-    auto bin = [&](size_t x) {
-      FqV v;
-      for (size_t k = r_len; k-- > 0;) v.push_back(fq_from_u64((x >> k) & 1));
-      return v;
-    };
-    const std::vector<uint8_t>& live = W->liveness;
-    std::vector<size_t> idx;
-    for (size_t i = 0; i + 2 < live.size(); i++) idx.push_back(2 + a.input_offset + i);
-    if (live.size() > 1 && live[1]) idx.insert(idx.begin(), 5);
-    if (live.size() > 0 && live[0]) idx.insert(idx.begin(), 6);
-    FqV live_in;
-    for (size_t i = 0; i < live.size(); i++)
-      if (live[i]) live_in.push_back(W->input[i]);
-    idx.resize(live_in.size());
-    const size_t oe = a.output_exec_num * num_ios;
-    std::vector<size_t> pts = {0, oe, 2, oe + 2 + (niu - 1), oe + 2 + (niu - 1) + a.output_offset - 1};
-    pts.insert(pts.end(), idx.begin(), idx.end());
-    std::vector<FqV> r_list;
-    for (auto x : pts) r_list.push_back(bin(x));
-    FqV Zr = {fq_one(), fq_one(), input_block_num, output_block_num, W->output};
-    Zr.insert(Zr.end(), live_in.begin(), live_in.end());
-    FqV Z = pad_pow2(flatten(W->exec));
-    if ((rc = prove_batched_points(ctx, g, Z, r_list, Zr, t, tape, w))) return rc;
+  const Fq c = t.challenge("challenge_c");
+  // the evaluations sum_k poly[k] c^k (lib.rs:2640-2655) from the uni-batched proof's L.Z bounds, computed once
+  // over the pool: sum_k LZ[k] c^k, LZ[k] = sum_j c^(Rs j) poly[j Rs + k]
+  std::vector<const FqV*> all(orig);
+  all.insert(all.end(), shifted.begin(), shifted.end());
+  const std::vector<FqV> LZs = uni_bounds(all, c);
+  size_t rs_max = 0;
+  for (auto& v : LZs) rs_max = std::max(rs_max, v.size());
+  FqV c_pow(rs_max);
+  Fq nc = fq_one();
+  for (size_t i = 0; i < rs_max; i++) {
+    c_pow[i] = nc;
+    nc = fq_mul(nc, c);
   }
-  lp.lap("io");
+  FqV ev(2 * n);
+  for (size_t p = 0; p < 2 * n; p++) {
+    Fq x = fq_zero();
+    for (size_t k = 0; k < LZs[p].size(); k++) x = fq_add(x, fq_mul(LZs[p][k], c_pow[k]));
+    ev[p] = x;
+  }
+  std::vector<CJob> jobs;
+  for (auto& x : ev) jobs.push_back(CJob(g.gens_1, {x}, fq_zero()));
+  std::vector<Pt> ce = commit_batch(g, jobs);
+  int rc = prove_uni_batched(ctx, g, all, LZs, c, ev, t, tape, w);
+  if (rc) return rc;
+  w.pts(std::vector<Pt>(ce.begin(), ce.begin() + n));
+  w.pts(std::vector<Pt>(ce.begin() + n, ce.end()));
+  w.u64(n);
+  for (auto& o : openings) w.pts(o);
+  return 0;
+}
+
+// IO_PROOFS (lib.rs:194-272)
+int SnarkProver::prove_io() {
+  const IoPoints io = io_points(a, sh.consis, W->liveness.data(), W->liveness.size(), W->input, W->output);
+  return prove_batched_points(ctx, g, pad_pow2(flatten(W->exec)), io.r_list(), io.Zr, t, tape, w);
+}
+
+// the trace lines of the whole prove, then the proof into the caller's buffer
+int SnarkProver::finish(uint8_t* proof, size_t proof_cap, size_t* proof_len) {
   lp.print();
-  if (getenv("SPG_TRACE") && atoi(getenv("SPG_TRACE")) >= 2) {
+  if (kn.trace >= 2) {
     fprintf(stderr, "[spg] sigma-protocol commitments: %zu calls, %zu commitments, %.0f us on the host\n",
                     g_commit_stats.calls, g_commit_stats.points, g_commit_stats.us);
     g_commit_stats = CommitStats();
@@ -1460,11 +1385,24 @@ static int spg_snark_prove_impl(spg_ctx* ctx, spg_snark_comp* block, spg_snark_c
     bursts0 = pool().bursts();
     keccak0 = keccak_count();
   }
-  if (getenv("SPG_COPY_TRACE") && atoi(getenv("SPG_COPY_TRACE"))) print_copy_counts();
+  if (kn.copy_trace) print_copy_counts();
   *proof_len = w.out.size();
   if (!proof || w.out.size() > proof_cap) return set_err(ctx, SPG_E_ARG, "proof buffer too small");
   memcpy(proof, w.out.data(), w.out.size());
   return SPG_OK;
+}
+
+}  // namespace
+
+static int spg_snark_prove_impl(spg_ctx* ctx, spg_snark_comp* block, spg_snark_comp* pairwise, spg_snark_comp* perm_root,
+                               const spg_snark_wit* W, spg_r1cs_gens* vars_gens, spg_transcript* transcript,
+                               spg_random_tape* tape_h, uint8_t* proof, size_t proof_cap, size_t* proof_len) {
+  if (!ctx || !block || !pairwise || !perm_root || !W || !vars_gens || !transcript || !tape_h || !proof_len)
+    return SPG_E_ARG;
+  if (2 * W->a.num_inputs_unpadded > W->a.num_ios) return set_err(ctx, SPG_E_ARG, "num_ios < 2 * num_inputs_unpadded");
+  SnarkProver pr(ctx, block, pairwise, perm_root, W, vars_gens, transcript, tape_h);
+  const int rc = pr.run();
+  return rc ? rc : pr.finish(proof, proof_cap, proof_len);
 }
 
 extern "C" int spg_snark_prove(spg_ctx* ctx, spg_snark_comp* block, spg_snark_comp* pairwise, spg_snark_comp* perm_root,

@@ -282,10 +282,8 @@ static int encode_points(spg_ctx* ctx, const Ext* d_ext, size_t B, Pt* out, uint
 
 // L rows of R device scalars on the latency-path generators into device points: the comb tables when they apply
 // (>= 64 rows, >= 2^14 scalars in all), else the latency-path bucket kernels
-// (*halved: the comb path left P / 2, encode_points' halved form, when `want` -- batches of >= kHalvedMin points: below
-// that the host's lone encodings on the pool were as fast in the prover, 142 against 190 us for 128 rows;
-// SPG_HALVED_ENC=0 keeps the device / lone encodings everywhere)
-static const size_t kHalvedMin = 384;
+// (*halved: the comb path left P / 2, encode_points' halved form, when `want` -- batches of >= kHalvedMin points
+// (proto.hpp); SPG_HALVED_ENC=0 keeps the device / lone encodings everywhere)
 static int rows_to_points(spg_ctx* ctx, ProverGens& g, const Fq* d_Z, size_t R, size_t L, Ext* d_ext, bool* halved,
                           bool want) {
   static const bool on = !getenv("SPG_HALVED_ENC") || atoi(getenv("SPG_HALVED_ENC")) != 0;

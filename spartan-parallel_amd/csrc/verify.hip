@@ -21,6 +21,7 @@
 
 #include "hostpoly.hpp"
 #include "proto.hpp"
+#include "snark_shape.hpp"
 
 using namespace spg;
 using h::HExt;
@@ -718,27 +719,26 @@ struct V {
 struct VSec {
   std::vector<size_t> num_inputs, num_proofs;
   std::vector<PolyComm> comm_w;
-  // instances of the components interleaved by decreasing num_proofs (ties: the earlier component)
-  static VSec merge(const std::vector<const VSec*>& comps, std::vector<size_t>* inst_map) {
-    std::vector<size_t> ptr(comps.size(), 0);
-    size_t total = 0;
-    for (auto c : comps) total += c->num_inputs.size();
-    VSec s;
-    inst_map->clear();
-    while (inst_map->size() < total) {
-      size_t best = 0, nc = 0;
-      for (size_t i = 0; i < comps.size(); i++)
-        if (ptr[i] < comps[i]->num_proofs.size() && comps[i]->num_proofs[ptr[i]] > best) {
-          best = comps[i]->num_proofs[ptr[i]];
-          nc = i;
-        }
-      if (best == 0) throw Fail{"witness section sizes"};
-      inst_map->push_back(nc);
-      s.num_inputs.push_back(comps[nc]->num_inputs[ptr[nc]]);
-      s.num_proofs.push_back(comps[nc]->num_proofs[ptr[nc]]);
-      s.comm_w.push_back(comps[nc]->comm_w[ptr[nc]]);
-      ptr[nc]++;
+  // instances of the components interleaved by decreasing num_proofs (merge_order); inst_map (optional): the component
+  // each merged instance came from
+  static VSec merge(const std::vector<const VSec*>& comps, std::vector<size_t>* inst_map = nullptr) {
+    std::vector<const std::vector<size_t>*> sizes;
+    for (auto c : comps) {
+      if (c->num_inputs.size() != c->num_proofs.size() || c->comm_w.size() != c->num_proofs.size())
+        throw Fail{"witness section sizes"};
+      sizes.push_back(&c->num_proofs);
     }
+    std::vector<size_t> map;
+    if (!merge_order(sizes, &map)) throw Fail{"witness section sizes"};
+    VSec s;
+    std::vector<size_t> ptr(comps.size(), 0);
+    for (size_t c : map) {
+      const size_t k = ptr[c]++;
+      s.num_inputs.push_back(comps[c]->num_inputs[k]);
+      s.num_proofs.push_back(comps[c]->num_proofs[k]);
+      s.comm_w.push_back(comps[c]->comm_w[k]);
+    }
+    if (inst_map) *inst_map = map;
     return s;
   }
   static VSec concat(const std::vector<const VSec*>& comps) {
@@ -1065,8 +1065,6 @@ PolyComm commit_vec(spg_ctx* ctx, ProverGens& g, FqV Z) {
   return out;
 }
 
-const size_t INIT_PHY_MEM_WIDTH = 4, INIT_VIR_MEM_WIDTH = 4, PHY_MEM_WIDTH = 4, VIR_MEM_WIDTH = 8;
-
 // the public values SNARK::verify converts from bytes (src/lib.rs:2836-2850): input, output, and the input stack /
 // input memory whose init lists the verifier commits itself (:3274-3333); n = the list's length (unpadded)
 struct SnarkPub {
@@ -1075,115 +1073,59 @@ struct SnarkPub {
   FqV stack, mem;
 };
 
-// SNARK::verify (src/lib.rs:2750-3881)
-bool snark_verify(SnarkVerifier& v, const SnarkV& pf, const spg_snark_inputs& in, const SnarkPub& pub,
-                  const SnarkCompView& block, const SnarkCompView& pairwise, const SnarkCompView& perm_root,
-                  ProverGens& gpc) {
-  Tr& t = v.t;
-  const size_t niu = in.num_inputs_unpadded, num_ios = in.num_ios, Bb = in.block_num_instances_bound;
-  std::vector<size_t> bnv_all(in.block_num_vars, in.block_num_vars + Bb), bnp_all(in.block_num_proofs, in.block_num_proofs + Bb);
-  std::vector<size_t> phy(in.block_num_phy_ops, in.block_num_phy_ops + Bb), vir(in.block_num_vir_ops, in.block_num_vir_ops + Bb);
-  t.protocol("Spartan SNARK proof");
-  auto app = [&](const char* l, size_t x) { t.scalar(l, fq_from_u64(x)); };
-  app("func_input_width", in.func_input_width);
-  app("input_offset", in.input_offset);
-  app("output_offset", in.output_offset);
-  app("output_exec_num", in.output_exec_num);
-  app("num_ios", num_ios);
-  for (auto n : bnv_all) app("block_num_vars", n);
-  app("mem_addr_ts_bits_size", in.mem_addr_ts_bits_size);
-  app("num_inputs_unpadded", niu);
-  app("block_num_instances_bound", Bb);
-  app("block_max_num_proofs", in.block_max_num_proofs);
-  for (auto p : phy) app("block_num_phy_ops", p);
-  for (auto x : vir) app("block_num_vir_ops", x);
-  app("total_num_init_phy_mem_accesses", in.total_num_init_phy_mem_accesses);
-  app("total_num_init_vir_mem_accesses", in.total_num_init_vir_mem_accesses);
-  app("total_num_phy_mem_accesses", in.total_num_phy_mem_accesses);
-  app("total_num_vir_mem_accesses", in.total_num_vir_mem_accesses);
-  app("block_max_num_proofs", in.block_max_num_proofs);
-  for (auto n : bnp_all) app("block_num_proofs", n);
-  for (auto& b : *block.label_map)
-    for (auto l : b) app("block_comm_map", l);
-  auto comm_append = [&](const SnarkCompView& c, size_t gi) {  // R1CSCommitment::append_to_transcript
-    t.u64("num_cons", c.num_instances * c.max_num_cons);
-    t.u64("num_vars", c.num_vars);
-    spark_comm_append((*c.sparks)[gi], t);
-  };
-  for (size_t gi = 0; gi < block.sparks->size(); gi++) comm_append(block, gi);
-  comm_append(pairwise, 0);
-  comm_append(perm_root, 0);
-  const FqV& input = pub.input;
-  const Fq output = pub.output;
-  app("input_block_num", in.input_block_num);
-  app("output_block_num", in.output_block_num);
-  t.scalars("input_list", input);
-  t.scalar("output_list", output);
-  // sort and padding, sizes only (lib.rs:2922-3009)
-  size_t P = 0;
-  for (auto n : bnp_all)
-    if (n > 0) P++;
-  std::vector<size_t> order(Bb);
-  for (size_t i = 0; i < Bb; i++) order[i] = i;
-  std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return bnp_all[a] > bnp_all[b]; });
-  order.resize(P);
-  std::vector<size_t> bnp, bnv;
-  for (size_t i : order) {
-    bnp.push_back(npow2(bnp_all[i]));
-    bnv.push_back(bnv_all[i]);
+// SNARK::verify (src/lib.rs:2750-3881), split at the prover's stages (snark.hip SnarkProver): run() replays the
+// transcript in the prover's order and makes every check of the reference verifier
+struct SnarkCheck {
+  SnarkVerifier& v;
+  const SnarkV& pf;
+  const spg_snark_inputs& in;
+  const SnarkPub& pub;
+  const SnarkCompView &block, &pairwise, &perm_root;
+  ProverGens& gpc;
+  Tr& t;
+  const size_t niu, num_ios;
+  const SnarkShape sh;
+  PolyComm c_w0;
+  VSec w0, bw3;
+  VSec pe2, pe3, pe3s;  // perm-exec (w2, w3, w3_shifted)
+  VSec ms[4][3];        // memory (w2, w3, w3_shifted) of init phy / init vir / phy / vir
+  VSec ex1, init_phy_v, init_vir_v, addr_phy_v, addr_phy_sv, addr_vir_v, addr_vir_sv, ts_bits_v;
+
+  SnarkCheck(SnarkVerifier& ver, const SnarkV& proof, const spg_snark_inputs& inputs, const SnarkPub& p,
+             const SnarkCompView& b, const SnarkCompView& pw, const SnarkCompView& pr, ProverGens& g)
+      : v(ver), pf(proof), in(inputs), pub(p), block(b), pairwise(pw), perm_root(pr), gpc(g), t(ver.t),
+        niu(in.num_inputs_unpadded), num_ios(in.num_ios),
+        sh(in, in.block_num_proofs, in.block_num_vars, in.block_num_phy_ops, in.block_num_vir_ops) {}
+
+  bool run() {
+    t.protocol("Spartan SNARK proof");
+    append_instance();
+    return append_commitments() && check_block() && check_pairwise() && check_perm_root() && check_perm_product() &&
+           check_shift() && check_io();
   }
-  const size_t bmax = npow2(in.block_max_num_proofs), consis = npow2(in.consis_num_proofs);
-  auto pad0 = [](size_t x) { return x == 0 ? (size_t)0 : npow2(x); };
-  const size_t t_iphy = pad0(in.total_num_init_phy_mem_accesses), t_ivir = pad0(in.total_num_init_vir_mem_accesses),
-               t_phy = pad0(in.total_num_phy_mem_accesses), t_vir = pad0(in.total_num_vir_mem_accesses);
-  std::vector<std::pair<size_t, size_t>> ps = {{consis, 0}, {t_phy, 1}, {t_vir, 2}};
-  std::stable_sort(ps.begin(), ps.end(), [](const std::pair<size_t, size_t>& a, const std::pair<size_t, size_t>& b) {
-    return a.first > b.first;
-  });
-  std::vector<size_t> pw_index;
-  for (size_t i = 0; i < 1 + (t_phy > 0 ? 1 : 0) + (t_vir > 0 ? 1 : 0); i++) pw_index.push_back(ps[i].second);
-  // commitments in the prover's order
-  const Fq tau = t.challenge("challenge_tau"), r = t.challenge("challenge_r");
-  if (getenv("SPG_DEBUG_TR")) fprintf(stderr, "[verify] tau %08x r %08x\n", tau.l[0], r.l[0]);
-  FqV perm_w0 = {tau};
-  {
-    Fq rt = r;
-    for (size_t i = 1; i < 2 * niu; i++) {
-      perm_w0.push_back(rt);
-      rt = fq_mul(rt, r);
-    }
-    perm_w0.resize(num_ios, fq_zero());
+
+  void append_instance() {
+    append_snark_params(t, in, in.block_num_proofs, in.block_num_vars, in.block_num_phy_ops, in.block_num_vir_ops);
+    append_comm_map(t, *block.label_map);
+    auto comm_append = [&](const SnarkCompView& c, size_t gi) {  // R1CSCommitment::append_to_transcript
+      t.u64("num_cons", c.num_instances * c.max_num_cons);
+      t.u64("num_vars", c.num_vars);
+      spark_comm_append((*c.sparks)[gi], t);
+    };
+    for (size_t gi = 0; gi < block.sparks->size(); gi++) comm_append(block, gi);
+    comm_append(pairwise, 0);
+    comm_append(perm_root, 0);
+    append_snark_io(t, in, pub.input, pub.output);
   }
-  const PolyComm c_w0 = commit_vec(v.ctx, gpc, perm_w0);
-  append_polycomm(t, "poly_commitment", c_w0);
-  append_polycomm(t, "poly_commitment", pf.perm_exec_comm_w2_list);
-  append_polycomm(t, "poly_commitment", pf.perm_exec_comm_w3_list);
-  append_polycomm(t, "poly_commitment", pf.perm_exec_comm_w3_shifted);
-  if (pf.block_comm_w2_list.size() != P || pf.block_comm_w3_list.size() != P || pf.block_comm_w3_list_shifted.size() != P ||
-      pf.block_comm_vars_list.size() != P || pf.exec_comm_inputs.size() != 1)
-    return v.fail("witness commitment counts");
-  for (auto& c : pf.block_comm_w2_list) append_polycomm(t, "poly_commitment", c);
-  for (size_t p = 0; p < P; p++) {
-    append_polycomm(t, "poly_commitment", pf.block_comm_w3_list[p]);
-    append_polycomm(t, "poly_commitment", pf.block_comm_w3_list_shifted[p]);
+
+  // one committed section of `total` rows; empty for a memory list the program does not use
+  static VSec mem_vsec(size_t width, size_t total, const PolyComm& c) {
+    return total ? vsec({width}, {total}, {c}) : VSec();
   }
-  // memory (w2, w3, w3_shifted) triples (lib.rs:3100-3240)
-  VSec ms[4][3];
-  const size_t totals[4] = {t_iphy, t_ivir, t_phy, t_vir}, widths[4] = {INIT_PHY_MEM_WIDTH, INIT_VIR_MEM_WIDTH, PHY_MEM_WIDTH, VIR_MEM_WIDTH};
-  for (int m = 0; m < 4; m++) {
-    if (totals[m] == 0) continue;
-    for (int k = 0; k < 3; k++) append_polycomm(t, "poly_commitment", pf.mem_comm[m][k]);
-    ms[m][0] = vsec({widths[m]}, {totals[m]}, {pf.mem_comm[m][0]});
-    ms[m][1] = vsec({8}, {totals[m]}, {pf.mem_comm[m][1]});
-    ms[m][2] = vsec({8}, {totals[m]}, {pf.mem_comm[m][2]});
-  }
-  for (auto& c : pf.block_comm_vars_list) append_polycomm(t, "poly_commitment", c);
-  append_polycomm(t, "poly_commitment", pf.exec_comm_inputs[0]);
   // the verifier commits the init lists itself from the public input stack / memory (lib.rs:3274-3333): rows
   // (1, 0, i, value_i) for the list, zero rows up to the padded total
-  auto init_vsec = [&](size_t total, const FqV& vals, size_t width) {
-    VSec s;
-    if (vals.empty()) return s;
+  VSec init_vsec(size_t total, const FqV& vals, size_t width) {
+    if (vals.empty()) return VSec();
     FqV flat(total * width, fq_zero());
     for (size_t i = 0; i < vals.size(); i++) {
       flat[i * width] = fq_one();
@@ -1193,109 +1135,146 @@ bool snark_verify(SnarkVerifier& v, const SnarkV& pf, const spg_snark_inputs& in
     const PolyComm c = commit_vec(v.ctx, gpc, flat);
     append_polycomm(t, "poly_commitment", c);
     return vsec({width}, {total}, {c});
-  };
-  if (pub.stack.size() > t_iphy || pub.mem.size() > t_ivir) return v.fail("init memory lists longer than their totals");
-  const VSec init_phy_v = init_vsec(t_iphy, pub.stack, INIT_PHY_MEM_WIDTH);
-  const VSec init_vir_v = init_vsec(t_ivir, pub.mem, INIT_VIR_MEM_WIDTH);
-  VSec addr_phy_v, addr_phy_sv, addr_vir_v, addr_vir_sv, ts_bits_v;
-  if (t_phy > 0) {
-    append_polycomm(t, "poly_commitment", pf.addr_comm_phy_mems);
-    append_polycomm(t, "poly_commitment", pf.addr_comm_phy_mems_shifted);
-    addr_phy_v = vsec({PHY_MEM_WIDTH}, {t_phy}, {pf.addr_comm_phy_mems});
-    addr_phy_sv = vsec({PHY_MEM_WIDTH}, {t_phy}, {pf.addr_comm_phy_mems_shifted});
   }
-  if (t_vir > 0) {
-    append_polycomm(t, "poly_commitment", pf.addr_comm_vir_mems);
-    append_polycomm(t, "poly_commitment", pf.addr_comm_vir_mems_shifted);
-    append_polycomm(t, "poly_commitment", pf.addr_comm_ts_bits);
-    addr_vir_v = vsec({VIR_MEM_WIDTH}, {t_vir}, {pf.addr_comm_vir_mems});
-    addr_vir_sv = vsec({VIR_MEM_WIDTH}, {t_vir}, {pf.addr_comm_vir_mems_shifted});
-    ts_bits_v = vsec({in.mem_addr_ts_bits_size}, {t_vir}, {pf.addr_comm_ts_bits});
-  }
-  // BLOCK_CORRECTNESS_EXTRACT
-  std::vector<size_t> w2sz;
-  for (size_t p = 0; p < P; p++) w2sz.push_back(npow2(2 * niu + 2 * phy[order[p]] + 4 * vir[order[p]]));
-  const VSec bv = vsec(bnv, bnp, pf.block_comm_vars_list), w0 = vsec({num_ios}, {1}, {c_w0}),
-             bw2 = vsec(w2sz, bnp, pf.block_comm_w2_list), bw3 = vsec(std::vector<size_t>(P, 8), bnp, pf.block_comm_w3_list),
-             bw3s = vsec(std::vector<size_t>(P, 8), bnp, pf.block_comm_w3_list_shifted);
-  std::vector<FqV> ch;
-  if (!v.r1cs(gpc, pf.block_sat, P, bmax, bnp, in.num_vars, {&bv, &w0, &bw2, &bw3, &bw3s}, block.max_num_cons,
-              pf.block_bound, &ch))
-    return false;
-  auto bound_rp = [&](const FqV& list, const FqV& rp, const Fq bound[3], const std::vector<size_t>& index) {
-    FqV a, b, c;
-    for (size_t i : index) {
-      if (3 * i + 2 >= list.size()) return false;
-      a.push_back(list[3 * i]);
-      b.push_back(list[3 * i + 1]);
-      c.push_back(list[3 * i + 2]);
+
+  // the witness commitments in the prover's order (the commit queue's), each with its section
+  bool append_commitments() {
+    auto app = [&](const PolyComm& c) { append_polycomm(t, "poly_commitment", c); };
+    const Fq tau = t.challenge("challenge_tau"), r = t.challenge("challenge_r");
+    if (getenv("SPG_DEBUG_TR")) fprintf(stderr, "[verify] tau %08x r %08x\n", tau.l[0], r.l[0]);
+    c_w0 = commit_vec(v.ctx, gpc, perm_w0(tau, r, niu, num_ios));
+    app(c_w0);
+    app(pf.perm_exec_comm_w2_list);
+    app(pf.perm_exec_comm_w3_list);
+    app(pf.perm_exec_comm_w3_shifted);
+    const size_t P = sh.P;
+    if (pf.block_comm_w2_list.size() != P || pf.block_comm_w3_list.size() != P || pf.block_comm_w3_list_shifted.size() != P ||
+        pf.block_comm_vars_list.size() != P || pf.exec_comm_inputs.size() != 1)
+      return v.fail("witness commitment counts");
+    for (auto& c : pf.block_comm_w2_list) app(c);
+    for (size_t p = 0; p < P; p++) {
+      app(pf.block_comm_w3_list[p]);
+      app(pf.block_comm_w3_list_shifted[p]);
     }
-    return fq_eq(dense_eval_host(a, rp), bound[0]) && fq_eq(dense_eval_host(b, rp), bound[1]) &&
-           fq_eq(dense_eval_host(c, rp), bound[2]);
-  };
-  {
+    // memory (w2, w3, w3_shifted) triples (lib.rs:3100-3240)
+    const size_t totals[4] = {sh.t_iphy, sh.t_ivir, sh.t_phy, sh.t_vir},
+                 widths[4] = {INIT_PHY_MEM_WIDTH, INIT_VIR_MEM_WIDTH, PHY_MEM_WIDTH, VIR_MEM_WIDTH};
+    for (int m = 0; m < 4; m++)
+      for (int k = 0; k < 3 && totals[m]; k++) {
+        app(pf.mem_comm[m][k]);
+        ms[m][k] = mem_vsec(k == 0 ? widths[m] : W3_WIDTH, totals[m], pf.mem_comm[m][k]);
+      }
+    for (auto& c : pf.block_comm_vars_list) app(c);
+    app(pf.exec_comm_inputs[0]);
+    if (pub.stack.size() > sh.t_iphy || pub.mem.size() > sh.t_ivir) return v.fail("init memory lists longer than their totals");
+    init_phy_v = init_vsec(sh.t_iphy, pub.stack, INIT_PHY_MEM_WIDTH);
+    init_vir_v = init_vsec(sh.t_ivir, pub.mem, INIT_VIR_MEM_WIDTH);
+    if (sh.t_phy > 0) {
+      app(pf.addr_comm_phy_mems);
+      app(pf.addr_comm_phy_mems_shifted);
+    }
+    if (sh.t_vir > 0) {
+      app(pf.addr_comm_vir_mems);
+      app(pf.addr_comm_vir_mems_shifted);
+      app(pf.addr_comm_ts_bits);
+    }
+    addr_phy_v = mem_vsec(PHY_MEM_WIDTH, sh.t_phy, pf.addr_comm_phy_mems);
+    addr_phy_sv = mem_vsec(PHY_MEM_WIDTH, sh.t_phy, pf.addr_comm_phy_mems_shifted);
+    addr_vir_v = mem_vsec(VIR_MEM_WIDTH, sh.t_vir, pf.addr_comm_vir_mems);
+    addr_vir_sv = mem_vsec(VIR_MEM_WIDTH, sh.t_vir, pf.addr_comm_vir_mems_shifted);
+    ts_bits_v = mem_vsec(in.mem_addr_ts_bits_size, sh.t_vir, pf.addr_comm_ts_bits);
+    w0 = vsec({num_ios}, {1}, {c_w0});
+    bw3 = vsec(std::vector<size_t>(P, W3_WIDTH), sh.bnp_pad, pf.block_comm_w3_list);
+    pe2 = vsec({num_ios}, {sh.consis}, {pf.perm_exec_comm_w2_list});
+    pe3 = vsec({W3_WIDTH}, {sh.consis}, {pf.perm_exec_comm_w3_list});
+    pe3s = vsec({W3_WIDTH}, {sh.consis}, {pf.perm_exec_comm_w3_shifted});
+    ex1 = vsec({num_ios}, {sh.consis}, {pf.exec_comm_inputs[0]});
+    return true;
+  }
+
+  // After an R1CSProof over the instances of c, as the prover's sat_then_evals: the claimed evaluations against their
+  // rp-bound in the sorted `order`, the claims into the transcript, then one R1CSEvalProof per commitment of a
+  // multi-commitment instance, or the one proof over all evaluations. what: the failure messages for (evaluation
+  // count, rp-bound evaluations, SPARK proof count; the last null for the single proof)
+  bool sat_then_evals(const SnarkCompView& c, const std::vector<FqV>& ch, const FqV& evals, const Fq bound[3],
+                      const std::vector<size_t>& order, const std::vector<const SparkV*>& proofs, const char* const what[3]) {
     const FqV &rp = ch[0], &rx = ch[2], &ry = ch[3];
-    if (pf.block_evals.size() != 3 * block.num_instances) return v.fail("block evaluation count");
-    if (!bound_rp(pf.block_evals, rp, pf.block_bound, order)) return v.fail("block rp-bound evaluations");
-    for (auto& e : pf.block_evals) t.scalar("ABCr_claim", e);
+    if (evals.size() != 3 * c.num_instances) return v.fail(what[0]);
+    for (int m = 0; m < 3; m++) {
+      FqV col;
+      for (size_t i : order) {
+        if (3 * i + 2 >= evals.size()) return v.fail(what[1]);
+        col.push_back(evals[3 * i + m]);
+      }
+      if (!fq_eq(dense_eval_host(col, rp), bound[m])) return v.fail(what[1]);
+    }
+    for (auto& e : evals) t.scalar("ABCr_claim", e);
     t.challenge("challenge_c0");
     t.challenge("challenge_c1");
     t.challenge("challenge_c2");
-    if (pf.block_eval_proofs.size() != block.sparks->size()) return v.fail("block SPARK proof count");
-    for (size_t i = 0; i < block.sparks->size(); i++) {
+    if (what[2] && proofs.size() != c.sparks->size()) return v.fail(what[2]);
+    if (!what[2]) return v.spark((*c.sparks)[0], *proofs[0], rx, ry, evals);
+    for (size_t i = 0; i < proofs.size(); i++) {
       FqV ev;
-      for (auto l : (*block.label_map)[i]) ev.push_back(pf.block_evals[l]);
-      if (!v.spark((*block.sparks)[i], pf.block_eval_proofs[i], rx, ry, ev)) return false;
+      for (auto l : (*c.label_map)[i]) ev.push_back(evals[l]);
+      if (!v.spark((*c.sparks)[i], *proofs[i], rx, ry, ev)) return false;
     }
+    return true;
   }
+
+  // BLOCK_CORRECTNESS_EXTRACT
+  bool check_block() {
+    const size_t P = sh.P;
+    std::vector<size_t> w2sz;
+    for (size_t p = 0; p < P; p++) w2sz.push_back(sh.w2_size(p));
+    const VSec bv = vsec(sh.bnv, sh.bnp_pad, pf.block_comm_vars_list), bw2 = vsec(w2sz, sh.bnp_pad, pf.block_comm_w2_list),
+               bw3s = vsec(std::vector<size_t>(P, W3_WIDTH), sh.bnp_pad, pf.block_comm_w3_list_shifted);
+    std::vector<FqV> ch;
+    if (!v.r1cs(gpc, pf.block_sat, P, sh.bmax, sh.bnp_pad, in.num_vars, {&bv, &w0, &bw2, &bw3, &bw3s}, block.max_num_cons,
+                pf.block_bound, &ch))
+      return false;
+    std::vector<const SparkV*> proofs;
+    for (auto& p : pf.block_eval_proofs) proofs.push_back(&p);
+    static const char* const what[3] = {"block evaluation count", "block rp-bound evaluations", "block SPARK proof count"};
+    return sat_then_evals(block, ch, pf.block_evals, pf.block_bound, sh.order, proofs, what);
+  }
+
   // PAIRWISE_CHECK (lib.rs:3474-3568)
-  const VSec pe3 = vsec({8}, {consis}, {pf.perm_exec_comm_w3_list}), pe3s = vsec({8}, {consis}, {pf.perm_exec_comm_w3_shifted});
-  const size_t pw_nv = std::max<size_t>(8, in.mem_addr_ts_bits_size);
-  std::vector<size_t> pw_map, pw_map2;
-  const VSec pw = VSec::merge({&pe3, &addr_phy_v, &addr_vir_v}, &pw_map);
-  const VSec pws = VSec::merge({&pe3s, &addr_phy_sv, &addr_vir_sv}, &pw_map2);
-  VSec pwb;
-  {
+  bool check_pairwise() {
+    std::vector<size_t> pw_map;
+    const VSec pw = VSec::merge({&pe3, &addr_phy_v, &addr_vir_v}, &pw_map);
+    const VSec pws = VSec::merge({&pe3s, &addr_phy_sv, &addr_vir_sv});
     std::vector<const VSec*> comps(pw_map.size(), &w0);
     for (size_t i = 0; i < pw_map.size(); i++)
       if (pw_map[i] == 2) comps[i] = &ts_bits_v;
-    pwb = VSec::concat(comps);
+    const VSec pwb = VSec::concat(comps);
+    std::vector<FqV> ch;
+    if (!v.r1cs(gpc, pf.pairwise_sat, pw.num_proofs.size(), sh.pairwise_size, pw.num_proofs, sh.pw_nv, {&pw, &pws, &pwb},
+                pairwise.max_num_cons, pf.pairwise_bound, &ch))
+      return false;
+    static const char* const what[3] = {"pairwise evaluation count", "pairwise rp-bound evaluations", nullptr};
+    return sat_then_evals(pairwise, ch, pf.pairwise_evals, pf.pairwise_bound, sh.pw_order, {&pf.pairwise_eval_proof}, what);
   }
-  const size_t pairwise_size = std::max({consis, t_phy, t_vir});
-  if (!v.r1cs(gpc, pf.pairwise_sat, pw.num_proofs.size(), pairwise_size, pw.num_proofs, pw_nv, {&pw, &pws, &pwb},
-              pairwise.max_num_cons, pf.pairwise_bound, &ch))
-    return false;
-  {
-    const FqV &rp = ch[0], &rx = ch[2], &ry = ch[3];
-    if (pf.pairwise_evals.size() != 3 * pairwise.num_instances) return v.fail("pairwise evaluation count");
-    if (!bound_rp(pf.pairwise_evals, rp, pf.pairwise_bound, pw_index)) return v.fail("pairwise rp-bound evaluations");
-    for (auto& e : pf.pairwise_evals) t.scalar("ABCr_claim", e);
-    t.challenge("challenge_c0");
-    t.challenge("challenge_c1");
-    t.challenge("challenge_c2");
-    if (!v.spark((*pairwise.sparks)[0], pf.pairwise_eval_proof, rx, ry, pf.pairwise_evals)) return false;
-  }
+
   // PERM_EXEC_ROOT, MEM_ADDR_ROOT (lib.rs:3569-3650)
-  const VSec ex1 = vsec({num_ios}, {consis}, {pf.exec_comm_inputs[0]}), pw2 = vsec({num_ios}, {consis}, {pf.perm_exec_comm_w2_list});
-  std::vector<size_t> mm;
-  const VSec r1 = VSec::merge({&ex1, &init_phy_v, &init_vir_v, &addr_phy_v, &addr_vir_v}, &mm);
-  const VSec r2 = VSec::merge({&pw2, &ms[0][0], &ms[1][0], &ms[2][0], &ms[3][0]}, &mm);
-  const VSec r3 = VSec::merge({&pe3, &ms[0][1], &ms[1][1], &ms[2][1], &ms[3][1]}, &mm);
-  const VSec r3s = VSec::merge({&pe3s, &ms[0][2], &ms[1][2], &ms[2][2], &ms[3][2]}, &mm);
-  const size_t perm_size = std::max({consis, t_iphy, t_ivir, t_phy, t_vir});
-  if (!v.r1cs(gpc, pf.perm_root_sat, r1.num_proofs.size(), perm_size, r1.num_proofs, num_ios, {&w0, &r1, &r2, &r3, &r3s},
-              perm_root.max_num_cons, pf.perm_root_evals, &ch))
-    return false;
-  {
-    const FqV &rx = ch[2], &ry = ch[3];
+  bool check_perm_root() {
+    const VSec r1 = VSec::merge({&ex1, &init_phy_v, &init_vir_v, &addr_phy_v, &addr_vir_v});
+    const VSec r2 = VSec::merge({&pe2, &ms[0][0], &ms[1][0], &ms[2][0], &ms[3][0]});
+    const VSec r3 = VSec::merge({&pe3, &ms[0][1], &ms[1][1], &ms[2][1], &ms[3][1]});
+    const VSec r3s = VSec::merge({&pe3s, &ms[0][2], &ms[1][2], &ms[2][2], &ms[3][2]});
+    std::vector<FqV> ch;
+    if (!v.r1cs(gpc, pf.perm_root_sat, r1.num_proofs.size(), sh.perm_size, r1.num_proofs, num_ios, {&w0, &r1, &r2, &r3, &r3s},
+                perm_root.max_num_cons, pf.perm_root_evals, &ch))
+      return false;
     t.scalar("Ar_claim", pf.perm_root_evals[0]);
     t.scalar("Br_claim", pf.perm_root_evals[1]);
     t.scalar("Cr_claim", pf.perm_root_evals[2]);
     const FqV e(pf.perm_root_evals, pf.perm_root_evals + 3);
-    if (!v.spark((*perm_root.sparks)[0], pf.perm_root_eval_proof, rx, ry, e)) return false;
+    return v.spark((*perm_root.sparks)[0], pf.perm_root_eval_proof, ch[2], ch[3], e);
   }
+
   // PERM_PRODUCT openings and identities (lib.rs:3652-3772)
-  {
+  bool check_perm_product() {
     std::vector<const VSec*> comps = {&pe3, &ms[0][1], &ms[1][1], &ms[2][1], &ms[3][1], &bw3};
     if (in.max_block_num_phy_ops > 0) comps.push_back(&bw3);
     if (in.max_block_num_vir_ops > 0) comps.push_back(&bw3);
@@ -1335,32 +1314,26 @@ bool snark_verify(SnarkVerifier& v, const SnarkV& pf, const spg_snark_inputs& in
     if (!fq_eq(pe, pb)) return v.fail("execution / block permutation products");
     if (!fq_eq(pmb, pma)) return v.fail("physical memory permutation products");
     if (!fq_eq(vmb, vma)) return v.fail("virtual memory permutation products");
+    return true;
   }
+
   // SHIFT_PROOFS (lib.rs:3772-3853 -> ShiftProofs::verify :449-506)
-  {
-    std::vector<const PolyComm*> orig = {&pf.perm_exec_comm_w3_list}, shifted = {&pf.perm_exec_comm_w3_shifted};
-    std::vector<size_t> sizes = {8 * consis}, hl = {6};
-    for (size_t p = 0; p < P; p++) {
-      orig.push_back(&pf.block_comm_w3_list[p]);
-      shifted.push_back(&pf.block_comm_w3_list_shifted[p]);
-      sizes.push_back(8 * bnp[p]);
-      hl.push_back(8);
-    }
-    auto add = [&](const PolyComm& o, const PolyComm& sh, size_t size, size_t hh) {
-      orig.push_back(&o);
-      shifted.push_back(&sh);
-      sizes.push_back(size);
-      hl.push_back(hh);
-    };
-    if (t_iphy > 0) add(pf.mem_comm[0][1], pf.mem_comm[0][2], 8 * t_iphy, 6);
-    if (t_ivir > 0) add(pf.mem_comm[1][1], pf.mem_comm[1][2], 8 * t_ivir, 6);
-    if (t_phy > 0) {
-      add(pf.addr_comm_phy_mems, pf.addr_comm_phy_mems_shifted, 4 * t_phy, 4);
-      add(pf.mem_comm[2][1], pf.mem_comm[2][2], 8 * t_phy, 6);
-    }
-    if (t_vir > 0) {
-      add(pf.addr_comm_vir_mems, pf.addr_comm_vir_mems_shifted, 8 * t_vir, 6);
-      add(pf.mem_comm[3][1], pf.mem_comm[3][2], 8 * t_vir, 6);
+  bool check_shift() {
+    std::vector<const PolyComm*> orig, shifted;
+    std::vector<size_t> sizes, hl;
+    for (const ShiftPair& sp : shift_pairs(sh)) {
+      const PolyComm *o = nullptr, *s = nullptr;
+      switch (sp.kind) {
+        case ShiftPair::kPermExecW3: o = &pf.perm_exec_comm_w3_list, s = &pf.perm_exec_comm_w3_shifted; break;
+        case ShiftPair::kBlockW3: o = &pf.block_comm_w3_list[sp.idx], s = &pf.block_comm_w3_list_shifted[sp.idx]; break;
+        case ShiftPair::kMemW3: o = &pf.mem_comm[sp.idx][1], s = &pf.mem_comm[sp.idx][2]; break;
+        case ShiftPair::kAddrPhy: o = &pf.addr_comm_phy_mems, s = &pf.addr_comm_phy_mems_shifted; break;
+        case ShiftPair::kAddrVir: o = &pf.addr_comm_vir_mems, s = &pf.addr_comm_vir_mems_shifted; break;
+      }
+      orig.push_back(o);
+      shifted.push_back(s);
+      sizes.push_back(sp.size);
+      hl.push_back(sp.header);
     }
     if (pf.shift_openings.size() != orig.size() || pf.shift_orig_evals.size() != orig.size() ||
         pf.shift_shifted_evals.size() != orig.size())
@@ -1377,34 +1350,20 @@ bool snark_verify(SnarkVerifier& v, const SnarkV& pf, const spg_snark_inputs& in
     comms.insert(comms.end(), shifted.begin(), shifted.end());
     std::vector<size_t> sz2(sizes);
     sz2.insert(sz2.end(), sizes.begin(), sizes.end());
-    if (!v.pe_uni_batched(gpc, pf.shift_proof, c, evals, comms, sz2)) return false;
+    return v.pe_uni_batched(gpc, pf.shift_proof, c, evals, comms, sz2);
   }
+
   // IO_PROOFS (lib.rs:3855-3873 -> IOProofs::verify :283-359)
-  {
-    const size_t r_len = lg2(consis * num_ios);
-    std::vector<uint8_t> live_flags(in.input_liveness, in.input_liveness + in.input_len);
-    std::vector<size_t> idx;
-    for (size_t i = 0; i + 2 < live_flags.size(); i++) idx.push_back(2 + in.input_offset + i);
-    if (live_flags.size() > 1 && live_flags[1]) idx.insert(idx.begin(), 5);
-    if (!live_flags.empty() && live_flags[0]) idx.insert(idx.begin(), 6);
-    FqV live;
-    for (size_t i = 0; i < live_flags.size() && i < input.size(); i++)
-      if (live_flags[i]) live.push_back(input[i]);
-    idx.resize(live.size());
-    const size_t oe = in.output_exec_num * num_ios;
-    std::vector<size_t> pts = {0, oe, 2, oe + 2 + (niu - 1), oe + 2 + (niu - 1) + in.output_offset - 1};
-    pts.insert(pts.end(), idx.begin(), idx.end());
-    std::vector<FqV> r_list;
-    for (size_t p : pts) {
-      FqV bits(r_len);
-      for (size_t i = 0; i < r_len; i++) bits[i] = ((p >> (r_len - 1 - i)) & 1) ? fq_one() : fq_zero();
-      r_list.push_back(bits);
-    }
-    FqV Zr = {fq_one(), fq_one(), fq_from_u64(in.input_block_num), fq_from_u64(in.output_block_num), output};
-    Zr.insert(Zr.end(), live.begin(), live.end());
-    if (!v.pe_plain_batched_points(gpc, pf.io_proofs, r_list, Zr, pf.exec_comm_inputs[0])) return false;
+  bool check_io() {
+    const IoPoints io = io_points(in, sh.consis, in.input_liveness, in.input_len, pub.input, pub.output);
+    return v.pe_plain_batched_points(gpc, pf.io_proofs, io.r_list(), io.Zr, pf.exec_comm_inputs[0]);
   }
-  return true;
+};
+
+bool snark_verify(SnarkVerifier& v, const SnarkV& pf, const spg_snark_inputs& in, const SnarkPub& pub,
+                  const SnarkCompView& block, const SnarkCompView& pairwise, const SnarkCompView& perm_root,
+                  ProverGens& gpc) {
+  return SnarkCheck(v, pf, in, pub, block, pairwise, perm_root, gpc).run();
 }
 
 }  // namespace

@@ -172,6 +172,55 @@ def test_round_forms(form):
     assert out.stdout.split()[-1] == golden["proof_sha256"]
 
 
+# the smallest straight-line program whose block witnesses take the commit queue's early path: two block-vars
+# polynomials of 2^7 executions x 2^10 variables = 2^17 scalars each, so Hyrax rows of 2^9 > 256 scalars, 512 of them
+# (>= 384: the halved encodings)
+CQ_CASE = dict(num_blocks=2, log_cons=5, log_proofs=7, num_vars=1024)
+CQ_FORMS = {
+    "side_stream": ({}, " rows_side_launch="),
+    "one_stream": ({"SPG_CQ_SIDE": "0"}, " rows_launch="),
+    "row_encodings_on_device": ({"SPG_HALVED_ENC": "0"}, " rows_side_launch="),
+}
+
+
+@pytest.fixture(scope="module")
+def cq_ref(oracle):
+    import workload
+
+    ref, rc = oracle.snark_prove(workload.SnarkWorkload(**CQ_CASE), workload.tape_seed())
+    assert rc == 0, "oracle verifier rejected its own proof"
+    return hashlib.sha256(ref).hexdigest()
+
+
+@pytest.mark.parametrize("form", sorted(CQ_FORMS))
+def test_commit_queue_forms(cq_ref, form):
+    """the commit queue's early group (the block witnesses' rows in one batch MSM launched before the host builds the
+    permutation witnesses), which no smaller case reaches, against the oracle's bytes in a fresh process per form: the
+    other rows on the second stream (the default), on the main stream (SPG_CQ_SIDE=0), and the early rows encoded on
+    the device (SPG_HALVED_ENC=0) instead of from halved points on the host. The flush's trace line names the form
+    that ran; the side stream is taken only behind an early launch, so it also shows that this shape reaches it."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = (
+        "import sys, hashlib; sys.path[:0] = [%r, %r]\n"
+        "import spg, workload\n"
+        "from test_gpu_snark import gpu_snark, CQ_CASE, GENS_LABEL, GENS_NV\n"
+        "ctx = spg.Context(0)\n"
+        "g = spg.R1CSGens(ctx, GENS_LABEL, GENS_NV)\n"
+        "(p,) = gpu_snark(ctx, g, workload.SnarkWorkload(**CQ_CASE), workload.tape_seed())\n"
+        "print(hashlib.sha256(p).hexdigest())\n"
+    ) % (os.path.join(root, "spartan-parallel_amd"), os.path.join(root, "tests"))
+    env, lap = CQ_FORMS[form]
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, SPG_TRACE="2", **env),
+                         capture_output=True, text=True, timeout=240)
+    assert out.returncode == 0, out.stderr[-2000:]
+    flush = [l for l in out.stderr.splitlines() if "commit queue flush" in l]
+    assert flush and all(lap in l for l in flush), out.stderr[-2000:]
+    assert out.stdout.split()[-1] == cq_ref
+
+
 @pytest.mark.parametrize("host_max,comb", [("0", "1"), ("0", "0"), ("4096", "1")])
 def test_bullet_paths(host_max, comb):
     """every DotProductProofLog through the device Bullet rounds (SPG_BULLET_HOST_MAX=0) -- in the comb form
