@@ -35,7 +35,12 @@ struct SparseMat {
   // sparse_mlpoly.rs:454-472 : z[w][i] = col / max_num_cols, col % max_num_cols
   FqVec multiply_vec_disjoint_rounds(size_t num_rows, size_t max_num_cols, const std::vector<FqVec>& z) const {
     FqVec Mz(num_rows, fq_zero());
-    for (auto& e : M) Mz[e.row] = fq_add(Mz[e.row], fq_mul(e.val, z[e.col / max_num_cols][e.col % max_num_cols]));
+    for (auto& e : M) {
+      // the reference's slice indexing panics here; z[w] holds this instance's num_inputs entries, not max_num_cols
+      if (e.row >= num_rows || e.col / max_num_cols >= z.size() || e.col % max_num_cols >= z[e.col / max_num_cols].size())
+        throw std::string("multiply_vec: a matrix entry lies outside the instance's rows or its witness width");
+      Mz[e.row] = fq_add(Mz[e.row], fq_mul(e.val, z[e.col / max_num_cols][e.col % max_num_cols]));
+    }
     return Mz;
   }
   // sparse_mlpoly.rs:524-541
@@ -43,6 +48,8 @@ struct SparseMat {
                                                 size_t num_cols) const {
     std::vector<FqVec> out(num_segs, FqVec(num_cols, fq_zero()));
     for (auto& e : M) {
+      if (e.row >= rx.size() || e.col / max_num_cols >= num_segs || e.col % max_num_cols >= num_cols)
+        throw std::string("eval_table: a matrix entry lies outside the instance's rows or its witness width");
       Fq& d = out[e.col / max_num_cols][e.col % max_num_cols];
       d = fq_add(d, fq_mul(rx[e.row], e.val));
     }

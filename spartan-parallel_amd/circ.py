@@ -294,6 +294,18 @@ class CircProgram:
         # Instance::gen_block_inst / gen_pairwise_check_inst / gen_perm_root_inst (interface.rs:482-518)
         args = [[tuple([(col, scalar_from_bytes(v)) for col, v in terms] for terms in row) for row in block]
                 for block in ctk.args]
+        # a block's witness rows hold num_vars_per_block[b] entries: the io and memory-operation variables and every
+        # column a user row names must lie inside them (the reference indexes its vectors there and panics)
+        for b, block in enumerate(args):
+            w = self._num_vars_per_block[b]
+            if w > ctk.num_vars or w < 2 * niu + 2 * self.block_num_phy_ops[b] + 4 * self.block_num_vir_ops[b]:
+                raise ValueError(f"num_vars_per_block[{b}] = {w} does not hold the block's io and memory variables")
+            for i, row in enumerate(block):
+                for terms in row:
+                    for col, _ in terms:
+                        if col >= w:
+                            raise ValueError(f"block {b}, constraint {i}: column {col} is beyond "
+                                             f"num_vars_per_block[{b}] = {w}")
         self.block_num_vars, self.block_max_num_cons, self.block_nnz, self.block_inst = workload.gen_block_inst(
             ctk.num_vars, args, niu, self.block_num_phy_ops, self.block_num_vir_ops)
         (self.pairwise_num_vars, self.pairwise_max_num_cons, self.pairwise_nnz,

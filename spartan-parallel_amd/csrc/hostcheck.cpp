@@ -398,6 +398,15 @@ long spgh_snark_shape(size_t Bb, const size_t* nproofs, const size_t* nvars, con
   }
   return (long)s.P;
 }
+// block_width_violation (snark_shape.hpp), the check spg_snark_prove makes before any launch: the first executed
+// block whose io / memory-operation part or whose matrix columns reach beyond its block_num_vars, or -1
+long spgh_block_width_violation(size_t Bb, const size_t* nproofs, const size_t* nvars, const size_t* phy_ops,
+                                const size_t* vir_ops, size_t niu, size_t stride, const spg_sparse_entry* const* entries,
+                                const size_t* nnz) {
+  if (!stride) return 0;
+  const std::vector<size_t> need = block_cols_needed(Bb, stride, entries, nnz);
+  return block_width_violation(Bb, nproofs, nvars, phy_ops, vir_ops, niu, stride, need.data());
+}
 
 }  // extern "C"
 

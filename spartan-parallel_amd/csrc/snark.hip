@@ -89,6 +89,8 @@ struct spg_snark_comp {
   spg_r1cs_inst* dev = nullptr;
   spg_r1cs_inst* dev_sorted = nullptr;
   std::vector<size_t> sorted_order;
+  std::vector<size_t> cols_needed;  // block_cols_needed for section width cols_needed_stride (spg_snark_prove's check)
+  size_t cols_needed_stride = 0;
   spg_r1cs_instance view(const std::vector<size_t>& order, std::vector<const spg_sparse_entry*>* ptrs,
                          std::vector<size_t>* nnz_o, std::vector<size_t>* nc_o) const {
     ptrs->clear();
@@ -1400,6 +1402,20 @@ static int spg_snark_prove_impl(spg_ctx* ctx, spg_snark_comp* block, spg_snark_c
   if (!ctx || !block || !pairwise || !perm_root || !W || !vars_gens || !transcript || !tape_h || !proof_len)
     return SPG_E_ARG;
   if (2 * W->a.num_inputs_unpadded > W->a.num_ios) return set_err(ctx, SPG_E_ARG, "num_ios < 2 * num_inputs_unpadded");
+  {  // before any launch: a block whose rows or matrices reach beyond its witness width (snark_shape.hpp)
+    const size_t Bb = W->a.block_num_instances_bound;
+    if (block->num_instances != Bb || block->mats.size() != 3 * Bb || !W->a.num_vars)
+      return set_err(ctx, SPG_E_ARG, "block instance and witness disagree on the number of blocks");
+    if (block->cols_needed_stride != W->a.num_vars) {  // the matrices are read once per encoded instance
+      std::vector<const spg_sparse_entry*> ent;
+      for (auto& m : block->mats) ent.push_back(m.data());
+      block->cols_needed = block_cols_needed(Bb, W->a.num_vars, ent.data(), block->nnz.data());
+      block->cols_needed_stride = W->a.num_vars;
+    }
+    if (block_width_violation(Bb, W->nproofs.data(), W->nvars.data(), W->phy_ops.data(), W->vir_ops.data(),
+                              W->a.num_inputs_unpadded, W->a.num_vars, block->cols_needed.data()) >= 0)
+      return set_err(ctx, SPG_E_ARG, "a block names a column beyond its block_num_vars");
+  }
   SnarkProver pr(ctx, block, pairwise, perm_root, W, vars_gens, transcript, tape_h);
   const int rc = pr.run();
   return rc ? rc : pr.finish(proof, proof_cap, proof_len);

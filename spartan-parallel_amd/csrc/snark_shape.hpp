@@ -64,6 +64,28 @@ struct SnarkShape {
   }
 };
 
+// Block b's witness rows hold nvars[b] entries, and every section of its R1CS instance is that wide: the row's io and
+// memory-operation part (2 niu + 2 phy + 4 vir entries, which the w2 recurrences read on the host) and every column
+// its matrices name (col % stride, stride = num_vars: the section width of the matrices) must lie inside them. The
+// reference indexes its vectors there and panics; the device kernels would skip such entries (k_spmv, k_abc) and the
+// host would read past a row's end. block_cols_needed reads the matrices once (entries[3 b + m] / nnz[3 b + m]:
+// matrix m of block b, spg_r1cs_instance's layout): need[b] = 1 + the largest in-section column block b names, 0
+// without entries. block_width_violation returns the first executed block that breaks either rule, or -1.
+inline std::vector<size_t> block_cols_needed(size_t Bb, size_t stride, const spg_sparse_entry* const* entries,
+                                             const size_t* nnz) {
+  std::vector<size_t> need(Bb, 0);
+  for (size_t k = 0; k < 3 * Bb; k++)
+    for (size_t e = 0; e < nnz[k]; e++) need[k / 3] = std::max<size_t>(need[k / 3], entries[k][e].col % stride + 1);
+  return need;
+}
+inline long block_width_violation(size_t Bb, const size_t* nproofs, const size_t* nvars, const size_t* phy_ops,
+                                  const size_t* vir_ops, size_t niu, size_t stride, const size_t* need) {
+  for (size_t b = 0; b < Bb; b++)
+    if (nproofs[b] && (nvars[b] < 2 * niu + 2 * phy_ops[b] + 4 * vir_ops[b] || nvars[b] > stride || need[b] > nvars[b]))
+      return (long)b;
+  return -1;
+}
+
 // the parameters of the program, in the reference's order (block_max_num_proofs is appended twice there)
 template <class T>
 void append_snark_params(T& t, const spg_snark_inputs& a, const size_t* nproofs, const size_t* nvars,

@@ -214,16 +214,72 @@ def snark_fixture():
     return out
 
 
+def hetero_snark_fixture():
+    """snark_proofs.json entries of the heterogeneous programs (tests/hetero_program.py), keyed by case name: the
+    oracle's SNARK::prove after its verifier accepted"""
+    sys.path.insert(0, os.path.join(ROOT, "spartan-parallel_amd"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import hetero_program
+    import workload
+
+    out = {}
+    for name in sorted(hetero_program.CASES):
+        proof, rc = O.snark_prove(hetero_program.program(name), workload.tape_seed())
+        assert rc == 0, (name, rc)
+        out[name] = {"proof_sha256": hashlib.sha256(proof).hexdigest(), "proof_len": len(proof)}
+    return out
+
+
+def structured_spark_fixture():
+    """spark_proofs.json entries of the structured matrices (tests/sparse_cases.py), keyed structured_<case>"""
+    sys.path.insert(0, os.path.join(ROOT, "spartan-parallel_amd"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sparse_cases
+    import workload
+
+    out = {}
+    for name in sorted(sparse_cases.CASES):
+        wl = sparse_cases.structured(name)
+        rx, ry = sparse_cases.eval_point(O, wl)
+        comm, proof, ok = O.spark_prove(wl, rx, ry, workload.tape_seed())
+        assert ok, name
+        out["structured_" + name] = {"comm_sha256": hashlib.sha256(comm).hexdigest(),
+                                     "proof_sha256": hashlib.sha256(proof).hexdigest(), "proof_len": len(proof)}
+    return out
+
+
+def structured_r1cs_fixture():
+    """r1cs_proofs.json entries of the structured matrices, keyed structured_<case> (R1CSProof::prove alone: these
+    matrices are not satisfied by the witness), and of the satisfiable one after prove -> verify"""
+    sys.path.insert(0, os.path.join(ROOT, "spartan-parallel_amd"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import sparse_cases
+    import workload
+
+    out = {}
+    for name in sorted(sparse_cases.CASES):
+        pf, _ = O.r1cs_prove(sparse_cases.structured(name), workload.tape_seed())
+        out["structured_" + name] = {"len": len(pf), "sha256": hashlib.sha256(pf).hexdigest()}
+    wl = sparse_cases.satisfiable()
+    pf, _ = O.r1cs_prove(wl, workload.tape_seed())
+    assert O.r1cs_verify(wl, pf, workload.tape_seed()) == 1
+    out["structured_satisfiable"] = {"len": len(pf), "sha256": hashlib.sha256(pf).hexdigest()}
+    return out
+
+
 def main():
     O.build()
     if sys.argv[1:] == ["snark"]:
-        json.dump(snark_fixture(), open(os.path.join(HERE, "snark_proofs.json"), "w"), indent=1)
+        json.dump(dict(snark_fixture(), **hetero_snark_fixture()), open(os.path.join(HERE, "snark_proofs.json"), "w"),
+                  indent=1)
         return
     if sys.argv[1:] == ["r1cs"]:
-        json.dump(r1cs_fixture(), open(os.path.join(HERE, "r1cs_proofs.json"), "w"), indent=1)
+        json.dump(dict(r1cs_fixture(), **structured_r1cs_fixture()), open(os.path.join(HERE, "r1cs_proofs.json"), "w"),
+                  indent=1)
         return
     if sys.argv[1:] == ["spark"]:
-        json.dump(spark_fixture(), open(os.path.join(HERE, "spark_proofs.json"), "w"), indent=1)
+        json.dump(dict(spark_fixture(), **structured_spark_fixture()),
+                  open(os.path.join(HERE, "spark_proofs.json"), "w"), indent=1)
         return
     rng = np.random.default_rng(0x5350415254414E31)
     lib = sodium()
@@ -234,9 +290,9 @@ def main():
     w("gens_spg_bench_msm_first16.json", gens_fixture(lib, b"spg_bench_msm", 16))
     w("msm_64.json", msm_fixture(lib, rng, b"gens_r1cs_sat", 64))
     w("msm_256.json", msm_fixture(lib, rng, b"spg_bench_msm", 256))
-    w("r1cs_proofs.json", r1cs_fixture())
-    w("spark_proofs.json", spark_fixture())
-    w("snark_proofs.json", snark_fixture())
+    w("r1cs_proofs.json", dict(r1cs_fixture(), **structured_r1cs_fixture()))
+    w("spark_proofs.json", dict(spark_fixture(), **structured_spark_fixture()))
+    w("snark_proofs.json", dict(snark_fixture(), **hetero_snark_fixture()))
     print("golden fixtures written to", HERE)
 
 

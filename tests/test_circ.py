@@ -3,7 +3,9 @@ writer (spartan-parallel_amd/circ.py), and CircProgram's restatement of interfac
 construction. The byte layout is checked against files assembled field by field from the Rust struct definitions
 (interface.rs:45-71, 195-216; src/lib.rs:87-92), and a program that goes through the files proves to the same bytes
 as the program it was exported from (CPU oracle, whose verifier accepts them). The reference ships no .ctk/.rtk
-files (its zok_tests/ directory is not in the snapshot), so no CirC-generated file is exercised."""
+files (its zok_tests/ directory is not in the snapshot), so no CirC-generated file is exercised; programs with what
+such files have and SnarkWorkload lacks (block types of different sizes, long rows with arbitrary coefficients,
+per-block memory operations) come from tests/hetero_program.py (tests/test_hetero_program.py)."""
 import hashlib
 import json
 import os
@@ -130,3 +132,44 @@ def test_program_rejects_malformed_knowledge():
     r2.exec_inputs = r2.exec_inputs[:-1]
     with pytest.raises(ValueError, match="consis_num_proofs"):
         circ.CircProgram(ctk, r2)
+
+
+def out_of_width_program(executed=True):
+    """hetero_nomem_b4 with one user row naming column 20 of a block whose rows hold 16 entries (block 1, one
+    execution) or 40 of one that holds 32 (block 2, which never runs): (ctk, rtk, the program as CircProgram would
+    build it without its width check)"""
+    import circ
+    import hetero_program
+    import workload
+
+    ctk, rtk = hetero_program.build(**hetero_program.CASES["hetero_nomem_b4"])
+    prog = circ.CircProgram(ctk, rtk)
+    b, col = (1, 20) if executed else (2, 40)
+    assert ctk.num_vars_per_block[b] <= col < ctk.num_vars
+    a, bb, c = ctk.args[b][1]
+    ctk.args[b][1] = (a + [(col, circ.scalar_to_bytes(5))], bb, c)
+    args = [[tuple([(k, circ.scalar_from_bytes(v)) for k, v in terms] for terms in row) for row in block]
+            for block in ctk.args]
+    prog.block_num_vars, prog.block_max_num_cons, prog.block_nnz, prog.block_inst = workload.gen_block_inst(
+        ctk.num_vars, args, ctk.num_inputs_unpadded, prog.block_num_phy_ops, prog.block_num_vir_ops)
+    return ctk, rtk, prog
+
+
+def test_program_rejects_column_beyond_block_width(oracle):
+    """a user row naming a column at or beyond num_vars_per_block[b]: the reference indexes a vector of that length
+    and panics. CircProgram raises, for a block that never runs too; the oracle, given the instance anyway, returns
+    its error code (it used to write past the block's evaluation table, sparse_mlpoly.rs:524-541's restatement)"""
+    import circ
+    import workload
+
+    for executed in (True, False):
+        ctk, rtk, prog = out_of_width_program(executed)
+        with pytest.raises(ValueError, match="beyond num_vars_per_block"):
+            circ.CircProgram(ctk, rtk)
+    ctk, rtk, prog = out_of_width_program()
+    with pytest.raises(AssertionError, match="-2"):
+        oracle.snark_prove(prog, workload.tape_seed())
+    ctk, rtk = circ.export_workload(workload.SnarkWorkload(**SNARK_CASES["mem_both_b3_x64_q2"]))
+    ctk.num_vars_per_block[1] = 16  # below the 10 io + 2 + 8 memory-operation variables
+    with pytest.raises(ValueError, match="io and memory"):
+        circ.CircProgram(ctk, rtk)

@@ -480,6 +480,27 @@ def test_multiply_vec_block_matches_oracle(ctx, oracle, case):
 
 
 @pytest.mark.gpu
+@pytest.mark.parametrize("case", ["ragged_p2_x64", "tiled_p2_x256"])
+def test_multiply_vec_block_on_structured_matrices(ctx, oracle, case):
+    """rows of hundreds of entries, duplicate (row, col) entries, an empty matrix and shuffled entry lists
+    (tests/sparse_cases.py): ragged instances over three sections, and 256-row instances in the tiled form"""
+    import sparse_cases
+    import spg
+    import workload
+
+    wl = sparse_cases.structured(case)
+    z = np.concatenate([np.stack([wl.sections[w][p][q] for w in range(wl.nws)]).reshape(-1, 4)
+                        for p in range(wl.P) for q in range(wl.num_proofs[p])])
+    inst = spg.R1CSInst(ctx, workload.CViews(wl).inst)
+    got = spg.r1cs_multiply_vec_block(ctx, inst, wl.num_proofs, wl.max_num_proofs, wl.num_inputs, wl.max_num_inputs,
+                                      wl.nws, z)
+    want = oracle.r1cs_multiply_vec_block(wl, z, wl.num_inputs)
+    assert any(W.any() for W in want)
+    for T, W in zip(got, want):
+        assert np.array_equal(T.download(), W)
+
+
+@pytest.mark.gpu
 def test_multiply_vec_block_rejects_bad_shapes(ctx, oracle):
     import spg
     import workload

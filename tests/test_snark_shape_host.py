@@ -147,6 +147,42 @@ def test_snark_shape_orders_by_case():
     assert pw["phy_and_vir_all_equal_sizes"] == [3, 0, 1, 2]
 
 
+def width_violation(hc, prog):
+    """block_width_violation on the C views spg_snark_encode / spg_snark_witness_new are given"""
+    import workload
+
+    v = workload.SnarkViews(prog)
+    a, ci = v.inputs, v.block.inst
+    hc.spgh_block_width_violation.restype = ctypes.c_long
+    return hc.spgh_block_width_violation(
+        ctypes.c_size_t(a.block_num_instances_bound), a.block_num_proofs, a.block_num_vars, a.block_num_phy_ops,
+        a.block_num_vir_ops, ctypes.c_size_t(a.num_inputs_unpadded), ctypes.c_size_t(a.num_vars), ci.entries, ci.nnz)
+
+
+def test_block_width_check(hc):
+    """what spg_snark_prove refuses with SPG_E_ARG before any launch: an executed block whose matrices name a column
+    at or beyond its block_num_vars, or whose rows are too short for its io and memory-operation variables (the
+    host's w2 recurrences would read past them). Honest programs pass, and a block that never runs is not read."""
+    import hetero_program
+    import workload
+    from r1cs_cases import SNARK_CASES
+    from test_circ import out_of_width_program
+
+    for case in hetero_program.CASES:
+        assert width_violation(hc, hetero_program.program(case)) == -1
+    for case in ("widths_b3_x64", "mem_uneven_b3_x64", "uneven_b3_x32"):
+        assert width_violation(hc, workload.SnarkWorkload(**SNARK_CASES[case])) == -1
+    assert width_violation(hc, out_of_width_program(executed=True)[2]) == 1
+    assert width_violation(hc, out_of_width_program(executed=False)[2]) == -1
+    prog = hetero_program.program("hetero_mem_b3")
+    prog._num_vars_per_block = [32, 64, 32]  # block 2: 10 io + 2 + 16 memory-operation variables, then the chain
+    assert width_violation(hc, prog) == 2
+    prog._num_vars_per_block = [32, 64, 16]
+    assert width_violation(hc, prog) == 2
+    prog._num_vars_per_block = [32, 128, 64]  # wider than num_vars, the section stride of the matrices
+    assert width_violation(hc, prog) == 1
+
+
 def test_snark_shape_random(hc):
     rng = np.random.default_rng(11)
     for _ in range(200):
