@@ -349,6 +349,71 @@ int spg_random_tape_new(const char* name, const uint64_t* init_mont, spg_random_
 int spg_random_tape_scalar(spg_random_tape* tp, const char* label, uint64_t* out_mont);
 int spg_random_tape_free(spg_random_tape* tp);
 
+/* ---- Hyrax dense polynomial commitments and evaluation proofs on device vectors (csrc/polyeval.hip) ----------
+ * PolyCommitmentGens, DensePolynomial::commit and PolyEvalProof (src/dense_mlpoly.rs:31-38, 184-256, 437-857) one call
+ * at a time, over polynomials resident in HBM (spg_buf). Proof bytes are the reference's bincode. A prove whose output
+ * does not fit `cap` still sets *len (a function of the shapes alone), returns SPG_E_ARG and leaves transcript and tape
+ * untouched. SPG_E_ARG before anything is launched or appended: num_vars outside 1 .. 30, 2^(num_vars - num_vars/2)
+ * beyond the handle's n, offset + 2^num_vars past spg_buf_len, K = 0 or n = 0, a null pointer (except the optional
+ * blinds / blind_Zr / C_Zr of the provers). The verifiers return 0 or SPG_E_VERIFY (spg_last_error names the check);
+ * malformed or truncated proof bytes, a wrong proof count, a commitment of the wrong row count and a commitment point
+ * that does not decompress are all SPG_E_VERIFY, as in spg_snark_verify. Single-rank, like the spg_prodc_* seams:
+ * spg_set_comm does not shard these. */
+typedef struct spg_poly_gens spg_poly_gens;
+/* PolyCommitmentGens::new(num_vars, label) (:31-38) = DotProductProofGens::new(n = 2^(num_vars - num_vars/2), label):
+ * the first n + 2 points of label's stream; gens_n = G_0 .. G_{n-1} with h = point n + 1, gens_1 = G_n with the same h */
+int spg_poly_gens_new(spg_ctx* ctx, const uint8_t* label, size_t label_len, size_t num_vars, spg_poly_gens** out);
+size_t spg_poly_gens_n(const spg_poly_gens* g);
+/* (n + 2) x 32 bytes: G_0 .. G_n, h */
+int spg_poly_gens_download(spg_ctx* ctx, const spg_poly_gens* g, uint8_t* out);
+int spg_poly_gens_free(spg_ctx* ctx, spg_poly_gens* g);
+/* DensePolynomial::commit / commit_with_blind (:184-256) of Z[offset .. offset + 2^num_vars): L = 2^(num_vars/2) rows of
+ * 2^(num_vars - num_vars/2) scalars into comm (32 bytes each; comm_cap bytes; *L_out = L also when they do not fit);
+ * blinds_mont: L scalars, or NULL for zeros */
+int spg_poly_commit(spg_ctx* ctx, const spg_poly_gens* g, const spg_buf* Z, size_t offset, size_t num_vars,
+                    const uint64_t* blinds_mont, uint8_t* comm, size_t comm_cap, size_t* L_out);
+/* PolyEvalProof::prove (:437-490) at the point r (num_vars scalars) with the claimed value Zr. blinds_mont (L scalars,
+ * the commitment's) and blind_Zr_mont may be NULL (zeros). proof = bincode(PolyEvalProof); C_Zr (optional) receives
+ * C_Zr_prime, the commitment to Zr under blind_Zr */
+int spg_poly_eval_prove(spg_ctx* ctx, const spg_poly_gens* g, const spg_buf* Z, size_t offset, const uint64_t* r_mont,
+                        size_t num_vars, const uint64_t* Zr_mont, const uint64_t* blinds_mont,
+                        const uint64_t* blind_Zr_mont, spg_transcript* t, spg_random_tape* tape, uint8_t* proof,
+                        size_t cap, size_t* len, uint8_t C_Zr[32]);
+/* PolyEvalProof::verify (:492-514) and verify_plain (:516-528); comm = L x 32 bytes */
+int spg_poly_eval_verify(spg_ctx* ctx, const spg_poly_gens* g, const uint64_t* r_mont, size_t num_vars,
+                         const uint8_t C_Zr[32], const uint8_t* comm, size_t L, spg_transcript* t, const uint8_t* proof,
+                         size_t proof_len);
+int spg_poly_eval_verify_plain(spg_ctx* ctx, const spg_poly_gens* g, const uint64_t* r_mont, size_t num_vars,
+                               const uint64_t* Zr_mont, const uint8_t* comm, size_t L, spg_transcript* t,
+                               const uint8_t* proof, size_t proof_len);
+/* prove_batched_points (:531-622): K points (K x num_vars scalars, row-major) on one polynomial, no blinds. proof =
+ * bincode(Vec<PolyEvalProof>): one proof per distinct left half of r (its first num_vars/2 scalars), in first-seen
+ * order. The L.Z vectors of all distinct left halves come from one launch pair and one download. */
+int spg_poly_eval_prove_batched_points(spg_ctx* ctx, const spg_poly_gens* g, const spg_buf* Z, size_t offset,
+                                       size_t num_vars, const uint64_t* r_list_mont, size_t K,
+                                       const uint64_t* Zr_list_mont, spg_transcript* t, spg_random_tape* tape,
+                                       uint8_t* proof, size_t cap, size_t* len);
+/* verify_plain_batched_points (:624-685) */
+int spg_poly_eval_verify_plain_batched_points(spg_ctx* ctx, const spg_poly_gens* g, size_t num_vars,
+                                              const uint64_t* r_list_mont, size_t K, const uint64_t* Zr_list_mont,
+                                              const uint8_t* comm, size_t L, spg_transcript* t, const uint8_t* proof,
+                                              size_t proof_len);
+/* prove_batched_instances (:689-780): n polynomials polys[i][offsets[i] .. + 2^num_vars_list[i]), each with its own
+ * point of r_lens[i] scalars (concatenated in r_list_mont). As the reference: a point shorter than num_vars_list[i] is
+ * padded with zeros at the FRONT, a longer one keeps its LAST num_vars_list[i] entries. One proof per distinct
+ * (num_vars, R vector) in first-seen order; no blinds. The polynomial count is limited by memory alone. */
+int spg_poly_eval_prove_batched_instances(spg_ctx* ctx, const spg_poly_gens* g, const spg_buf* const* polys,
+                                          const size_t* offsets, const size_t* num_vars_list, size_t n,
+                                          const uint64_t* r_list_mont, const size_t* r_lens,
+                                          const uint64_t* Zr_list_mont, spg_transcript* t, spg_random_tape* tape,
+                                          uint8_t* proof, size_t cap, size_t* len);
+/* verify_plain_batched_instances (:782-857): comms = every polynomial's rows concatenated, comm_lens[i] rows each */
+int spg_poly_eval_verify_plain_batched_instances(spg_ctx* ctx, const spg_poly_gens* g, const uint64_t* r_list_mont,
+                                                 const size_t* r_lens, const uint64_t* Zr_list_mont,
+                                                 const uint8_t* comms, const size_t* comm_lens,
+                                                 const size_t* num_vars_list, size_t n, spg_transcript* t,
+                                                 const uint8_t* proof, size_t proof_len);
+
 /* ---- R1CSProof::prove (src/r1csproof.rs:210-685) ----------------------------------------------
  * R1CSGens::new(label, _, num_vars) (src/r1csproof.rs:71-79): gens_pc = PolyCommitmentGens for
  * log2(num_vars) variables; gens_1 = gens_pc.gens_1, gens_4 = MultiCommitGens::new(4, label). All of

@@ -16,6 +16,7 @@
 #include "hostmath.hpp"
 #include "hpool.hpp"
 #include "keccak.hpp"
+#include "pe_plan.hpp"
 #include "snark_shape.hpp"
 #include "vmsm.hpp"
 
@@ -406,6 +407,37 @@ long spgh_block_width_violation(size_t Bb, const size_t* nproofs, const size_t* 
   if (!stride) return 0;
   const std::vector<size_t> need = block_cols_needed(Bb, stride, entries, nnz);
   return block_width_violation(Bb, nproofs, nvars, phy_ops, vir_ops, niu, stride, need.data());
+}
+// PePlan (pe_plan.hpp), the grouping and slab plan the spg_poly_eval_*_batched_* entries prove and verify by.
+// instances = 0: the points form, n points of nv_list[0] scalars each in r_list (r_lens unused); else the instances
+// form, polynomial i of nv_list[i] variables with a point of r_lens[i] scalars. Per term: term[6 i ..] = (group,
+// coefficient exponent, bound, S, chunk, first slab); fitted (optional) receives its fitted point, nv_i scalars each,
+// concatenated. Per group: grp[7 g ..] = (num_vars, Ls, Rs, first term, S, part_off, out_off). tot (optional) =
+// (part_len, out_len, xblocks, proof list bytes). Returns the number of groups.
+long spgh_pe_plan(int instances, size_t n, const size_t* nv_list, const uint64_t* r_list, const size_t* r_lens,
+                  size_t* term, uint64_t* fitted, size_t* grp, size_t* tot) {
+  size_t tot_r = 0;
+  for (size_t i = 0; i < n; i++) tot_r += instances ? r_lens[i] : nv_list[0];
+  std::vector<Fq> r(tot_r);
+  for (size_t i = 0; i < tot_r; i++) r[i] = ldq(r_list + 4 * i);
+  const PePlan p = instances ? pe_plan_instances(nv_list, r.data(), r_lens, n) : pe_plan_points(r.data(), n, nv_list[0]);
+  size_t fo = 0;
+  for (size_t i = 0; i < n; i++) {
+    const PeTerm& t = p.terms[i];
+    const size_t row[6] = {t.group, t.exp, t.bound ? (size_t)1 : 0, t.S, t.chunk, t.slab};
+    memcpy(term + 6 * i, row, sizeof(row));
+    for (size_t k = 0; fitted && k < t.r.size(); k++) stq(fitted + 4 * (fo + k), t.r[k]);
+    fo += t.r.size();
+  }
+  for (size_t k = 0; k < p.groups.size(); k++) {
+    const PeGroup& g = p.groups[k];
+    const size_t row[7] = {g.nv, g.Ls, g.Rs, g.first, g.S, g.part_off, g.out_off};
+    memcpy(grp + 7 * k, row, sizeof(row));
+  }
+  if (tot) {
+    tot[0] = p.part_len, tot[1] = p.out_len, tot[2] = p.xblocks, tot[3] = pe_list_bytes(p);
+  }
+  return (long)p.groups.size();
 }
 
 }  // extern "C"

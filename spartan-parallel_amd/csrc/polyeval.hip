@@ -1,0 +1,453 @@
+// spg — the Hyrax dense polynomial commitment scheme on device-resident vectors, one call at a time.
+//
+//   PolyCommitmentGens::new                        src/dense_mlpoly.rs:31-38    spg_poly_gens_new
+//   DensePolynomial::commit / commit_with_blind    :184-256                      spg_poly_commit
+//   PolyEvalProof::prove / verify / verify_plain   :437-528                      spg_poly_eval_prove / _verify(_plain)
+//   prove_batched_points / verify_plain_..         :531-685                      spg_poly_eval_*_batched_points
+//   prove_batched_instances / verify_plain_..      :689-857                      spg_poly_eval_*_batched_instances
+//
+// The prover's O(2^num_vars) work is the bound L.Z of every polynomial of a call (DensePolynomial::bound, :258-265).
+// One launch pair computes them all from the plan of pe_plan.hpp:
+//   k_pe_part   out of job (Z, L'_0 .. L'_{kt-1}): part_k[y][col] = sum_{j in row range y} L'_k[j] Z[j Rs + col]
+//   k_pe_sum    out_g[col] = sum of the S_g slabs of group g (the slabs of a group's terms are contiguous)
+// L'_i = c_i L_i is the eq table already scaled by the term's batching coefficient, so the random linear combination
+// sum_k c^k L_k.Z_k of the instances form comes out of the second launch; in the points form one read of Z can feed
+// up to kPeKTMax accumulators (the plan gives it kPeKT = 1: the measured tile did not pay, pe_plan.hpp). Job and
+// group descriptors live in device memory: a call's polynomial count is limited by memory alone. Fq sums are exact
+// and canonical, so the result does not depend on the summation order.
+// The Bullet reductions (dotproduct_log_prove) and the verifier's checks (verify.hip) are the whole-proof paths'.
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+
+#include "hostpoly.hpp"
+#include "pe_bound.hpp"
+#include "pe_plan.hpp"
+#include "pe_verify.hpp"
+#include "proto.hpp"
+
+struct spg_poly_gens {  // PolyCommitmentGens: gens_n = G_0 .. G_{n-1} with h, gens_1 = G_n with the same h
+  spg::ProverGens g;
+};
+
+namespace spg {
+
+constexpr size_t kWsPeJobs = 124, kWsPeSums = 125, kWsPeL = 126, kWsPePart = 127, kWsPeOut = 128, kWsPeBlinds = 129;
+
+// Every L.Z vector of a plan in one launch pair and one download. Z: the polynomial of every term (points form: of
+// term 0, shared by all). Lp: the scaled eq table of every bound term, in term order. out: plan.out_len scalars, group g
+// at its out_off.
+static int pe_bound(spg_ctx* ctx, const PePlan& plan, bool points, const std::vector<const Fq*>& Z,
+                    const std::vector<FqV>& Lp, FqV* out) {
+  std::vector<size_t> offL;  // per bound term, in term order
+  FqV Lall;
+  for (const FqV& l : Lp) {
+    offL.push_back(Lall.size());
+    Lall.insert(Lall.end(), l.begin(), l.end());
+  }
+  std::vector<PeJob> jobs;
+  uint32_t b0 = 0, Smax = 1;
+  double zbytes = 0;
+  auto close_job = [&](PeJob& j) {
+    j.b0 = b0;
+    b0 += (uint32_t)((j.Rs + 255) / 256);
+    Smax = std::max(Smax, j.S);
+    zbytes += 32.0 * (double)j.Ls * (double)j.Rs;
+    jobs.push_back(j);
+  };
+  size_t bi = 0;  // bound terms met so far
+  if (points) {
+    const size_t D = plan.groups.size();
+    for (size_t p0 = 0; p0 < D; p0 += kPeKT) {
+      PeJob j;
+      memset(&j, 0, sizeof(j));
+      const PeGroup& g0 = plan.groups[p0];
+      const PeTerm& t0 = plan.terms[g0.first];
+      j.Z = Z[0], j.Rs = g0.Rs, j.Ls = (uint32_t)g0.Ls, j.chunk = (uint32_t)t0.chunk, j.S = (uint32_t)t0.S;
+      j.kt = (uint32_t)std::min<size_t>(kPeKT, D - p0);
+      for (uint32_t k = 0; k < j.kt; k++) {  // group p0 + k is the (p0 + k)-th bound term
+        j.offL[k] = offL[p0 + k];
+        j.offP[k] = plan.groups[p0 + k].part_off;
+      }
+      close_job(j);
+    }
+  } else {
+    for (size_t i = 0; i < plan.terms.size(); i++) {
+      const PeTerm& t = plan.terms[i];
+      const PeGroup& g = plan.groups[t.group];
+      PeJob j;
+      memset(&j, 0, sizeof(j));
+      j.Z = Z[i], j.Rs = g.Rs, j.Ls = (uint32_t)g.Ls, j.chunk = (uint32_t)t.chunk, j.S = (uint32_t)t.S, j.kt = 1;
+      j.offL[0] = offL[bi++];
+      j.offP[0] = g.part_off + t.slab * g.Rs;
+      close_job(j);
+    }
+  }
+  std::vector<PeSum> sums;
+  uint32_t c0 = 0;
+  for (const PeGroup& g : plan.groups) {
+    sums.push_back(PeSum{g.part_off, g.out_off, g.Rs, (uint32_t)g.S, c0});
+    c0 += (uint32_t)((g.Rs + kPeSumCols - 1) / kPeSumCols);
+  }
+  if (b0 != plan.xblocks) return set_err(ctx, SPG_E_ARG, "poly eval: plan and jobs disagree");
+  PeJob* dj = (PeJob*)ws_get(ctx, kWsPeJobs, jobs.size() * sizeof(PeJob) + 64);
+  PeSum* ds = (PeSum*)ws_get(ctx, kWsPeSums, sums.size() * sizeof(PeSum) + 64);
+  Fq* dL = (Fq*)ws_get(ctx, kWsPeL, Lall.size() * sizeof(Fq) + 64);
+  Fq* dpart = (Fq*)ws_get(ctx, kWsPePart, plan.part_len * sizeof(Fq) + 64);
+  Fq* dout = (Fq*)ws_get(ctx, kWsPeOut, plan.out_len * sizeof(Fq) + 64);
+  if (!dj || !ds || !dL || !dpart || !dout) return set_err(ctx, SPG_E_NOMEM, "poly eval: bound workspace");
+  hipStream_t s = ctx->stream;
+  SPG_HIP(ctx, hipMemcpyAsync(dj, jobs.data(), jobs.size() * sizeof(PeJob), hipMemcpyHostToDevice, s));
+  SPG_HIP(ctx, hipMemcpyAsync(ds, sums.data(), sums.size() * sizeof(PeSum), hipMemcpyHostToDevice, s));
+  SPG_HIP(ctx, hipMemcpyAsync(dL, Lall.data(), Lall.size() * sizeof(Fq), hipMemcpyHostToDevice, s));
+  {
+    // Z once per job (the points form: once per kPeKT distinct L vectors), the partials written and read back
+    KScope ks(ctx, "pe_bound", zbytes + 64.0 * (double)plan.part_len);
+    hipLaunchKernelGGL(k_pe_part, dim3(b0, Smax), dim3(256), 0, s, dj, (uint32_t)jobs.size(), dL, dpart, plan.part_len);
+    hipLaunchKernelGGL(k_pe_sum, dim3(c0), dim3(256), 0, s, ds, (uint32_t)sums.size(), dpart, dout, plan.out_len);
+    if (hipGetLastError() != hipSuccess) return set_err(ctx, SPG_E_HIP, "poly eval: bound launch");
+  }
+  out->assign(plan.out_len, fq_zero());
+  return d2h_fq(ctx, dout, out->data(), plan.out_len);  // synchronises: the host vectors above outlive their copies
+}
+
+static FqV lds(const uint64_t* p, size_t n) {
+  FqV v(n);
+  for (size_t i = 0; i < n; i++) v[i] = ld_fq(p + 4 * i);
+  return v;
+}
+static bool nv_ok(size_t nv) { return nv >= 1 && nv <= kPeMaxVars; }
+static size_t rs_of(size_t nv) { return (size_t)1 << (nv - nv / 2); }
+static void eq_halves(const FqV& r, FqV* L, FqV* R) {
+  const size_t ln = r.size() / 2;
+  *L = eq_evals_host(FqV(r.begin(), r.begin() + ln));
+  *R = eq_evals_host(FqV(r.begin() + ln, r.end()));
+}
+static int put_bytes(spg_ctx* ctx, const Writer& w, uint8_t* proof, size_t cap, const char* what) {
+  if (w.out.size() > cap) return set_err(ctx, SPG_E_ARG, std::string(what) + ": proof size differs from its shapes'");
+  memcpy(proof, w.out.data(), w.out.size());
+  return SPG_OK;
+}
+
+static int commit_impl(spg_ctx* ctx, const spg_poly_gens* pg, const spg_buf* Z, size_t offset, size_t nv,
+                       const uint64_t* blinds, uint8_t* comm, size_t comm_cap, size_t* L_out) {
+  if (!ctx || !pg || !Z || !comm || !L_out) return SPG_E_ARG;
+  if (!nv_ok(nv)) return set_err(ctx, SPG_E_ARG, "poly commit: num_vars must be 1 .. 30");
+  const size_t L = (size_t)1 << (nv / 2), R = rs_of(nv);
+  if (R > pg->g.n_pc) return set_err(ctx, SPG_E_ARG, "poly commit: polynomial wider than the generators");
+  if (offset > Z->n || ((size_t)1 << nv) > Z->n - offset) return set_err(ctx, SPG_E_ARG, "poly commit: Z too short");
+  *L_out = L;
+  if (32 * L > comm_cap) return set_err(ctx, SPG_E_ARG, "poly commit: output buffer too small");
+  SPG_HIP(ctx, hipSetDevice(ctx->device));
+  ProverGens& g = const_cast<ProverGens&>(pg->g);
+  if (!blinds) return commit_rows(ctx, g, Z->d + offset, R, L, reinterpret_cast<Pt*>(comm));
+  Fq* db = (Fq*)ws_get(ctx, kWsPeBlinds, L * sizeof(Fq) + 64);
+  if (!db) return set_err(ctx, SPG_E_NOMEM, "poly commit: blinds");
+  const FqV hb = lds(blinds, L);
+  SPG_HIP(ctx, hipMemcpyAsync(db, hb.data(), L * sizeof(Fq), hipMemcpyHostToDevice, ctx->stream));
+  return msm_rows_host_enc(ctx, g.dev, Z->d + offset, R, L, db, -1, comm);  // synchronous: hb outlives its copy
+}
+
+static int prove_impl(spg_ctx* ctx, const spg_poly_gens* pg, const spg_buf* Z, size_t offset, const uint64_t* r_mont,
+                      size_t nv, const uint64_t* Zr, const uint64_t* blinds, const uint64_t* blind_Zr,
+                      spg_transcript* tr, spg_random_tape* tape, uint8_t* proof, size_t cap, size_t* len,
+                      uint8_t* C_Zr) {
+  if (!ctx || !pg || !Z || !r_mont || !Zr || !tr || !tape || !proof || !len) return SPG_E_ARG;
+  if (!nv_ok(nv)) return set_err(ctx, SPG_E_ARG, "poly eval prove: num_vars must be 1 .. 30");
+  const size_t Ls = (size_t)1 << (nv / 2), Rs = rs_of(nv);
+  if (Rs > pg->g.n_pc) return set_err(ctx, SPG_E_ARG, "poly eval prove: polynomial wider than the generators");
+  if (offset > Z->n || ((size_t)1 << nv) > Z->n - offset) return set_err(ctx, SPG_E_ARG, "poly eval prove: Z too short");
+  *len = pe_proof_bytes(Rs);
+  if (*len > cap) return set_err(ctx, SPG_E_ARG, "poly eval prove: proof buffer too small");
+  SPG_HIP(ctx, hipSetDevice(ctx->device));
+  ProverGens& g = const_cast<ProverGens&>(pg->g);
+  Tr& t = tr->t;
+  t.protocol("polynomial evaluation proof");
+  const FqV r = lds(r_mont, nv);
+  const PePlan plan = pe_plan_instances(&nv, r.data(), &nv, 1);
+  FqV L, R, LZ;
+  eq_halves(r, &L, &R);
+  int rc = pe_bound(ctx, plan, false, {Z->d + offset}, {L}, &LZ);
+  if (rc) return rc;
+  Fq LZ_blind = fq_zero();
+  for (size_t i = 0; blinds && i < Ls; i++) LZ_blind = fq_add(LZ_blind, fq_mul(ld_fq(blinds + 4 * i), L[i]));
+  DotProductProofLogP p;
+  Pt cy;
+  rc = dotproduct_log_prove(ctx, g, t, tape->t, LZ, LZ_blind, R, ld_fq(Zr), blind_Zr ? ld_fq(blind_Zr) : fq_zero(), &p,
+                            &cy);
+  if (rc) return rc;
+  Writer w;
+  p.ser(w);
+  if (C_Zr) memcpy(C_Zr, cy.b, 32);
+  return put_bytes(ctx, w, proof, cap, "poly eval prove");
+}
+
+// the proofs of a plan's groups, in order, after their bounds: bincode(Vec<PolyEvalProof>)
+static int prove_groups(spg_ctx* ctx, ProverGens& g, const PePlan& plan, const FqV& LZ, const std::vector<FqV>& Rg,
+                        const FqV& Zc, Tr& t, Tape& tape, Writer& w) {
+  w.u64(plan.groups.size());
+  for (size_t k = 0; k < plan.groups.size(); k++) {
+    const PeGroup& gr = plan.groups[k];
+    const FqV x(LZ.begin() + gr.out_off, LZ.begin() + gr.out_off + gr.Rs);
+    DotProductProofLogP p;
+    Pt cy;
+    const int rc = dotproduct_log_prove(ctx, g, t, tape, x, fq_zero(), Rg[k], Zc[k], fq_zero(), &p, &cy);
+    if (rc) return rc;
+    p.ser(w);
+  }
+  return 0;
+}
+// c_base^e for e = 0 .. the plan's largest exponent
+static FqV coeff_powers(const PePlan& plan, const Fq& c_base) {
+  size_t E = 0;
+  for (const PeTerm& t : plan.terms) E = std::max(E, t.exp);
+  FqV c(E + 1, fq_one());
+  for (size_t e = 1; e <= E; e++) c[e] = fq_mul(c[e - 1], c_base);
+  return c;
+}
+
+static int prove_points_impl(spg_ctx* ctx, const spg_poly_gens* pg, const spg_buf* Z, size_t offset, size_t nv,
+                             const uint64_t* r_list, size_t K, const uint64_t* Zr_list, spg_transcript* tr,
+                             spg_random_tape* tape, uint8_t* proof, size_t cap, size_t* len) {
+  if (!ctx || !pg || !Z || !r_list || !Zr_list || !tr || !tape || !proof || !len || K == 0) return SPG_E_ARG;
+  if (!nv_ok(nv)) return set_err(ctx, SPG_E_ARG, "poly eval prove (points): num_vars must be 1 .. 30");
+  if (rs_of(nv) > pg->g.n_pc) return set_err(ctx, SPG_E_ARG, "poly eval prove (points): polynomial wider than the generators");
+  if (offset > Z->n || ((size_t)1 << nv) > Z->n - offset)
+    return set_err(ctx, SPG_E_ARG, "poly eval prove (points): Z too short");
+  const FqV rs = lds(r_list, K * nv), Zr = lds(Zr_list, K);
+  const PePlan plan = pe_plan_points(rs.data(), K, nv);
+  *len = pe_list_bytes(plan);
+  if (*len > cap) return set_err(ctx, SPG_E_ARG, "poly eval prove (points): proof buffer too small");
+  SPG_HIP(ctx, hipSetDevice(ctx->device));
+  ProverGens& g = const_cast<ProverGens&>(pg->g);
+  Tr& t = tr->t;
+  t.protocol("polynomial evaluation proof");
+  const FqV c = coeff_powers(plan, t.challenge("challenge_c"));
+  const size_t D = plan.groups.size();
+  std::vector<FqV> Lp, Rg(D);
+  FqV Zc(D, fq_zero());
+  for (size_t i = 0; i < K; i++) {
+    const PeTerm& tm = plan.terms[i];
+    FqV L, R;
+    eq_halves(tm.r, &L, &R);
+    if (tm.bound) {
+      Lp.push_back(L);
+      Rg[tm.group] = R;
+      Zc[tm.group] = Zr[i];
+    } else {  // R_idx += c R_i, Zc_idx += c Zr_i: Rs-sized host work
+      FqV& dst = Rg[tm.group];
+      for (size_t j = 0; j < R.size(); j++) dst[j] = fq_add(dst[j], fq_mul(c[tm.exp], R[j]));
+      Zc[tm.group] = fq_add(Zc[tm.group], fq_mul(c[tm.exp], Zr[i]));
+    }
+  }
+  FqV LZ;
+  int rc = pe_bound(ctx, plan, true, {Z->d + offset}, Lp, &LZ);
+  if (rc) return rc;
+  Writer w;
+  rc = prove_groups(ctx, g, plan, LZ, Rg, Zc, t, tape->t, w);
+  return rc ? rc : put_bytes(ctx, w, proof, cap, "poly eval prove (points)");
+}
+
+// the shapes of an instance list, checked before anything else reads them; *tot_r = scalars of r_list
+static int instances_args(spg_ctx* ctx, const spg_poly_gens* pg, const size_t* nv_list, const size_t* r_lens, size_t n,
+                          size_t* tot_r, const char* what) {
+  *tot_r = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (!nv_ok(nv_list[i])) return set_err(ctx, SPG_E_ARG, std::string(what) + ": num_vars must be 1 .. 30");
+    if (rs_of(nv_list[i]) > pg->g.n_pc)
+      return set_err(ctx, SPG_E_ARG, std::string(what) + ": polynomial wider than the generators");
+    *tot_r += r_lens[i];
+  }
+  return SPG_OK;
+}
+
+static int prove_instances_impl(spg_ctx* ctx, const spg_poly_gens* pg, const spg_buf* const* polys,
+                                const size_t* offsets, const size_t* nv_list, size_t n, const uint64_t* r_list,
+                                const size_t* r_lens, const uint64_t* Zr_list, spg_transcript* tr,
+                                spg_random_tape* tape, uint8_t* proof, size_t cap, size_t* len) {
+  if (!ctx || !pg || !polys || !offsets || !nv_list || !r_list || !r_lens || !Zr_list || !tr || !tape || !proof ||
+      !len || n == 0)
+    return SPG_E_ARG;
+  size_t tot_r = 0;
+  int rc = instances_args(ctx, pg, nv_list, r_lens, n, &tot_r, "poly eval prove (instances)");
+  if (rc) return rc;
+  for (size_t i = 0; i < n; i++) {
+    if (!polys[i]) return SPG_E_ARG;
+    if (offsets[i] > polys[i]->n || ((size_t)1 << nv_list[i]) > polys[i]->n - offsets[i])
+      return set_err(ctx, SPG_E_ARG, "poly eval prove (instances): Z too short");
+  }
+  const FqV rs = lds(r_list, tot_r), Zr = lds(Zr_list, n);
+  const PePlan plan = pe_plan_instances(nv_list, rs.data(), r_lens, n);
+  *len = pe_list_bytes(plan);
+  if (*len > cap) return set_err(ctx, SPG_E_ARG, "poly eval prove (instances): proof buffer too small");
+  SPG_HIP(ctx, hipSetDevice(ctx->device));
+  ProverGens& g = const_cast<ProverGens&>(pg->g);
+  Tr& t = tr->t;
+  t.protocol("polynomial evaluation proof");
+  const FqV c = coeff_powers(plan, t.challenge("challenge_c"));
+  const size_t D = plan.groups.size();
+  std::vector<FqV> Lp(n), Rg(D);
+  std::vector<const Fq*> Zs(n);
+  FqV Zc(D, fq_zero());
+  for (size_t i = 0; i < n; i++) {
+    const PeTerm& tm = plan.terms[i];
+    Zs[i] = polys[i]->d + offsets[i];
+    const size_t ln = tm.nv / 2;
+    Lp[i] = eq_evals_host(FqV(tm.r.begin(), tm.r.begin() + ln));
+    if (tm.exp) {  // L'_i = c L_i: the kernel's group sum is then LZ_idx += c LZ_i
+      for (Fq& x : Lp[i]) x = fq_mul(x, c[tm.exp]);
+      Zc[tm.group] = fq_add(Zc[tm.group], fq_mul(c[tm.exp], Zr[i]));
+    } else {
+      Rg[tm.group] = eq_evals_host(FqV(tm.r.begin() + ln, tm.r.end()));
+      Zc[tm.group] = Zr[i];
+    }
+  }
+  FqV LZ;
+  rc = pe_bound(ctx, plan, false, Zs, Lp, &LZ);
+  if (rc) return rc;
+  Writer w;
+  rc = prove_groups(ctx, g, plan, LZ, Rg, Zc, t, tape->t, w);
+  return rc ? rc : put_bytes(ctx, w, proof, cap, "poly eval prove (instances)");
+}
+
+static std::vector<Pt> ldpts(const uint8_t* p, size_t n) {
+  std::vector<Pt> v(n);
+  for (size_t i = 0; i < n; i++) memcpy(v[i].b, p + 32 * i, 32);
+  return v;
+}
+
+}  // namespace spg
+
+using namespace spg;
+
+extern "C" int spg_poly_gens_new(spg_ctx* ctx, const uint8_t* label, size_t label_len, size_t num_vars,
+                                 spg_poly_gens** out) {
+  if (!ctx || !label || !out) return SPG_E_ARG;
+  if (!nv_ok(num_vars)) return set_err(ctx, SPG_E_ARG, "poly gens: num_vars must be 1 .. 30");
+  const size_t n = rs_of(num_vars);
+  spg_gens* dev = nullptr;
+  const int rc = spg_gens_derive(ctx, label, label_len, n + 1, &dev);  // G_0 .. G_n, then h
+  if (rc) return rc;
+  spg_poly_gens* pg = new spg_poly_gens();
+  pg->g = gens_view(dev, num_vars);
+  for (size_t i : {n, n + 1}) pg->g.host.get(i);  // gens_1 and h: the host tables of every proof's Cy and beta
+  *out = pg;
+  return SPG_OK;
+}
+extern "C" size_t spg_poly_gens_n(const spg_poly_gens* g) { return g ? g->g.n_pc : 0; }
+extern "C" int spg_poly_gens_download(spg_ctx* ctx, const spg_poly_gens* g, uint8_t* out) {
+  if (!ctx || !g || !out) return SPG_E_ARG;
+  memcpy(out, g->g.dev->compressed, 32 * (g->g.n_pc + 2));
+  return SPG_OK;
+}
+extern "C" int spg_poly_gens_free(spg_ctx* ctx, spg_poly_gens* g) {
+  if (!g) return SPG_OK;
+  spg_gens_free(ctx, g->g.dev);
+  delete g;
+  return SPG_OK;
+}
+
+extern "C" int spg_poly_commit(spg_ctx* ctx, const spg_poly_gens* g, const spg_buf* Z, size_t offset, size_t num_vars,
+                               const uint64_t* blinds_mont, uint8_t* comm, size_t comm_cap, size_t* L_out) {
+  HostPin pin;
+  return commit_impl(ctx, g, Z, offset, num_vars, blinds_mont, comm, comm_cap, L_out);
+}
+
+extern "C" int spg_poly_eval_prove(spg_ctx* ctx, const spg_poly_gens* g, const spg_buf* Z, size_t offset,
+                                   const uint64_t* r_mont, size_t num_vars, const uint64_t* Zr_mont,
+                                   const uint64_t* blinds_mont, const uint64_t* blind_Zr_mont, spg_transcript* t,
+                                   spg_random_tape* tape, uint8_t* proof, size_t cap, size_t* len, uint8_t C_Zr[32]) {
+  if (!ctx || !t) return SPG_E_ARG;
+  HostPin pin;
+  return tr_status(ctx, t->t, prove_impl(ctx, g, Z, offset, r_mont, num_vars, Zr_mont, blinds_mont, blind_Zr_mont, t,
+                                         tape, proof, cap, len, C_Zr));
+}
+extern "C" int spg_poly_eval_prove_batched_points(spg_ctx* ctx, const spg_poly_gens* g, const spg_buf* Z, size_t offset,
+                                                  size_t num_vars, const uint64_t* r_list_mont, size_t K,
+                                                  const uint64_t* Zr_list_mont, spg_transcript* t,
+                                                  spg_random_tape* tape, uint8_t* proof, size_t cap, size_t* len) {
+  if (!ctx || !t) return SPG_E_ARG;
+  HostPin pin;
+  return tr_status(ctx, t->t, prove_points_impl(ctx, g, Z, offset, num_vars, r_list_mont, K, Zr_list_mont, t, tape,
+                                                proof, cap, len));
+}
+extern "C" int spg_poly_eval_prove_batched_instances(spg_ctx* ctx, const spg_poly_gens* g, const spg_buf* const* polys,
+                                                     const size_t* offsets, const size_t* num_vars_list, size_t n,
+                                                     const uint64_t* r_list_mont, const size_t* r_lens,
+                                                     const uint64_t* Zr_list_mont, spg_transcript* t,
+                                                     spg_random_tape* tape, uint8_t* proof, size_t cap, size_t* len) {
+  if (!ctx || !t) return SPG_E_ARG;
+  HostPin pin;
+  return tr_status(ctx, t->t, prove_instances_impl(ctx, g, polys, offsets, num_vars_list, n, r_list_mont, r_lens,
+                                                   Zr_list_mont, t, tape, proof, cap, len));
+}
+
+// ---- verifiers: the Verifier members of verify.hip behind pe_verify.hpp
+static int verify_one(spg_ctx* ctx, const spg_poly_gens* g, const uint64_t* r_mont, size_t nv, const uint8_t* C_Zr,
+                      const uint64_t* Zr, const uint8_t* comm, size_t L, spg_transcript* t, const uint8_t* proof,
+                      size_t proof_len) {
+  if (!g || !r_mont || (!C_Zr && !Zr) || !comm || !proof) return SPG_E_ARG;
+  if (!nv_ok(nv)) return set_err(ctx, SPG_E_ARG, "poly eval verify: num_vars must be 1 .. 30");
+  if (rs_of(nv) > g->g.n_pc) return set_err(ctx, SPG_E_ARG, "poly eval verify: polynomial wider than the generators");
+  SPG_HIP(ctx, hipSetDevice(ctx->device));
+  Pt cz;
+  if (C_Zr) memcpy(cz.b, C_Zr, 32);
+  const Fq zr = Zr ? ld_fq(Zr) : fq_zero();
+  return pe_verify_one(ctx, const_cast<ProverGens&>(g->g), t->t, lds(r_mont, nv), C_Zr ? &cz : nullptr,
+                       Zr ? &zr : nullptr, ldpts(comm, L), proof, proof_len);
+}
+extern "C" int spg_poly_eval_verify(spg_ctx* ctx, const spg_poly_gens* g, const uint64_t* r_mont, size_t num_vars,
+                                    const uint8_t C_Zr[32], const uint8_t* comm, size_t L, spg_transcript* t,
+                                    const uint8_t* proof, size_t proof_len) {
+  if (!ctx || !t || !C_Zr) return SPG_E_ARG;
+  HostPin pin;
+  return tr_status(ctx, t->t, verify_one(ctx, g, r_mont, num_vars, C_Zr, nullptr, comm, L, t, proof, proof_len));
+}
+extern "C" int spg_poly_eval_verify_plain(spg_ctx* ctx, const spg_poly_gens* g, const uint64_t* r_mont, size_t num_vars,
+                                          const uint64_t* Zr_mont, const uint8_t* comm, size_t L, spg_transcript* t,
+                                          const uint8_t* proof, size_t proof_len) {
+  if (!ctx || !t || !Zr_mont) return SPG_E_ARG;
+  HostPin pin;
+  return tr_status(ctx, t->t, verify_one(ctx, g, r_mont, num_vars, nullptr, Zr_mont, comm, L, t, proof, proof_len));
+}
+extern "C" int spg_poly_eval_verify_plain_batched_points(spg_ctx* ctx, const spg_poly_gens* g, size_t num_vars,
+                                                         const uint64_t* r_list_mont, size_t K,
+                                                         const uint64_t* Zr_list_mont, const uint8_t* comm, size_t L,
+                                                         spg_transcript* t, const uint8_t* proof, size_t proof_len) {
+  if (!ctx || !t || !g || !r_list_mont || !Zr_list_mont || !comm || !proof || K == 0) return SPG_E_ARG;
+  if (!nv_ok(num_vars)) return set_err(ctx, SPG_E_ARG, "poly eval verify (points): num_vars must be 1 .. 30");
+  if (rs_of(num_vars) > g->g.n_pc)
+    return set_err(ctx, SPG_E_ARG, "poly eval verify (points): polynomial wider than the generators");
+  SPG_HIP(ctx, hipSetDevice(ctx->device));
+  HostPin pin;
+  std::vector<FqV> rl(K);
+  for (size_t i = 0; i < K; i++) rl[i] = lds(r_list_mont + 4 * i * num_vars, num_vars);
+  return tr_status(ctx, t->t, pe_verify_points(ctx, const_cast<ProverGens&>(g->g), t->t, rl, lds(Zr_list_mont, K),
+                                               ldpts(comm, L), proof, proof_len));
+}
+extern "C" int spg_poly_eval_verify_plain_batched_instances(spg_ctx* ctx, const spg_poly_gens* g,
+                                                            const uint64_t* r_list_mont, const size_t* r_lens,
+                                                            const uint64_t* Zr_list_mont, const uint8_t* comms,
+                                                            const size_t* comm_lens, const size_t* num_vars_list,
+                                                            size_t n, spg_transcript* t, const uint8_t* proof,
+                                                            size_t proof_len) {
+  if (!ctx || !t || !g || !r_list_mont || !r_lens || !Zr_list_mont || !comms || !comm_lens || !num_vars_list ||
+      !proof || n == 0)
+    return SPG_E_ARG;
+  size_t tot_r = 0;
+  const int rc = instances_args(ctx, g, num_vars_list, r_lens, n, &tot_r, "poly eval verify (instances)");
+  if (rc) return rc;
+  SPG_HIP(ctx, hipSetDevice(ctx->device));
+  HostPin pin;
+  std::vector<FqV> rl(n);
+  std::vector<std::vector<Pt>> cl(n);
+  size_t ro = 0, co = 0;
+  for (size_t i = 0; i < n; ro += r_lens[i], co += comm_lens[i], i++) {
+    rl[i] = lds(r_list_mont + 4 * ro, r_lens[i]);
+    cl[i] = ldpts(comms + 32 * co, comm_lens[i]);
+  }
+  return tr_status(ctx, t->t,
+                   pe_verify_instances(ctx, const_cast<ProverGens&>(g->g), t->t, rl, lds(Zr_list_mont, n), cl,
+                                       std::vector<size_t>(num_vars_list, num_vars_list + n), proof, proof_len));
+}

@@ -1733,3 +1733,50 @@ extern "C" int spg_snark_verify_public(spg_ctx* ctx, const spg_snark_comp* block
                         spg_snark_verify_public_impl(ctx, block, pairwise, perm_root, pub, vars_gens, transcript, proof,
                                                      proof_len));
 }
+
+// ---- PolyEvalProof::verify* one call at a time (pe_verify.hpp; the spg_poly_eval_verify* entries of polyeval.hip): the
+// Verifier members above on proof bytes. Malformed bytes, a wrong proof count, a commitment of the wrong row count and
+// a point that does not decompress are all SPG_E_VERIFY, as in the whole-proof verifiers.
+namespace spg {
+template <class Run>
+static int pe_verify_run(spg_ctx* ctx, Tr& t, const char* what, bool parsed, const Run& run) {
+  if (!parsed) return set_err(ctx, SPG_E_VERIFY, std::string(what) + ": malformed proof bytes");
+  V v(ctx, t);
+  bool ok = false;
+  try {
+    ok = run(v);
+  } catch (const Fail& f) {
+    v.fail(f.what);
+  }
+  if (!ok) return set_err(ctx, SPG_E_VERIFY, std::string(what) + ": " + (v.failed ? v.failed : "rejected"));
+  return SPG_OK;
+}
+int pe_verify_one(spg_ctx* ctx, ProverGens& g, Tr& t, const FqV& r, const Pt* C_Zr, const Fq* Zr,
+                  const std::vector<Pt>& comm, const uint8_t* proof, size_t len) {
+  DotProductProofLogP p;
+  Rd rdr(proof, len);
+  rd(rdr, p);
+  return pe_verify_run(ctx, t, "poly eval verify", !rdr.bad && rdr.o == rdr.n, [&](V& v) {
+    return C_Zr ? v.pe_verify(g, p, r, dec(*C_Zr), comm) : v.pe_verify_plain(g, p, r, *Zr, comm);
+  });
+}
+int pe_verify_points(spg_ctx* ctx, ProverGens& g, Tr& t, const std::vector<FqV>& r_list, const FqV& Zr_list,
+                     const std::vector<Pt>& comm, const uint8_t* proof, size_t len) {
+  std::vector<DotProductProofLogP> ps;
+  Rd rdr(proof, len);
+  rd(rdr, ps);
+  return pe_verify_run(ctx, t, "poly eval verify (points)", !rdr.bad && rdr.o == rdr.n,
+                       [&](V& v) { return v.pe_plain_batched_points(g, ps, r_list, Zr_list, comm); });
+}
+int pe_verify_instances(spg_ctx* ctx, ProverGens& g, Tr& t, const std::vector<FqV>& r_list, const FqV& Zr_list,
+                        const std::vector<std::vector<Pt>>& comms, const std::vector<size_t>& nv_list,
+                        const uint8_t* proof, size_t len) {
+  std::vector<DotProductProofLogP> ps;
+  Rd rdr(proof, len);
+  rd(rdr, ps);
+  std::vector<const PolyComm*> cp;
+  for (const PolyComm& c : comms) cp.push_back(&c);
+  return pe_verify_run(ctx, t, "poly eval verify (instances)", !rdr.bad && rdr.o == rdr.n,
+                       [&](V& v) { return v.pe_plain_batched_instances(g, ps, r_list, Zr_list, cp, nv_list); });
+}
+}  // namespace spg

@@ -1171,6 +1171,7 @@ def snark_prove(ctx, block, pairwise, perm_root, witness, vars_gens, transcript,
 
 
 SPG_E_VERIFY = -6
+SPG_E_ARG = -1
 
 
 def snark_verify(ctx, block, pairwise, perm_root, inputs, vars_gens, transcript, proof):
@@ -1206,3 +1207,196 @@ def points_sum_compress(parts):
     rc = lib().spg_points_sum_compress(_p(buf), ctypes.c_size_t(len(parts)), _p(out))
     assert rc == 0, rc
     return out.tobytes()
+
+
+# ---- Hyrax dense polynomial commitments and evaluation proofs on device vectors (csrc/polyeval.hip)
+class PolyGens:
+    """PolyCommitmentGens::new(num_vars, label) (src/dense_mlpoly.rs:31-38), resident in HBM: n = 2^(num_vars -
+    num_vars/2) row generators G_0 .. G_{n-1}, G_n for evaluations, and h."""
+
+    def __init__(self, ctx, label, num_vars):
+        self.ctx = ctx
+        self._h = ctypes.c_void_p()
+        lb = np.frombuffer(bytes(label), dtype=np.uint8).copy()
+        ctx.check(lib().spg_poly_gens_new(ctx.handle, _p(lb), ctypes.c_size_t(len(label)), ctypes.c_size_t(num_vars),
+                                          ctypes.byref(self._h)), "spg_poly_gens_new")
+        lib().spg_poly_gens_n.restype = ctypes.c_size_t
+        lib().spg_poly_gens_n.argtypes = [ctypes.c_void_p]
+        self.n = int(lib().spg_poly_gens_n(self._h))
+
+    @property
+    def handle(self):
+        return self._h
+
+    def compressed(self):
+        """[n + 2, 32]: G_0 .. G_n, h"""
+        out = np.zeros((self.n + 2, 32), dtype=np.uint8)
+        self.ctx.check(lib().spg_poly_gens_download(self.ctx.handle, self._h, _p(out)), "spg_poly_gens_download")
+        return out
+
+    def free(self):
+        if self._h:
+            lib().spg_poly_gens_free(self.ctx.handle, self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def _opt(x):
+    return None if x is None else _scalars(x)
+
+
+def _optp(a):
+    return None if a is None else _p(a)
+
+
+def _bytes_arr(b):
+    return np.frombuffer(bytes(b), dtype=np.uint8).copy() if len(b) else np.zeros(1, np.uint8)
+
+
+def _prove_call(ctx, what, call, cap):
+    """the provers' output convention: with cap None the size is asked for first (a call whose output does not fit
+    sets *len, returns SPG_E_ARG and touches neither transcript nor tape). ctx.last_len keeps *len of the last call."""
+    n = ctypes.c_size_t(0)
+    if cap is None:
+        probe = np.zeros(1, dtype=np.uint8)
+        rc = call(_p(probe), ctypes.c_size_t(0), ctypes.byref(n))
+        ctx.last_len = int(n.value)
+        if rc != SPG_E_ARG or n.value == 0:
+            ctx.check(rc, what)
+            raise SpgError(f"{what}: no proof size")
+        cap = int(n.value)
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    rc = call(_p(out), ctypes.c_size_t(cap), ctypes.byref(n))
+    ctx.last_len = int(n.value)
+    ctx.check(rc, what)
+    return out[:n.value].tobytes()
+
+
+def _verify_result(ctx, rc, what):
+    if rc == SPG_E_VERIFY:
+        return False, lib().spg_last_error(ctx.handle).decode(errors="replace")
+    ctx.check(rc, what)
+    return True, ""
+
+
+def poly_commit(ctx, gens, Z, num_vars, offset=0, blinds=None):
+    """DensePolynomial::commit / commit_with_blind (src/dense_mlpoly.rs:184-256) of Z[offset : offset + 2^num_vars] (a
+    Buf): [L, 32] row commitments, L = 2^(num_vars/2); blinds: L scalars or None (zeros)."""
+    rows = 1 << (max(int(num_vars), 0) // 2)
+    out = np.zeros((rows, 32), dtype=np.uint8)
+    b = _opt(blinds)
+    L = ctypes.c_size_t(0)
+    ctx.check(lib().spg_poly_commit(ctx.handle, gens.handle, Z.handle, ctypes.c_size_t(offset),
+                                    ctypes.c_size_t(num_vars), _optp(b), _p(out), ctypes.c_size_t(out.size),
+                                    ctypes.byref(L)), "spg_poly_commit")
+    return out[:L.value]
+
+
+def poly_eval_prove(ctx, gens, Z, r, Zr, transcript, tape, offset=0, blinds=None, blind_Zr=None, cap=None):
+    """PolyEvalProof::prove (src/dense_mlpoly.rs:437-490) of Z[offset : offset + 2^len(r)] at r with the claimed value
+    Zr. Returns (bincode(PolyEvalProof), C_Zr_prime)."""
+    rr, zr, b, bz = _scalars(r), _scalars(Zr), _opt(blinds), _opt(blind_Zr)
+    czr = np.zeros(32, dtype=np.uint8)
+
+    def call(out, c, n):
+        return lib().spg_poly_eval_prove(ctx.handle, gens.handle, Z.handle, ctypes.c_size_t(offset), _p(rr),
+                                         ctypes.c_size_t(rr.shape[0]), _p(zr), _optp(b), _optp(bz), transcript.handle,
+                                         tape.handle, out, c, n, _p(czr))
+
+    proof = _prove_call(ctx, "spg_poly_eval_prove", call, cap)
+    return proof, czr.tobytes()
+
+
+def poly_eval_verify(ctx, gens, r, C_Zr, comm, transcript, proof):
+    """PolyEvalProof::verify (src/dense_mlpoly.rs:492-514): comm [L, 32], C_Zr 32 bytes. Returns (ok, reason)."""
+    rr, cz, cm, pf = _scalars(r), _bytes_arr(C_Zr), np.ascontiguousarray(comm, dtype=np.uint8), _bytes_arr(proof)
+    rc = lib().spg_poly_eval_verify(ctx.handle, gens.handle, _p(rr), ctypes.c_size_t(rr.shape[0]), _p(cz), _p(cm),
+                                    ctypes.c_size_t(cm.size // 32), transcript.handle, _p(pf),
+                                    ctypes.c_size_t(len(proof)))
+    return _verify_result(ctx, rc, "spg_poly_eval_verify")
+
+
+def poly_eval_verify_plain(ctx, gens, r, Zr, comm, transcript, proof):
+    """PolyEvalProof::verify_plain (src/dense_mlpoly.rs:516-528). Returns (ok, reason)."""
+    rr, zr, cm, pf = _scalars(r), _scalars(Zr), np.ascontiguousarray(comm, dtype=np.uint8), _bytes_arr(proof)
+    rc = lib().spg_poly_eval_verify_plain(ctx.handle, gens.handle, _p(rr), ctypes.c_size_t(rr.shape[0]), _p(zr), _p(cm),
+                                          ctypes.c_size_t(cm.size // 32), transcript.handle, _p(pf),
+                                          ctypes.c_size_t(len(proof)))
+    return _verify_result(ctx, rc, "spg_poly_eval_verify_plain")
+
+
+def poly_eval_prove_batched_points(ctx, gens, Z, num_vars, r_list, Zr_list, transcript, tape, offset=0, cap=None):
+    """PolyEvalProof::prove_batched_points (src/dense_mlpoly.rs:531-622): r_list [K, num_vars, 4], Zr_list [K, 4] on
+    the polynomial Z[offset : offset + 2^num_vars]. Returns bincode(Vec<PolyEvalProof>)."""
+    zr = _scalars(Zr_list)
+    K = zr.shape[0]
+    rl = np.ascontiguousarray(r_list, dtype=np.uint64).reshape(K * num_vars, 4) if K * num_vars else np.zeros((1, 4), np.uint64)
+
+    def call(out, c, n):
+        return lib().spg_poly_eval_prove_batched_points(ctx.handle, gens.handle, Z.handle, ctypes.c_size_t(offset),
+                                                        ctypes.c_size_t(num_vars), _p(rl), ctypes.c_size_t(K), _p(zr),
+                                                        transcript.handle, tape.handle, out, c, n)
+
+    return _prove_call(ctx, "spg_poly_eval_prove_batched_points", call, cap)
+
+
+def poly_eval_verify_plain_batched_points(ctx, gens, num_vars, r_list, Zr_list, comm, transcript, proof):
+    """PolyEvalProof::verify_plain_batched_points (src/dense_mlpoly.rs:624-685). Returns (ok, reason)."""
+    zr = _scalars(Zr_list)
+    K = zr.shape[0]
+    rl = np.ascontiguousarray(r_list, dtype=np.uint64).reshape(K * num_vars, 4) if K * num_vars else np.zeros((1, 4), np.uint64)
+    cm, pf = np.ascontiguousarray(comm, dtype=np.uint8), _bytes_arr(proof)
+    rc = lib().spg_poly_eval_verify_plain_batched_points(ctx.handle, gens.handle, ctypes.c_size_t(num_vars), _p(rl),
+                                                         ctypes.c_size_t(K), _p(zr), _p(cm),
+                                                         ctypes.c_size_t(cm.size // 32), transcript.handle, _p(pf),
+                                                         ctypes.c_size_t(len(proof)))
+    return _verify_result(ctx, rc, "spg_poly_eval_verify_plain_batched_points")
+
+
+def _cat_points(r_list):
+    lens = [len(r) for r in r_list]
+    flat = [_scalars(r) for r in r_list if len(r)]
+    rl = np.ascontiguousarray(np.concatenate(flat)) if flat else np.zeros((1, 4), np.uint64)
+    return rl, (ctypes.c_size_t * max(len(lens), 1))(*lens)
+
+
+def poly_eval_prove_batched_instances(ctx, gens, polys, num_vars_list, r_list, Zr_list, transcript, tape, offsets=None,
+                                      cap=None):
+    """PolyEvalProof::prove_batched_instances (src/dense_mlpoly.rs:689-780): polynomial i is polys[i][offsets[i] :
+    offsets[i] + 2^num_vars_list[i]] (Bufs; several entries may name one Buf), r_list[i] its point ([len_i, 4], fitted
+    to num_vars_list[i] as the reference does), Zr_list [n, 4]. Returns bincode(Vec<PolyEvalProof>)."""
+    n = len(polys)
+    offs = (ctypes.c_size_t * max(n, 1))(*(offsets if offsets is not None else [0] * n))
+    nvs = (ctypes.c_size_t * max(n, 1))(*num_vars_list)
+    rl, lens = _cat_points(r_list)
+    zr = _scalars(Zr_list)
+    arr = _buf_array(polys)
+
+    def call(out, c, ln):
+        return lib().spg_poly_eval_prove_batched_instances(ctx.handle, gens.handle, arr, offs, nvs, ctypes.c_size_t(n),
+                                                           _p(rl), lens, _p(zr), transcript.handle, tape.handle, out, c,
+                                                           ln)
+
+    return _prove_call(ctx, "spg_poly_eval_prove_batched_instances", call, cap)
+
+
+def poly_eval_verify_plain_batched_instances(ctx, gens, r_list, Zr_list, comms, num_vars_list, transcript, proof):
+    """PolyEvalProof::verify_plain_batched_instances (src/dense_mlpoly.rs:782-857): comms[i] the [L_i, 32] rows of
+    polynomial i. Returns (ok, reason)."""
+    n = len(comms)
+    nvs = (ctypes.c_size_t * max(n, 1))(*num_vars_list)
+    rl, lens = _cat_points(r_list)
+    zr = _scalars(Zr_list)
+    cms = [np.ascontiguousarray(c, dtype=np.uint8).reshape(-1, 32) for c in comms]
+    cl = (ctypes.c_size_t * max(n, 1))(*[c.shape[0] for c in cms])
+    blob = np.ascontiguousarray(np.concatenate(cms)) if n else np.zeros((1, 32), np.uint8)
+    pf = _bytes_arr(proof)
+    rc = lib().spg_poly_eval_verify_plain_batched_instances(ctx.handle, gens.handle, _p(rl), lens, _p(zr), _p(blob), cl,
+                                                            nvs, ctypes.c_size_t(n), transcript.handle, _p(pf),
+                                                            ctypes.c_size_t(len(proof)))
+    return _verify_result(ctx, rc, "spg_poly_eval_verify_plain_batched_instances")
