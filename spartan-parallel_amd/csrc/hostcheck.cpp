@@ -439,6 +439,17 @@ long spgh_pe_plan(int instances, size_t n, const size_t* nv_list, const uint64_t
   }
   return (long)p.groups.size();
 }
+// The disjoint-rounds walk (pe_walk_disjoint, pe_plan.hpp) the R1CS witness opening proves and verifies by: term i has
+// the shape (num_proofs, num_inputs) = (shape[2 i], shape[2 i + 1]); group[i] and exp[i] receive its proof slot and
+// coefficient exponent. Returns the number of groups.
+long spgh_pe_walk_disjoint(size_t n, const size_t* shape, size_t* group, size_t* exp) {
+  std::vector<std::pair<size_t, size_t>> s(n);
+  for (size_t i = 0; i < n; i++) s[i] = {shape[2 * i], shape[2 * i + 1]};
+  const PeWalk w = pe_walk_disjoint(s);
+  std::copy(w.group.begin(), w.group.end(), group);
+  std::copy(w.exp.begin(), w.exp.end(), exp);
+  return (long)w.first.size();
+}
 
 }  // extern "C"
 

@@ -1,15 +1,23 @@
-// spg — the grouping plan of PolyEvalProof's batched openings (src/dense_mlpoly.rs:531-857), derived from the points
-// and sizes alone and written once. Host-only (no HIP types): polyeval.hip's provers and verifiers and
-// libspg_hostcheck.so (spgh_pe_plan, the tests' view of it) include it.
+// spg — the grouping rule of PolyEvalProof's batched openings (src/dense_mlpoly.rs:531-960), derived from the points
+// and sizes alone and written once. Host-only (no HIP types). Every prover and verifier of a batched form asks it
+// for the walk: polyeval.hip (the whole-proof provers prove_batched_points / prove_batched_instances and the
+// spg_poly_eval_* entries), r1cs.hip (Prover::polyeval_batched), verify.hip (V::pe_batched_disjoint,
+// V::pe_plain_batched_points, V::pe_plain_batched_instances), and libspg_hostcheck.so (spgh_pe_plan and
+// spgh_pe_walk_disjoint: the tests' view of it).
 //
-// Both batched forms walk their terms in order and keep a map from a key to a proof slot. A term whose key is new
+// Every batched form walks its terms in order and keeps a map from a key to a proof slot. A term whose key is new
 // opens a slot (coefficient 1); a term whose key repeats first advances the one running coefficient c <- c * c_base
 // and then joins its slot with that c. c advances on every repeat of any key, so the exponents of the repeats count
-// 1, 2, 3, .. in encounter order across all slots, not per slot.
+// 1, 2, 3, .. in encounter order across all slots, not per slot (pe_walk; the coefficients: pe_coeff_powers).
 //   points form    (prove_batched_points, :531-622):    key = the left half of r (the first num_vars / 2 entries)
 //   instances form (prove_batched_instances, :689-780): key = (num_vars, R vector) of the fitted point
+//   disjoint rounds (prove_batched_instances_disjoint_rounds, :861-960): key = (num_proofs, num_inputs)
 // The reference compares R vectors; eq tables of equal length are equal exactly when their points are (r_j is the sum
-// of the entries whose index has bit j set), so the plan compares the right halves of the fitted points instead.
+// of the entries whose index has bit j set), so the walk compares the right halves of the fitted points instead.
+// Points are compared by their bytes: an Fq is the unique canonical value in [0, q) (field.hpp; fq_eq is the same
+// limb comparison), which holds for transcript challenges, field results and the reduced scalars the C-ABI takes.
+// The univariate form (prove_uni_batched_instances, :1046-1130) has no grouping: c advances after every term. It
+// shares the power vectors below.
 //
 // The plan also lays out the device bound (polyeval.hip): every term that is bound owns S row ranges of `chunk` rows
 // ("slabs" of Rs partial sums each), and the slabs of one group's terms are contiguous, so the column-sum stage adds
@@ -18,6 +26,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "field.hpp"
@@ -56,9 +65,58 @@ struct PePlan {
   size_t xblocks = 0;                // column blocks of the partial stage over all its jobs
 };
 
+// ---- the walk
+struct PeWalk {
+  std::vector<size_t> group, exp;  // per term: its slot, and the e of its coefficient c_base^e (0 if it opened the slot)
+  std::vector<size_t> first;       // per slot, in first-seen order: the term that opened it
+  bool opens(size_t i) const { return first[group[i]] == i; }
+  size_t repeats() const { return group.size() - first.size(); }  // the largest exponent
+};
+// same(i, j): is term i's key equal to the key of term j (j < i, a term that opened a slot)
+template <class Same>
+inline PeWalk pe_walk(size_t n, const Same& same) {
+  PeWalk w;
+  size_t e = 0;
+  for (size_t i = 0; i < n; i++) {
+    size_t k = 0;
+    while (k < w.first.size() && !same(i, w.first[k])) k++;
+    const bool opens = k == w.first.size();
+    if (opens) w.first.push_back(i);
+    w.group.push_back(k);
+    w.exp.push_back(opens ? 0 : ++e);
+  }
+  return w;
+}
+inline bool pe_same(const Fq* a, const Fq* b, size_t n) { return n == 0 || memcmp(a, b, n * sizeof(Fq)) == 0; }
+// points form: points of one length
+inline PeWalk pe_walk_points(const std::vector<FqV>& r) {
+  const size_t ln = r.empty() ? 0 : r[0].size() / 2;
+  return pe_walk(r.size(), [&](size_t i, size_t j) { return pe_same(r[i].data(), r[j].data(), ln); });
+}
+// instances form: the fitted point of every polynomial (num_vars scalars each)
+inline PeWalk pe_walk_instances(const std::vector<FqV>& r) {
+  return pe_walk(r.size(), [&](size_t i, size_t j) {
+    const size_t nv = r[i].size(), ln = nv / 2;
+    return r[j].size() == nv && pe_same(r[i].data() + ln, r[j].data() + ln, nv - ln);
+  });
+}
+// disjoint rounds: (num_proofs, num_inputs) of every polynomial
+inline PeWalk pe_walk_disjoint(const std::vector<std::pair<size_t, size_t>>& shape) {
+  return pe_walk(shape.size(), [&](size_t i, size_t j) { return shape[i] == shape[j]; });
+}
+
+// (b^i)_i, i < n
+inline FqV pe_powers(const Fq& b, size_t n) {
+  FqV p(n, fq_one());
+  for (size_t i = 1; i < n; i++) p[i] = fq_mul(p[i - 1], b);
+  return p;
+}
+// c_base^e for e = 0 .. a walk's largest exponent
+inline FqV pe_coeff_powers(const Fq& c_base, size_t repeats) { return pe_powers(c_base, repeats + 1); }
+
 // a point shorter than nv is padded with zeros at the front, a longer one keeps its last nv entries (:712-722)
-inline std::vector<Fq> pe_fit(const Fq* r, size_t len, size_t nv) {
-  std::vector<Fq> v;
+inline FqV pe_fit(const Fq* r, size_t len, size_t nv) {
+  FqV v;
   if (nv >= len) {
     v.assign(nv - len, fq_zero());
     v.insert(v.end(), r, r + len);
@@ -67,7 +125,35 @@ inline std::vector<Fq> pe_fit(const Fq* r, size_t len, size_t nv) {
   }
   return v;
 }
-inline bool pe_same(const Fq* a, const Fq* b, size_t n) { return n == 0 || memcmp(a, b, n * sizeof(Fq)) == 0; }
+inline FqV pe_fit(const FqV& r, size_t nv) { return pe_fit(r.data(), r.size(), nv); }
+// the eq tables of both halves of a point: L over its first |r| / 2 scalars, R over the rest
+inline void pe_eq_halves(const FqV& r, FqV* L, FqV* R) {
+  const size_t ln = r.size() / 2;
+  *L = eq_evals_host(FqV(r.begin(), r.begin() + ln));
+  *R = eq_evals_host(FqV(r.begin() + ln, r.end()));
+}
+// the univariate form's vectors at r: L = (r^(Rs j))_j, j < Ls, of a polynomial of nv variables (one table per
+// distinct nv, `of` = each term's), and R = (r^i)_i, i < Rs, of the largest
+struct PeUniL {
+  std::vector<FqV> L;
+  std::vector<size_t> nv, of;
+};
+inline PeUniL pe_uni_Ls(const Fq& r, const std::vector<size_t>& nv_list) {
+  PeUniL u;
+  for (size_t nv : nv_list) {
+    size_t k = 0;
+    while (k < u.nv.size() && u.nv[k] != nv) k++;
+    if (k == u.nv.size()) {
+      Fq r_base = fq_one();
+      for (size_t e = 0; e < ((size_t)1 << (nv - nv / 2)); e++) r_base = fq_mul(r_base, r);
+      u.nv.push_back(nv);
+      u.L.push_back(pe_powers(r_base, (size_t)1 << (nv / 2)));
+    }
+    u.of.push_back(k);
+  }
+  return u;
+}
+inline FqV pe_uni_R(const Fq& r, size_t max_nv) { return pe_powers(r, (size_t)1 << (max_nv - max_nv / 2)); }
 
 // slabs: jobs of up to kt L vectors each (1 in the instances form) share the grid; a job of nbx column blocks gets
 // about kPeBlocks / xblocks row ranges, at most one per row
@@ -99,64 +185,35 @@ inline void pe_layout(PePlan* p, bool points, int kt = kPeKT) {
   }
 }
 
-// points form: K points of nv scalars each (row-major) on one polynomial
-inline PePlan pe_plan_points(const Fq* r_list, size_t K, size_t nv, int kt = kPeKT) {
+// the plan of a walk over the terms' (fitted) points: a term is bound if it opened its slot, or always (instances)
+inline PePlan pe_plan_of(const PeWalk& w, std::vector<FqV> r, bool points, int kt) {
   PePlan p;
-  const size_t ln = nv / 2;
-  size_t e = 0;
-  for (size_t i = 0; i < K; i++) {
+  for (size_t i = 0; i < r.size(); i++) {
     PeTerm t;
-    t.nv = nv;
-    t.r.assign(r_list + i * nv, r_list + (i + 1) * nv);
-    size_t idx = p.groups.size();
-    for (size_t k = 0; k < p.groups.size(); k++)
-      if (pe_same(p.terms[p.groups[k].first].r.data(), t.r.data(), ln)) {
-        idx = k;
-        break;
-      }
-    t.group = idx;
-    if (idx < p.groups.size()) {
-      t.exp = ++e;
-    } else {
-      PeGroup g;
-      g.nv = nv, g.Ls = (size_t)1 << ln, g.Rs = (size_t)1 << (nv - ln), g.first = i;
-      p.groups.push_back(g);
-      t.bound = true;
-    }
+    t.group = w.group[i], t.exp = w.exp[i], t.nv = r[i].size();
+    t.bound = !points || w.opens(i);
+    t.r = std::move(r[i]);
     p.terms.push_back(std::move(t));
   }
-  pe_layout(&p, true, kt);
+  for (size_t i : w.first) {
+    PeGroup g;
+    g.nv = p.terms[i].nv, g.Ls = (size_t)1 << (g.nv / 2), g.Rs = (size_t)1 << (g.nv - g.nv / 2), g.first = i;
+    p.groups.push_back(g);
+  }
+  pe_layout(&p, points, kt);
   return p;
 }
-
+// points form: K points of nv scalars each (row-major) on one polynomial
+inline PePlan pe_plan_points(const Fq* r_list, size_t K, size_t nv, int kt = kPeKT) {
+  std::vector<FqV> r(K);
+  for (size_t i = 0; i < K; i++) r[i].assign(r_list + i * nv, r_list + (i + 1) * nv);
+  return pe_plan_of(pe_walk_points(r), r, true, kt);
+}
 // instances form: n polynomials of nv_list[i] variables, point i of r_lens[i] scalars (concatenated in r_list)
 inline PePlan pe_plan_instances(const size_t* nv_list, const Fq* r_list, const size_t* r_lens, size_t n) {
-  PePlan p;
-  size_t e = 0, o = 0;
-  for (size_t i = 0; i < n; o += r_lens[i++]) {
-    PeTerm t;
-    t.nv = nv_list[i];
-    t.r = pe_fit(r_list + o, r_lens[i], t.nv);
-    t.bound = true;
-    const size_t ln = t.nv / 2, rn = t.nv - ln;
-    size_t idx = p.groups.size();
-    for (size_t k = 0; k < p.groups.size(); k++)
-      if (p.groups[k].nv == t.nv && pe_same(p.terms[p.groups[k].first].r.data() + ln, t.r.data() + ln, rn)) {
-        idx = k;
-        break;
-      }
-    t.group = idx;
-    if (idx < p.groups.size()) {
-      t.exp = ++e;
-    } else {
-      PeGroup g;
-      g.nv = t.nv, g.Ls = (size_t)1 << ln, g.Rs = (size_t)1 << rn, g.first = i;
-      p.groups.push_back(g);
-    }
-    p.terms.push_back(std::move(t));
-  }
-  pe_layout(&p, false);
-  return p;
+  std::vector<FqV> r(n);
+  for (size_t i = 0, o = 0; i < n; o += r_lens[i++]) r[i] = pe_fit(r_list + o, r_lens[i], nv_list[i]);
+  return pe_plan_of(pe_walk_instances(r), r, false, kPeKT);
 }
 
 // bincode(DotProductProofLog) of n = Rs scalars: two point vectors of lg Rs, delta, beta, z1, z2

@@ -16,6 +16,10 @@
 // group descriptors live in device memory: a call's polynomial count is limited by memory alone. Fq sums are exact
 // and canonical, so the result does not depend on the summation order.
 // The Bullet reductions (dotproduct_log_prove) and the verifier's checks (verify.hip) are the whole-proof paths'.
+//
+// SNARK::prove's PolyEvalProof provers on host polynomials live here too (pe_prove.hpp): prove_batched_points,
+// prove_batched_instances, uni_bounds / prove_uni_batched (:1046-1130). They bind on the host pool (host_bounds) and
+// take their slots and exponents from the same walk (pe_plan.hpp) as the entries above.
 #include <string.h>
 
 #include <algorithm>
@@ -24,6 +28,7 @@
 #include "hostpoly.hpp"
 #include "pe_bound.hpp"
 #include "pe_plan.hpp"
+#include "pe_prove.hpp"
 #include "pe_verify.hpp"
 #include "proto.hpp"
 
@@ -119,11 +124,6 @@ static FqV lds(const uint64_t* p, size_t n) {
 }
 static bool nv_ok(size_t nv) { return nv >= 1 && nv <= kPeMaxVars; }
 static size_t rs_of(size_t nv) { return (size_t)1 << (nv - nv / 2); }
-static void eq_halves(const FqV& r, FqV* L, FqV* R) {
-  const size_t ln = r.size() / 2;
-  *L = eq_evals_host(FqV(r.begin(), r.begin() + ln));
-  *R = eq_evals_host(FqV(r.begin() + ln, r.end()));
-}
 static int put_bytes(spg_ctx* ctx, const Writer& w, uint8_t* proof, size_t cap, const char* what) {
   if (w.out.size() > cap) return set_err(ctx, SPG_E_ARG, std::string(what) + ": proof size differs from its shapes'");
   memcpy(proof, w.out.data(), w.out.size());
@@ -167,7 +167,7 @@ static int prove_impl(spg_ctx* ctx, const spg_poly_gens* pg, const spg_buf* Z, s
   const FqV r = lds(r_mont, nv);
   const PePlan plan = pe_plan_instances(&nv, r.data(), &nv, 1);
   FqV L, R, LZ;
-  eq_halves(r, &L, &R);
+  pe_eq_halves(r, &L, &R);
   int rc = pe_bound(ctx, plan, false, {Z->d + offset}, {L}, &LZ);
   if (rc) return rc;
   Fq LZ_blind = fq_zero();
@@ -183,28 +183,25 @@ static int prove_impl(spg_ctx* ctx, const spg_poly_gens* pg, const spg_buf* Z, s
   return put_bytes(ctx, w, proof, cap, "poly eval prove");
 }
 
-// the proofs of a plan's groups, in order, after their bounds: bincode(Vec<PolyEvalProof>)
-static int prove_groups(spg_ctx* ctx, ProverGens& g, const PePlan& plan, const FqV& LZ, const std::vector<FqV>& Rg,
-                        const FqV& Zc, Tr& t, Tape& tape, Writer& w) {
-  w.u64(plan.groups.size());
-  for (size_t k = 0; k < plan.groups.size(); k++) {
-    const PeGroup& gr = plan.groups[k];
-    const FqV x(LZ.begin() + gr.out_off, LZ.begin() + gr.out_off + gr.Rs);
+// one DotProductProofLog per proof slot: bincode(Vec<PolyEvalProof>)
+static int prove_slots(spg_ctx* ctx, ProverGens& g, const std::vector<FqV>& LZs, const std::vector<FqV>& Rs,
+                       const FqV& Zc, Tr& t, Tape& tape, Writer& w) {
+  w.u64(LZs.size());
+  for (size_t k = 0; k < LZs.size(); k++) {
     DotProductProofLogP p;
     Pt cy;
-    const int rc = dotproduct_log_prove(ctx, g, t, tape, x, fq_zero(), Rg[k], Zc[k], fq_zero(), &p, &cy);
+    const int rc = dotproduct_log_prove(ctx, g, t, tape, LZs[k], fq_zero(), Rs[k], Zc[k], fq_zero(), &p, &cy);
     if (rc) return rc;
     p.ser(w);
   }
   return 0;
 }
-// c_base^e for e = 0 .. the plan's largest exponent
-static FqV coeff_powers(const PePlan& plan, const Fq& c_base) {
-  size_t E = 0;
-  for (const PeTerm& t : plan.terms) E = std::max(E, t.exp);
-  FqV c(E + 1, fq_one());
-  for (size_t e = 1; e <= E; e++) c[e] = fq_mul(c[e - 1], c_base);
-  return c;
+// the proofs of a plan's groups, in order, after their bounds
+static int prove_groups(spg_ctx* ctx, ProverGens& g, const PePlan& plan, const FqV& LZ, const std::vector<FqV>& Rg,
+                        const FqV& Zc, Tr& t, Tape& tape, Writer& w) {
+  std::vector<FqV> x;
+  for (const PeGroup& gr : plan.groups) x.emplace_back(LZ.begin() + gr.out_off, LZ.begin() + gr.out_off + gr.Rs);
+  return prove_slots(ctx, g, x, Rg, Zc, t, tape, w);
 }
 
 static int prove_points_impl(spg_ctx* ctx, const spg_poly_gens* pg, const spg_buf* Z, size_t offset, size_t nv,
@@ -223,14 +220,14 @@ static int prove_points_impl(spg_ctx* ctx, const spg_poly_gens* pg, const spg_bu
   ProverGens& g = const_cast<ProverGens&>(pg->g);
   Tr& t = tr->t;
   t.protocol("polynomial evaluation proof");
-  const FqV c = coeff_powers(plan, t.challenge("challenge_c"));
+  const FqV c = pe_coeff_powers(t.challenge("challenge_c"), plan.terms.size() - plan.groups.size());
   const size_t D = plan.groups.size();
   std::vector<FqV> Lp, Rg(D);
   FqV Zc(D, fq_zero());
   for (size_t i = 0; i < K; i++) {
     const PeTerm& tm = plan.terms[i];
     FqV L, R;
-    eq_halves(tm.r, &L, &R);
+    pe_eq_halves(tm.r, &L, &R);
     if (tm.bound) {
       Lp.push_back(L);
       Rg[tm.group] = R;
@@ -285,7 +282,7 @@ static int prove_instances_impl(spg_ctx* ctx, const spg_poly_gens* pg, const spg
   ProverGens& g = const_cast<ProverGens&>(pg->g);
   Tr& t = tr->t;
   t.protocol("polynomial evaluation proof");
-  const FqV c = coeff_powers(plan, t.challenge("challenge_c"));
+  const FqV c = pe_coeff_powers(t.challenge("challenge_c"), plan.terms.size() - plan.groups.size());
   const size_t D = plan.groups.size();
   std::vector<FqV> Lp(n), Rg(D);
   std::vector<const Fq*> Zs(n);
@@ -309,6 +306,132 @@ static int prove_instances_impl(spg_ctx* ctx, const spg_poly_gens* pg, const spg
   Writer w;
   rc = prove_groups(ctx, g, plan, LZ, Rg, Zc, t, tape->t, w);
   return rc ? rc : put_bytes(ctx, w, proof, cap, "poly eval prove (instances)");
+}
+
+// ---- the whole-proof provers of SNARK::prove, on host polynomials (pe_prove.hpp)
+// DensePolynomial::bound (dense_mlpoly.rs:258-265) of several host (Z, L) pairs in one pool burst: each job's columns
+// are cut into slices of >= ~2048 products, all slices of all jobs go to the pool together (one wake-up instead of
+// one per polynomial)
+static std::vector<FqV> host_bounds(const std::vector<std::pair<const FqV*, const FqV*>>& jobs) {
+  std::vector<FqV> out(jobs.size());
+  struct Slice {
+    size_t j, Ls, Rs, i0, i1;
+  };
+  std::vector<Slice> sl;
+  for (size_t j = 0; j < jobs.size(); j++) {
+    const size_t nv = lg2(jobs[j].first->size()), Ls = (size_t)1 << (nv / 2), Rs = (size_t)1 << (nv - nv / 2);
+    out[j].assign(Rs, fq_zero());
+    const size_t C = std::max<size_t>(1, std::min<size_t>({8, Rs, Ls * Rs / 2048}));
+    for (size_t c = 0; c < C; c++) sl.push_back({j, Ls, Rs, Rs * c / C, Rs * (c + 1) / C});
+  }
+  auto run = [&](int k) {
+    const Slice& s = sl[k];
+    const FqV& Z = *jobs[s.j].first;
+    const FqV& L = *jobs[s.j].second;
+    FqV& o = out[s.j];
+    for (size_t j = 0; j < s.Ls; j++)
+      for (size_t i = s.i0; i < s.i1; i++) o[i] = fq_add(o[i], fq_mul(L[j], Z[j * s.Rs + i]));
+  };
+  if (sl.size() == 1)
+    run(0);
+  else if (!sl.empty())
+    pool().parallel_for((int)sl.size(), run);
+  return out;
+}
+int prove_batched_points(spg_ctx* ctx, ProverGens& g, const FqV& Z, const std::vector<FqV>& r_list, const FqV& Zr,
+                         Tr& t, Tape& tape, Writer& w) {
+  t.protocol("polynomial evaluation proof");
+  const PeWalk wk = pe_walk_points(r_list);
+  const FqV c = pe_coeff_powers(t.challenge("challenge_c"), wk.repeats());
+  const size_t D = wk.first.size();
+  std::vector<FqV> Ls(D), Rs(D), Rv(r_list.size());
+  FqV Zc(D);
+  std::vector<Axpy> ax;  // Rs[k] += c R_i
+  for (size_t i = 0; i < r_list.size(); i++) {
+    const size_t k = wk.group[i];
+    FqV L;
+    pe_eq_halves(r_list[i], &L, &Rv[i]);
+    if (wk.opens(i)) {
+      Ls[k] = L, Rs[k] = Rv[i], Zc[k] = Zr[i];
+    } else {
+      ax.push_back({&Rs[k], c[wk.exp[i]], &Rv[i]});
+      Zc[k] = fq_add(Zc[k], fq_mul(c[wk.exp[i]], Zr[i]));
+    }
+  }
+  axpy_pool(ax);
+  // every distinct point's L.Z bound up front, in one pool burst
+  std::vector<std::pair<const FqV*, const FqV*>> bj;
+  for (const FqV& L : Ls) bj.push_back({&Z, &L});
+  return prove_slots(ctx, g, host_bounds(bj), Rs, Zc, t, tape, w);
+}
+
+int prove_batched_instances(spg_ctx* ctx, ProverGens& g, const std::vector<const FqV*>& polys,
+                            const std::vector<FqV>& r_list, const FqV& Zr, Tr& t, Tape& tape, Writer& w) {
+  t.protocol("polynomial evaluation proof");
+  const Fq c_base = t.challenge("challenge_c");
+  // every polynomial's eq factors, then all L.Z bounds in one pool burst
+  const size_t n = polys.size();
+  std::vector<FqV> r(n), Lv(n), Rv(n);
+  std::vector<std::pair<const FqV*, const FqV*>> bj;
+  for (size_t i = 0; i < n; i++) {
+    r[i] = pe_fit(r_list[i], lg2(polys[i]->size()));
+    pe_eq_halves(r[i], &Lv[i], &Rv[i]);
+    bj.push_back({polys[i], &Lv[i]});
+  }
+  std::vector<FqV> LZall = host_bounds(bj);
+  const PeWalk wk = pe_walk_instances(r);
+  const FqV c = pe_coeff_powers(c_base, wk.repeats());
+  const size_t D = wk.first.size();
+  std::vector<FqV> LZs(D), Rs(D);
+  FqV Zc(D);
+  std::vector<Axpy> ax;  // LZs[k] += c LZ_i
+  for (size_t i = 0; i < n; i++) {
+    const size_t k = wk.group[i];
+    if (wk.opens(i)) {
+      LZs[k] = LZall[i], Rs[k] = Rv[i], Zc[k] = Zr[i];
+    } else {
+      ax.push_back({&LZs[k], c[wk.exp[i]], &LZall[i]});
+      Zc[k] = fq_add(Zc[k], fq_mul(c[wk.exp[i]], Zr[i]));
+    }
+  }
+  axpy_pool(ax);
+  return prove_slots(ctx, g, LZs, Rs, Zc, t, tape, w);
+}
+
+static std::vector<size_t> nvs_of(const std::vector<const FqV*>& polys) {
+  std::vector<size_t> nv;
+  for (const FqV* p : polys) nv.push_back(lg2(p->size()));
+  return nv;
+}
+std::vector<FqV> uni_bounds(const std::vector<const FqV*>& polys, const Fq& r) {
+  const PeUniL u = pe_uni_Ls(r, nvs_of(polys));
+  std::vector<std::pair<const FqV*, const FqV*>> bj;
+  for (size_t i = 0; i < polys.size(); i++) bj.push_back({polys[i], &u.L[u.of[i]]});
+  return host_bounds(bj);
+}
+
+int prove_uni_batched(spg_ctx* ctx, ProverGens& g, const std::vector<const FqV*>& polys, const std::vector<FqV>& LZs,
+                      const Fq& r, const FqV& Zr, Tr& t, Tape& tape, Writer& w) {
+  t.protocol("polynomial evaluation proof");
+  size_t max_nv = 0;
+  for (size_t nv : nvs_of(polys)) max_nv = std::max(max_nv, nv);
+  const FqV R = pe_uni_R(r, max_nv);
+  Fq c_base = t.challenge("challenge_c"), c = fq_one();
+  FqV LZc(R.size(), fq_zero());
+  Fq Zrc = fq_zero();
+  std::vector<Axpy> ax;
+  for (size_t i = 0; i < polys.size(); i++) {  // no grouping in this form: c advances after every term
+    ax.push_back({&LZc, c, &LZs[i]});
+    Zrc = fq_add(Zrc, fq_mul(c, Zr[i]));
+    c = fq_mul(c, c_base);
+  }
+  axpy_pool(ax);
+  DotProductProofLogP p;
+  Pt cy;
+  int rc = dotproduct_log_prove(ctx, g, t, tape, LZc, fq_zero(), R, Zrc, fq_zero(), &p, &cy);
+  if (rc) return rc;
+  p.ser(w);
+  return 0;
 }
 
 static std::vector<Pt> ldpts(const uint8_t* p, size_t n) {

@@ -16,6 +16,7 @@
 
 #include "comm.hpp"
 #include "hostpoly.hpp"
+#include "pe_plan.hpp"
 #include "proto.hpp"
 #include "lds.hpp"
 #include "sumcheck.hpp"
@@ -1793,36 +1794,26 @@ int Prover::witness_evals(std::vector<PolyRef>& polys, std::vector<FqV>& eval_li
 // PolyEvalProof::prove_batched_instances_disjoint_rounds (dense_mlpoly.rs:861-960)
 int Prover::polyeval_batched(std::vector<PolyRef>& polys) {
   t.protocol("polynomial evaluation proof");
-  std::vector<std::pair<size_t, size_t>> keys;
-  std::vector<FqV> LZ_list, R_list;
-  FqV Zc;
-  Fq c_base = t.challenge("challenge_c");
-  Fq c = fq_one();
-  // the coefficients in the reference's order (c advances once per polynomial joining an earlier shape), then every
-  // LZ_list[idx] += c LZ over the pool (axpy_pool; config 4 adds 7 x 1024 products here, ~170 us on one thread)
-  std::vector<int> into(polys.size(), -1);
-  std::vector<Fq> coef(polys.size());
+  std::vector<std::pair<size_t, size_t>> shape;
+  for (const PolyRef& pr : polys) shape.push_back({pr.np, pr.ni});
+  const PeWalk wk = pe_walk_disjoint(shape);
+  const FqV c = pe_coeff_powers(t.challenge("challenge_c"), wk.repeats());
+  // the coefficients in the reference's order (the walk of pe_plan.hpp), then every LZ_list[k] += c LZ over the pool
+  // (axpy_pool; config 4 adds 7 x 1024 products here, ~170 us on one thread)
+  const size_t D = wk.first.size();
+  std::vector<FqV> LZ_list(D), R_list(D);
+  FqV Zc(D);
+  std::vector<Axpy> ax;
   for (size_t q = 0; q < polys.size(); q++) {
     const PolyRef& pr = polys[q];
-    std::pair<size_t, size_t> key = {pr.np, pr.ni};
-    size_t idx = keys.size();
-    for (size_t k = 0; k < keys.size(); k++)
-      if (keys[k] == key) { idx = k; break; }
-    if (idx < keys.size()) {
-      c = fq_mul(c, c_base);
-      into[q] = (int)idx;
-      coef[q] = c;
-      Zc[idx] = fq_add(Zc[idx], fq_mul(c, pr.ev));
+    const size_t k = wk.group[q];
+    if (wk.opens(q)) {
+      LZ_list[k] = pr.LZ, R_list[k] = pr.R, Zc[k] = pr.ev;
     } else {
-      keys.push_back(key);
-      Zc.push_back(pr.ev);
-      LZ_list.push_back(pr.LZ);
-      R_list.push_back(pr.R);
+      ax.push_back({&LZ_list[k], c[wk.exp[q]], &pr.LZ});
+      Zc[k] = fq_add(Zc[k], fq_mul(c[wk.exp[q]], pr.ev));
     }
   }
-  std::vector<Axpy> ax;  // (LZ_list no longer grows: its element addresses are stable)
-  for (size_t q = 0; q < polys.size(); q++)
-    if (into[q] >= 0) ax.push_back({&LZ_list[into[q]], coef[q], &polys[q].LZ});
   axpy_pool(ax);
   for (size_t k = 0; k < LZ_list.size(); k++) {
     DotProductProofLogP dp;

@@ -8,7 +8,7 @@
 //     permutation / memory witnesses w2, w3, w3_shifted    lib.rs:1299-1955, 831-968    (host, O(Q * 8))
 //     Hyrax commitments of every witness polynomial        lib.rs:1957-2221             commit_dev (device MSMs)
 //     three R1CSProof::prove + multi_evaluate + R1CSEvalProof                             r1cs.hip / spark.hip
-//     perm product, shift and IO PolyEvalProofs            lib.rs:2534-2693, 187-446    host bound + device Bullet
+//     perm product, shift and IO PolyEvalProofs            lib.rs:2534-2693, 187-446    polyeval.hip (pe_prove.hpp)
 // The host side is the transcript, the small witness recurrences and the bincode writer; every O(N) table
 // (block_vars, Az/Bz/Cz, SPARK dense representations) lives in HBM. SnarkProver::run calls one stage per section
 // of the reference; what the verifier derives from the same public sizes is in snark_shape.hpp.
@@ -18,6 +18,8 @@
 #include <algorithm>
 
 #include "hostpoly.hpp"
+#include "pe_plan.hpp"
+#include "pe_prove.hpp"
 #include "proto.hpp"
 #include "snark_shape.hpp"
 
@@ -40,39 +42,6 @@ Rows shift_rows(const Rows& m, size_t width) {
 FqV pad_pow2(FqV v) {  // DensePolynomial::new pads to a power of two (dense_mlpoly.rs:152-161)
   v.resize(npow2(std::max<size_t>(v.size(), 1)), fq_zero());
   return v;
-}
-// DensePolynomial::bound (dense_mlpoly.rs:258-265) of several host (Z, L) pairs in one pool burst: each job's columns are cut into slices of >= ~2048
-// products, all slices of all jobs go to the pool together (one wake-up instead of one per polynomial)
-std::vector<FqV> host_bounds(const std::vector<std::pair<const FqV*, const FqV*>>& jobs) {
-  std::vector<FqV> out(jobs.size());
-  struct Slice {
-    size_t j, Ls, Rs, i0, i1;
-  };
-  std::vector<Slice> sl;
-  for (size_t j = 0; j < jobs.size(); j++) {
-    const size_t nv = lg2(jobs[j].first->size()), Ls = (size_t)1 << (nv / 2), Rs = (size_t)1 << (nv - nv / 2);
-    out[j].assign(Rs, fq_zero());
-    const size_t C = std::max<size_t>(1, std::min<size_t>({8, Rs, Ls * Rs / 2048}));
-    for (size_t c = 0; c < C; c++) sl.push_back({j, Ls, Rs, Rs * c / C, Rs * (c + 1) / C});
-  }
-  auto run = [&](int k) {
-    const Slice& s = sl[k];
-    const FqV& Z = *jobs[s.j].first;
-    const FqV& L = *jobs[s.j].second;
-    FqV& o = out[s.j];
-    for (size_t j = 0; j < s.Ls; j++)
-      for (size_t i = s.i0; i < s.i1; i++) o[i] = fq_add(o[i], fq_mul(L[j], Z[j * s.Rs + i]));
-  };
-  if (sl.size() == 1)
-    run(0);
-  else if (!sl.empty())
-    pool().parallel_for((int)sl.size(), run);
-  return out;
-}
-void eq_factored(const FqV& r, FqV* L, FqV* R) {
-  const size_t ln = r.size() / 2;
-  *L = eq_evals_host(FqV(r.begin(), r.begin() + ln));
-  *R = eq_evals_host(FqV(r.begin() + ln, r.end()));
 }
 
 }  // namespace
@@ -215,183 +184,6 @@ void append_r1cs_comm(const spg_snark_comp* C, size_t g, Tr& t) {
   t.u64("num_cons", C->num_instances * C->max_num_cons);
   t.u64("num_vars", C->num_vars);
   spark_comm_append(C->sparks[g], t);
-}
-
-// PolyEvalProof::prove_batched_points (dense_mlpoly.rs:531-622) on a host polynomial
-int prove_batched_points(spg_ctx* ctx, ProverGens& g, const FqV& Z, const std::vector<FqV>& r_list, const FqV& Zr,
-                         Tr& t, Tape& tape, Writer& w) {
-  t.protocol("polynomial evaluation proof");
-  const size_t ln = r_list[0].size() / 2;
-  std::vector<FqV> keys, Ls, Rs;
-  FqV Zc;
-  Fq c_base = t.challenge("challenge_c"), c = fq_one();
-  std::vector<FqV> Rv(r_list.size());
-  std::vector<std::pair<size_t, Fq>> acc(r_list.size(), {SIZE_MAX, fq_zero()});  // Rs[idx] += c R_i (axpy_pool)
-  for (size_t i = 0; i < r_list.size(); i++) {
-    FqV L;
-    FqV& R = Rv[i];
-    eq_factored(r_list[i], &L, &R);
-    FqV key(r_list[i].begin(), r_list[i].begin() + ln);
-    size_t idx = keys.size();
-    for (size_t k = 0; k < keys.size(); k++)
-      if (keys[k].size() == key.size() && std::equal(keys[k].begin(), keys[k].end(), key.begin(),
-                                                     [](const Fq& a, const Fq& b) { return memcmp(&a, &b, 32) == 0; })) {
-        idx = k;
-        break;
-      }
-    if (idx < keys.size()) {
-      c = fq_mul(c, c_base);
-      acc[i] = {idx, c};
-      Zc[idx] = fq_add(Zc[idx], fq_mul(c, Zr[i]));
-    } else {
-      keys.push_back(key);
-      Ls.push_back(L);
-      Rs.push_back(R);
-      Zc.push_back(Zr[i]);
-    }
-  }
-  {
-    std::vector<Axpy> ax;
-    for (size_t i = 0; i < r_list.size(); i++)
-      if (acc[i].first != SIZE_MAX) ax.push_back({&Rs[acc[i].first], acc[i].second, &Rv[i]});
-    axpy_pool(ax);
-  }
-  w.u64(Ls.size());
-  // every distinct point's L.Z bound up front, in one pool burst
-  std::vector<std::pair<const FqV*, const FqV*>> bj;
-  for (size_t i = 0; i < Ls.size(); i++) bj.push_back({&Z, &Ls[i]});
-  std::vector<FqV> LZs = host_bounds(bj);
-  for (size_t i = 0; i < Ls.size(); i++) {
-    DotProductProofLogP p;
-    Pt cy;
-    int rc = dotproduct_log_prove(ctx, g, t, tape, LZs[i], fq_zero(), Rs[i], Zc[i], fq_zero(), &p, &cy);
-    if (rc) return rc;
-    p.ser(w);
-  }
-  return 0;
-}
-
-// PolyEvalProof::prove_batched_instances (dense_mlpoly.rs:689-780) on host polynomials
-int prove_batched_instances(spg_ctx* ctx, ProverGens& g, const std::vector<const FqV*>& polys,
-                            const std::vector<FqV>& r_list, const FqV& Zr, Tr& t, Tape& tape, Writer& w) {
-  t.protocol("polynomial evaluation proof");
-  std::vector<std::pair<size_t, FqV>> keys;
-  std::vector<FqV> LZs, Rs;
-  FqV Zc;
-  Fq c_base = t.challenge("challenge_c"), c = fq_one();
-  // every polynomial's eq factors, then all L.Z bounds in one pool burst
-  std::vector<FqV> Lv(polys.size()), Rv(polys.size());
-  std::vector<std::pair<const FqV*, const FqV*>> bj;
-  for (size_t i = 0; i < polys.size(); i++) {
-    const size_t nv = lg2(polys[i]->size());
-    FqV r = r_list[i];
-    if (nv >= r.size())
-      r.insert(r.begin(), nv - r.size(), fq_zero());
-    else
-      r = FqV(r.end() - nv, r.end());
-    eq_factored(r, &Lv[i], &Rv[i]);
-    bj.push_back({polys[i], &Lv[i]});
-  }
-  std::vector<FqV> LZall = host_bounds(bj);
-  std::vector<std::pair<size_t, Fq>> acc(polys.size(), {SIZE_MAX, fq_zero()});  // LZs[idx] += c LZ_i (axpy_pool)
-  for (size_t i = 0; i < polys.size(); i++) {
-    const size_t nv = lg2(polys[i]->size());
-    const FqV& R = Rv[i];
-    size_t idx = keys.size();
-    for (size_t k = 0; k < keys.size(); k++)
-      if (keys[k].first == nv && keys[k].second.size() == R.size() &&
-          memcmp(keys[k].second.data(), R.data(), R.size() * sizeof(Fq)) == 0) {
-        idx = k;
-        break;
-      }
-    FqV& LZ = LZall[i];
-    if (idx < keys.size()) {
-      c = fq_mul(c, c_base);
-      acc[i] = {idx, c};
-      Zc[idx] = fq_add(Zc[idx], fq_mul(c, Zr[i]));
-    } else {
-      keys.push_back({nv, R});
-      Zc.push_back(Zr[i]);
-      LZs.push_back(LZ);
-      Rs.push_back(R);
-    }
-  }
-  {
-    std::vector<Axpy> ax;
-    for (size_t i = 0; i < polys.size(); i++)
-      if (acc[i].first != SIZE_MAX) ax.push_back({&LZs[acc[i].first], acc[i].second, &LZall[i]});
-    axpy_pool(ax);
-  }
-  w.u64(LZs.size());
-  for (size_t i = 0; i < LZs.size(); i++) {
-    DotProductProofLogP p;
-    Pt cy;
-    int rc = dotproduct_log_prove(ctx, g, t, tape, LZs[i], fq_zero(), Rs[i], Zc[i], fq_zero(), &p, &cy);
-    if (rc) return rc;
-    p.ser(w);
-  }
-  return 0;
-}
-
-// The L.Z bounds of PolyEvalProof::prove_uni_batched_instances (dense_mlpoly.rs:1046-1130): L = (r^(Rs j))_j for
-// each polynomial size 2^nv, all bounds in one pool burst. The shift proof also reads its evaluations from them:
-// sum_k LZ[k] r^k = sum_i Z[i] r^i.
-std::vector<FqV> uni_bounds(const std::vector<const FqV*>& polys, const Fq& r) {
-  std::vector<size_t> nvs;
-  std::vector<FqV> Lv;
-  std::vector<size_t> li(polys.size());
-  for (size_t i = 0; i < polys.size(); i++) {
-    const size_t nv = lg2(polys[i]->size());
-    size_t k = 0;
-    while (k < nvs.size() && nvs[k] != nv) k++;
-    if (k == nvs.size()) {
-      Fq r_base = fq_one();
-      for (size_t e = 0; e < ((size_t)1 << (nv - nv / 2)); e++) r_base = fq_mul(r_base, r);
-      FqV L;
-      Fq lb = fq_one();
-      for (size_t e = 0; e < ((size_t)1 << (nv / 2)); e++) {
-        L.push_back(lb);
-        lb = fq_mul(lb, r_base);
-      }
-      nvs.push_back(nv);
-      Lv.push_back(L);
-    }
-    li[i] = k;
-  }
-  std::vector<std::pair<const FqV*, const FqV*>> bj;
-  for (size_t i = 0; i < polys.size(); i++) bj.push_back({polys[i], &Lv[li[i]]});
-  return host_bounds(bj);
-}
-
-// PolyEvalProof::prove_uni_batched_instances (dense_mlpoly.rs:1046-1130) from the bounds of uni_bounds(polys, r)
-int prove_uni_batched(spg_ctx* ctx, ProverGens& g, const std::vector<const FqV*>& polys, const std::vector<FqV>& LZs,
-                      const Fq& r, const FqV& Zr, Tr& t, Tape& tape, Writer& w) {
-  t.protocol("polynomial evaluation proof");
-  size_t max_nv = 0;
-  for (auto p : polys) max_nv = std::max(max_nv, lg2(p->size()));
-  const size_t R_size = (size_t)1 << (max_nv - max_nv / 2);
-  FqV R;
-  Fq rb = fq_one();
-  for (size_t i = 0; i < R_size; i++) {
-    R.push_back(rb);
-    rb = fq_mul(rb, r);
-  }
-  Fq c_base = t.challenge("challenge_c"), c = fq_one();
-  FqV LZc(R_size, fq_zero());
-  Fq Zrc = fq_zero();
-  std::vector<Axpy> ax;
-  for (size_t i = 0; i < polys.size(); i++) {
-    ax.push_back({&LZc, c, &LZs[i]});
-    Zrc = fq_add(Zrc, fq_mul(c, Zr[i]));
-    c = fq_mul(c, c_base);
-  }
-  axpy_pool(ax);
-  DotProductProofLogP p;
-  Pt cy;
-  int rc = dotproduct_log_prove(ctx, g, t, tape, LZc, fq_zero(), R, Zrc, fq_zero(), &p, &cy);
-  if (rc) return rc;
-  p.ser(w);
-  return 0;
 }
 
 int env_int(const char* name, int dflt) {
@@ -1344,12 +1136,7 @@ int SnarkProver::prove_shift() {
   const std::vector<FqV> LZs = uni_bounds(all, c);
   size_t rs_max = 0;
   for (auto& v : LZs) rs_max = std::max(rs_max, v.size());
-  FqV c_pow(rs_max);
-  Fq nc = fq_one();
-  for (size_t i = 0; i < rs_max; i++) {
-    c_pow[i] = nc;
-    nc = fq_mul(nc, c);
-  }
+  const FqV c_pow = pe_powers(c, rs_max);
   FqV ev(2 * n);
   for (size_t p = 0; p < 2 * n; p++) {
     Fq x = fq_zero();

@@ -8,7 +8,7 @@
 //   KnowledgeProof / EqualityProof / ProductProof / DotProductProof::verify   src/nizk/mod.rs:50-404
 //   BulletReductionProof::verify, DotProductProofLog::verify                  src/nizk/bullet.rs:138-232, mod.rs:525-570
 //   ZKSumcheckInstanceProof::verify, SumcheckInstanceProof::verify            src/sumcheck.rs:37-189
-//   PolyEvalProof::verify*                                                    src/dense_mlpoly.rs:492-1205
+//   PolyEvalProof::verify* (slots, exponents, fit, eq halves: pe_plan.hpp)    src/dense_mlpoly.rs:492-1205
 //   R1CSProof::verify                                                         src/r1csproof.rs:687-954
 //   ProductCircuitEvalProofBatched::verify                                    src/product_tree.rs:398-487
 //   SparseMatPolyEvalProof::verify (+ product / hash layer)                   src/sparse_mlpoly.rs:920-1610
@@ -20,6 +20,7 @@
 #include <string>
 
 #include "hostpoly.hpp"
+#include "pe_plan.hpp"
 #include "proto.hpp"
 #include "snark_shape.hpp"
 
@@ -511,65 +512,42 @@ struct V {
     return true;
   }
 
-  // ---- PolyEvalProof (src/dense_mlpoly.rs)
-  static void factored(const FqV& r, FqV* L, FqV* R) {
-    const size_t ln = r.size() / 2;
-    *L = eq_evals_host(FqV(r.begin(), r.begin() + ln));
-    *R = eq_evals_host(FqV(r.begin() + ln, r.end()));
-  }
-  static bool same(const FqV& a, const FqV& b) {
-    if (a.size() != b.size()) return false;
-    for (size_t i = 0; i < a.size(); i++)
-      if (!fq_eq(a[i], b[i])) return false;
-    return true;
-  }
+  // ---- PolyEvalProof (src/dense_mlpoly.rs); slots and exponents of the batched forms: the walk of pe_plan.hpp
   bool pe_verify(ProverGens& g, const DotProductProofLogP& p, const FqV& r, const HExt& C_Zr, const PolyComm& comm) {
     t.protocol("polynomial evaluation proof");
     FqV L, R;
-    factored(r, &L, &R);
+    pe_eq_halves(r, &L, &R);
     if (comm.size() != L.size()) return fail("PolyEvalProof commitment size");
     return dotlog(g, R.size(), p, R, row_msm(L, comm), C_Zr);
   }
   bool pe_verify_plain(ProverGens& g, const DotProductProofLogP& p, const FqV& r, const Fq& Zr, const PolyComm& comm) {
     return pe_verify(g, p, r, commit1(g, g.gens_1, Zr, fq_zero()), comm);
   }
-  static FqV fit(const FqV& r, size_t nv) {  // pad with zeros at the front, or keep the last nv
-    if (nv >= r.size()) {
-      FqV v(nv - r.size(), fq_zero());
-      v.insert(v.end(), r.begin(), r.end());
-      return v;
-    }
-    return FqV(r.end() - nv, r.end());
-  }
   bool pe_batched_disjoint(ProverGens& g, const std::vector<DotProductProofLogP>& proofs,
                            const std::vector<size_t>& np_list, const std::vector<size_t>& ni_list, const FqV& rq,
                            const FqV& ry, const std::vector<HExt>& Zr_list, const std::vector<const PolyComm*>& comms) {
     t.protocol("polynomial evaluation proof");
-    std::vector<std::pair<size_t, size_t>> keys;
-    std::vector<HExt> LZ_list, Zc;
+    std::vector<std::pair<size_t, size_t>> shape;
+    for (size_t i = 0; i < comms.size(); i++) shape.push_back({np_list[i], ni_list[i]});
+    const PeWalk wk = pe_walk_disjoint(shape);
+    const FqV c = pe_coeff_powers(t.challenge("challenge_c"), wk.repeats());
+    std::vector<HExt> LZ_list, Zc;  // per slot, in the order the slots open
     std::vector<FqV> L_list, R_list;
-    const Fq c_base = t.challenge("challenge_c");
-    Fq c = fq_one();
     for (size_t i = 0; i < comms.size(); i++) {
-      const std::pair<size_t, size_t> key = {np_list[i], ni_list[i]};
-      size_t idx = keys.size();
-      for (size_t k = 0; k < keys.size(); k++)
-        if (keys[k] == key) idx = k;
-      if (idx < keys.size()) {
-        c = fq_mul(c, c_base);
-        if (comms[i]->size() != L_list[idx].size()) return fail("PolyEvalProof commitment size");
-        LZ_list[idx] = addP(LZ_list[idx], mulP(row_msm(L_list[idx], *comms[i]), c));
-        Zc[idx] = addP(Zc[idx], mulP(Zr_list[i], c));
+      const size_t k = wk.group[i];
+      if (!wk.opens(i)) {
+        if (comms[i]->size() != L_list[k].size()) return fail("PolyEvalProof commitment size");
+        LZ_list[k] = addP(LZ_list[k], mulP(row_msm(L_list[k], *comms[i]), c[wk.exp[i]]));
+        Zc[k] = addP(Zc[k], mulP(Zr_list[i], c[wk.exp[i]]));
       } else {
-        keys.push_back(key);
         Zc.push_back(Zr_list[i]);
-        const size_t nvq = lg2(key.first), nvy = lg2(key.second);
+        const size_t nvq = lg2(shape[i].first), nvy = lg2(shape[i].second);
         if (nvq > rq.size()) return fail("PolyEvalProof sizes");
         FqV r(rq.end() - nvq, rq.end());
-        const FqV rys = fit(ry, nvy);
+        const FqV rys = pe_fit(ry, nvy);
         r.insert(r.end(), rys.begin(), rys.end());
         FqV L, R;
-        factored(r, &L, &R);
+        pe_eq_halves(r, &L, &R);
         if (comms[i]->size() != L.size()) return fail("PolyEvalProof commitment size");
         LZ_list.push_back(row_msm(L, *comms[i]));
         L_list.push_back(L);
@@ -584,27 +562,19 @@ struct V {
   bool pe_plain_batched_points(ProverGens& g, const std::vector<DotProductProofLogP>& proofs,
                                const std::vector<FqV>& r_list, const FqV& Zr_list, const PolyComm& comm) {
     t.protocol("polynomial evaluation proof");
-    const size_t ln = r_list[0].size() / 2;
-    std::vector<FqV> keys, L_list, R_list;
+    const PeWalk wk = pe_walk_points(r_list);
+    const FqV c = pe_coeff_powers(t.challenge("challenge_c"), wk.repeats());
+    std::vector<FqV> L_list, R_list;
     FqV Zc;
-    const Fq c_base = t.challenge("challenge_c");
-    Fq c = fq_one();
     for (size_t i = 0; i < r_list.size(); i++) {
+      const size_t k = wk.group[i];
       FqV Li, Ri;
-      factored(r_list[i], &Li, &Ri);
-      const FqV key(r_list[i].begin(), r_list[i].begin() + ln);
-      size_t idx = keys.size();
-      for (size_t k = 0; k < keys.size(); k++)
-        if (same(keys[k], key)) {
-          idx = k;
-          break;
-        }
-      if (idx < keys.size()) {
-        c = fq_mul(c, c_base);
-        for (size_t j = 0; j < Ri.size(); j++) R_list[idx][j] = fq_add(R_list[idx][j], fq_mul(c, Ri[j]));
-        Zc[idx] = fq_add(Zc[idx], fq_mul(c, Zr_list[i]));
+      pe_eq_halves(r_list[i], &Li, &Ri);
+      if (!wk.opens(i)) {
+        const Fq& ci = c[wk.exp[i]];
+        for (size_t j = 0; j < Ri.size(); j++) R_list[k][j] = fq_add(R_list[k][j], fq_mul(ci, Ri[j]));
+        Zc[k] = fq_add(Zc[k], fq_mul(ci, Zr_list[i]));
       } else {
-        keys.push_back(key);
         L_list.push_back(Li);
         R_list.push_back(Ri);
         Zc.push_back(Zr_list[i]);
@@ -637,29 +607,23 @@ struct V {
                                   const std::vector<const PolyComm*>& comms, const std::vector<size_t>& nv_list) {
     t.protocol("polynomial evaluation proof");
     if (comms.size() != r_list.size()) return fail("PolyEvalProof count");
-    std::vector<std::pair<size_t, FqV>> keys;
+    std::vector<FqV> r;
+    for (size_t i = 0; i < comms.size(); i++) r.push_back(pe_fit(r_list[i], nv_list[i]));
+    const PeWalk wk = pe_walk_instances(r);
+    const FqV c = pe_coeff_powers(t.challenge("challenge_c"), wk.repeats());
     std::vector<HExt> LZ_list;
     FqV Zc;
     std::vector<FqV> R_list;
-    const Fq c_base = t.challenge("challenge_c");
-    Fq c = fq_one();
     for (size_t i = 0; i < comms.size(); i++) {
+      const size_t k = wk.group[i];
       FqV L, R;
-      factored(fit(r_list[i], nv_list[i]), &L, &R);
+      pe_eq_halves(r[i], &L, &R);
       if (comms[i]->size() != L.size()) return fail("PolyEvalProof commitment size");
       const HExt LZ = row_msm(L, *comms[i]);
-      size_t idx = keys.size();
-      for (size_t k = 0; k < keys.size(); k++)
-        if (keys[k].first == nv_list[i] && same(keys[k].second, R)) {
-          idx = k;
-          break;
-        }
-      if (idx < keys.size()) {
-        c = fq_mul(c, c_base);
-        LZ_list[idx] = addP(LZ_list[idx], mulP(LZ, c));
-        Zc[idx] = fq_add(Zc[idx], fq_mul(c, Zr_list[i]));
+      if (!wk.opens(i)) {
+        LZ_list[k] = addP(LZ_list[k], mulP(LZ, c[wk.exp[i]]));
+        Zc[k] = fq_add(Zc[k], fq_mul(c[wk.exp[i]], Zr_list[i]));
       } else {
-        keys.push_back({nv_list[i], R});
         Zc.push_back(Zr_list[i]);
         LZ_list.push_back(LZ);
         R_list.push_back(R);
@@ -674,39 +638,21 @@ struct V {
   bool pe_uni_batched(ProverGens& g, const DotProductProofLogP& p, const Fq& r, const std::vector<HExt>& C_Zr,
                       const std::vector<const PolyComm*>& comms, const std::vector<size_t>& sizes) {
     t.protocol("polynomial evaluation proof");
-    size_t max_size = 0;
-    for (auto s : sizes) max_size = std::max(max_size, s);
-    const size_t nvm = lg2(npow2(max_size)), rn = nvm - nvm / 2;
-    FqV R;
-    Fq rb = fq_one();
-    for (size_t i = 0; i < ((size_t)1 << rn); i++) {
-      R.push_back(rb);
-      rb = fq_mul(rb, r);
+    std::vector<size_t> nvs;
+    size_t nvm = 0;
+    for (auto s : sizes) {
+      nvs.push_back(lg2(npow2(s)));
+      nvm = std::max(nvm, nvs.back());
     }
-    std::vector<std::pair<size_t, FqV>> Lmap;
+    const FqV R = pe_uni_R(r, nvm);
+    const PeUniL u = pe_uni_Ls(r, nvs);
     const Fq c_base = t.challenge("challenge_c");
     Fq c = fq_one();
     HExt LZc = h::hext_identity(), Zrc = h::hext_identity();
-    for (size_t i = 0; i < comms.size(); i++) {
-      const size_t nv = lg2(npow2(sizes[i]));
-      const FqV* L = nullptr;
-      for (auto& kv : Lmap)
-        if (kv.first == nv) L = &kv.second;
-      if (!L) {
-        const size_t l2 = nv / 2, r2 = nv - nv / 2;
-        Fq r_base = fq_one();
-        for (size_t k = 0; k < ((size_t)1 << r2); k++) r_base = fq_mul(r_base, r);
-        FqV Lv;
-        Fq lb = fq_one();
-        for (size_t k = 0; k < ((size_t)1 << l2); k++) {
-          Lv.push_back(lb);
-          lb = fq_mul(lb, r_base);
-        }
-        Lmap.push_back({nv, Lv});
-        L = &Lmap.back().second;
-      }
-      if (comms[i]->size() != L->size()) return fail("PolyEvalProof commitment size");
-      LZc = addP(LZc, mulP(row_msm(*L, *comms[i]), c));
+    for (size_t i = 0; i < comms.size(); i++) {  // no grouping in this form: c advances after every term
+      const FqV& L = u.L[u.of[i]];
+      if (comms[i]->size() != L.size()) return fail("PolyEvalProof commitment size");
+      LZc = addP(LZc, mulP(row_msm(L, *comms[i]), c));
       Zrc = addP(Zrc, mulP(C_Zr[i], c));
       c = fq_mul(c, c_base);
     }

@@ -1,7 +1,8 @@
 """CPU checks of the dense polynomial commitment seam (include/spg.h spg_poly_*): the entry points are declared and
 exported, the tests' checker (tests/polyeval_ref.py over the oracle's headers) proves what the oracle's own verifiers
 accept, its blinded bound is the plain-integer sum, and the product's grouping plan (csrc/pe_plan.hpp through
-spgh_pe_plan) gives the groups, first-seen order and coefficient exponents the oracle's provers derive."""
+spgh_pe_plan) gives the groups, first-seen order and coefficient exponents the oracle's provers derive; the
+disjoint-rounds walk (spgh_pe_walk_disjoint) against the reference's rule stated in plain Python."""
 import ctypes
 import os
 import re
@@ -153,6 +154,49 @@ def test_plan_points_abacba(oracle):
     assert len(check_plan([4], pc.points(8, 4, "a"), False)[1]) == 1
     terms, groups = check_plan([11], pc.points(9, 11, "abcdea"), False)
     assert len(groups) == 5 and [t[1] for t in terms] == [0, 0, 0, 0, 0, 1]
+
+
+def walk_disjoint(shapes):
+    hc = ctypes.CDLL(HOSTCHECK)
+    hc.spgh_pe_walk_disjoint.restype = ctypes.c_long
+    n = len(shapes)
+    group, exp = (ctypes.c_size_t * n)(), (ctypes.c_size_t * n)()
+    flat = (ctypes.c_size_t * (2 * n))(*[x for s in shapes for x in s])
+    k = hc.spgh_pe_walk_disjoint(ctypes.c_size_t(n), flat, group, exp)
+    return list(group), list(exp), k
+
+
+def disjoint_rule(shapes):
+    """prove_batched_instances_disjoint_rounds (dense_mlpoly.rs:861-960) in plain Python: a map from (num_proofs,
+    num_inputs) to a slot; a repeat first advances the one running exponent, then joins its slot with it"""
+    slots, group, exp, e = {}, [], [], 0
+    for key in shapes:
+        if key in slots:
+            e += 1
+            exp.append(e)
+        else:
+            slots[key] = len(slots)
+            exp.append(0)
+        group.append(slots[key])
+    return group, exp, len(slots)
+
+
+A, B, C = (4, 8), (2, 8), (4, 4)
+DISJOINT_CASES = {
+    "one": ([A], [0], [0]),
+    "one_key": ([A, A, A], [0, 0, 0], [0, 1, 2]),
+    "distinct": ([A, B, C, (8, 8)], [0, 1, 2, 3], [0, 0, 0, 0]),
+    "abacba": ([A, B, A, C, B, A], [0, 1, 0, 2, 1, 0], [0, 0, 1, 0, 2, 3]),
+    "num_inputs_differs": ([(4, 8), (4, 16)], [0, 1], [0, 0]),
+    "num_proofs_differs": ([(4, 8), (8, 8)], [0, 1], [0, 0]),
+}
+
+
+@pytest.mark.parametrize("name", list(DISJOINT_CASES))
+def test_walk_disjoint(name):
+    shapes, groups, exps = DISJOINT_CASES[name]
+    assert disjoint_rule(shapes) == (groups, exps, max(groups) + 1)
+    assert walk_disjoint(shapes) == (groups, exps, max(groups) + 1)
 
 
 @pytest.mark.parametrize("name", ["mixed", "padtrim", "same_R", "forty"])
