@@ -413,6 +413,42 @@ int spg_poly_eval_verify_plain_batched_instances(spg_ctx* ctx, const spg_poly_ge
                                                  const uint8_t* comms, const size_t* comm_lens,
                                                  const size_t* num_vars_list, size_t n, spg_transcript* t,
                                                  const uint8_t* proof, size_t proof_len);
+/* The two remaining forms of PolyEvalProof (:861-1203), under the conventions of the block above: spg_buf polynomials,
+ * no blinds (the reference's blinds_opt / blind_Zr_opt of the disjoint form are None at every call site), single-rank,
+ * *len from the shapes alone, every SPG_E_ARG before anything is launched, appended or drawn: also num_proofs or
+ * num_inputs that is no power of two, lg num_proofs[i] > rq_len, and (univariate form) the widest polynomial's
+ * 2^(num_vars - num_vars/2) beyond the handle's n.
+ * prove_batched_instances_disjoint_rounds (:861-960): polynomial i has num_proofs_list[i] * num_inputs_list[i] scalars
+ * (both powers of two; num_vars_i = lg num_proofs + lg num_inputs in 1 .. 30). Its point is the last lg num_proofs
+ * entries of rq, followed by ry fitted to lg num_inputs entries: zeros at the FRONT when shorter, its LAST lg num_inputs
+ * entries when longer. One proof per distinct (num_proofs, num_inputs) in first-seen order: bincode(Vec<PolyEvalProof>)
+ * of 8 + sum over those of the single proof's size. */
+int spg_pe_prove_disjoint(spg_ctx* ctx, const spg_poly_gens* g, const spg_buf* const* polys, const size_t* offsets,
+                          const size_t* num_proofs_list, const size_t* num_inputs_list, size_t n,
+                          const uint64_t* rq_mont, size_t rq_len, const uint64_t* ry_mont, size_t ry_len,
+                          const uint64_t* Zr_list_mont, spg_transcript* t, spg_random_tape* tape, uint8_t* proof,
+                          size_t cap, size_t* len);
+/* verify_batched_instances_disjoint_rounds (:962-1044): C_Zr_list = n x 32 bytes (the commitments to the evaluations),
+ * comms = every polynomial's rows concatenated, comm_lens[i] rows each */
+int spg_pe_verify_disjoint(spg_ctx* ctx, const spg_poly_gens* g, const size_t* num_proofs_list,
+                           const size_t* num_inputs_list, size_t n, const uint64_t* rq_mont, size_t rq_len,
+                           const uint64_t* ry_mont, size_t ry_len, const uint8_t* C_Zr_list, const uint8_t* comms,
+                           const size_t* comm_lens, spg_transcript* t, const uint8_t* proof, size_t proof_len);
+/* The evaluations the univariate form opens (ShiftProofs::prove, src/lib.rs:417-418): polynomial i read as univariate,
+ * Zr_out[i] = sum_k Z_i[k] r^k. One launch pair for all of them. */
+int spg_pe_uni_evals(spg_ctx* ctx, const spg_buf* const* polys, const size_t* offsets, const size_t* num_vars_list,
+                     size_t n, const uint64_t* r_mont, uint64_t* Zr_out_mont);
+/* prove_uni_batched_instances (:1046-1130): every polynomial opened at the one scalar r, polynomial i joining with
+ * challenge_c^i into the first 2^(num_vars_i - num_vars_i/2) entries of one vector of the widest polynomial's size.
+ * proof = bincode(PolyEvalProof); C_Zr (optional) receives C_Zr_prime. One launch pair whatever n is. */
+int spg_pe_prove_uni(spg_ctx* ctx, const spg_poly_gens* g, const spg_buf* const* polys, const size_t* offsets,
+                     const size_t* num_vars_list, size_t n, const uint64_t* r_mont, const uint64_t* Zr_list_mont,
+                     spg_transcript* t, spg_random_tape* tape, uint8_t* proof, size_t cap, size_t* len,
+                     uint8_t C_Zr[32]);
+/* verify_uni_batched_instances (:1132-1203): poly_sizes as the reference takes them (num_vars_i = lg next_pow2(size_i)) */
+int spg_pe_verify_uni(spg_ctx* ctx, const spg_poly_gens* g, const uint64_t* r_mont, const uint8_t* C_Zr_list,
+                      const uint8_t* comms, const size_t* comm_lens, const size_t* poly_sizes, size_t n,
+                      spg_transcript* t, const uint8_t* proof, size_t proof_len);
 
 /* ---- R1CSProof::prove (src/r1csproof.rs:210-685) ----------------------------------------------
  * R1CSGens::new(label, _, num_vars) (src/r1csproof.rs:71-79): gens_pc = PolyCommitmentGens for

@@ -450,6 +450,55 @@ long spgh_pe_walk_disjoint(size_t n, const size_t* shape, size_t* group, size_t*
   std::copy(w.exp.begin(), w.exp.end(), exp);
   return (long)w.first.size();
 }
+// pe_plan_disjoint (pe_plan.hpp), the plan spg_pe_prove_disjoint proves by: term i has the shape (shape[2 i],
+// shape[2 i + 1]) (powers of two, lg num_proofs <= rq_len), the point halves rq and ry. term, fitted, grp, tot: the row
+// formats of spgh_pe_plan. Returns the number of groups.
+long spgh_pe_plan_disjoint(size_t n, const size_t* shape, const uint64_t* rq, size_t rq_len, const uint64_t* ry,
+                           size_t ry_len, size_t* term, uint64_t* fitted, size_t* grp, size_t* tot) {
+  std::vector<size_t> np(n), ni(n);
+  for (size_t i = 0; i < n; i++) np[i] = shape[2 * i], ni[i] = shape[2 * i + 1];
+  std::vector<Fq> q(rq_len), y(ry_len);
+  for (size_t i = 0; i < rq_len; i++) q[i] = ldq(rq + 4 * i);
+  for (size_t i = 0; i < ry_len; i++) y[i] = ldq(ry + 4 * i);
+  const PePlan p = pe_plan_disjoint(np.data(), ni.data(), n, q.data(), rq_len, y.data(), ry_len);
+  size_t fo = 0;
+  for (size_t i = 0; i < n; i++) {
+    const PeTerm& t = p.terms[i];
+    const size_t row[6] = {t.group, t.exp, t.bound ? (size_t)1 : 0, t.S, t.chunk, t.slab};
+    memcpy(term + 6 * i, row, sizeof(row));
+    for (size_t k = 0; fitted && k < t.r.size(); k++) stq(fitted + 4 * (fo + k), t.r[k]);
+    fo += t.r.size();
+  }
+  for (size_t k = 0; k < p.groups.size(); k++) {
+    const PeGroup& g = p.groups[k];
+    const size_t row[7] = {g.nv, g.Ls, g.Rs, g.first, g.S, g.part_off, g.out_off};
+    memcpy(grp + 7 * k, row, sizeof(row));
+  }
+  if (tot) {
+    tot[0] = p.part_len, tot[1] = p.out_len, tot[2] = p.xblocks, tot[3] = pe_list_bytes(p);
+  }
+  return (long)p.groups.size();
+}
+// pe_plan_uni (pe_plan.hpp), the plan of spg_pe_prove_uni (per_term = 0: one output of R_size) and spg_pe_uni_evals
+// (per_term = 1: one output per term). Per term: term[8 i ..] = (coefficient exponent, num_vars, Ls, Rs, S, chunk,
+// part_off, out_off). tot = (part_len, out_len, xblocks, proof bytes, R_size). ends (optional, with r and c_base):
+// the first and the last entry of every term's scaled table L'_i (pe_uni_scaled_Ls), 2 n scalars. Returns the number
+// of terms.
+long spgh_pe_plan_uni(int per_term, size_t n, const size_t* nv_list, size_t* term, size_t* tot, const uint64_t* r,
+                      const uint64_t* c_base, uint64_t* ends) {
+  const PeUniPlan p = pe_plan_uni(nv_list, n, per_term != 0);
+  if (ends && r && c_base) {
+    const std::vector<FqV> Lp = pe_uni_scaled_Ls(ldq(r), std::vector<size_t>(nv_list, nv_list + n), ldq(c_base));
+    for (size_t i = 0; i < n; i++) stq(ends + 8 * i, Lp[i].front()), stq(ends + 8 * i + 4, Lp[i].back());
+  }
+  for (size_t i = 0; i < n; i++) {
+    const PeUniTerm& t = p.terms[i];
+    const size_t row[8] = {t.exp, t.nv, t.Ls, t.Rs, t.S, t.chunk, t.part_off, t.out_off};
+    memcpy(term + 8 * i, row, sizeof(row));
+  }
+  tot[0] = p.part_len, tot[1] = p.out_len, tot[2] = p.xblocks, tot[3] = pe_proof_bytes(p.R_size), tot[4] = p.R_size;
+  return (long)p.terms.size();
+}
 
 }  // extern "C"
 

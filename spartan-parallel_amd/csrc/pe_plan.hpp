@@ -1,9 +1,9 @@
 // spg — the grouping rule of PolyEvalProof's batched openings (src/dense_mlpoly.rs:531-960), derived from the points
 // and sizes alone and written once. Host-only (no HIP types). Every prover and verifier of a batched form asks it
 // for the walk: polyeval.hip (the whole-proof provers prove_batched_points / prove_batched_instances and the
-// spg_poly_eval_* entries), r1cs.hip (Prover::polyeval_batched), verify.hip (V::pe_batched_disjoint,
-// V::pe_plain_batched_points, V::pe_plain_batched_instances), and libspg_hostcheck.so (spgh_pe_plan and
-// spgh_pe_walk_disjoint: the tests' view of it).
+// spg_poly_eval_* and spg_pe_* entries), r1cs.hip (Prover::polyeval_batched), verify.hip (V::pe_batched_disjoint,
+// V::pe_plain_batched_points, V::pe_plain_batched_instances), and libspg_hostcheck.so (spgh_pe_plan,
+// spgh_pe_plan_disjoint, spgh_pe_plan_uni and spgh_pe_walk_disjoint: the tests' view of it).
 //
 // Every batched form walks its terms in order and keeps a map from a key to a proof slot. A term whose key is new
 // opens a slot (coefficient 1); a term whose key repeats first advances the one running coefficient c <- c * c_base
@@ -17,7 +17,7 @@
 // Points are compared by their bytes: an Fq is the unique canonical value in [0, q) (field.hpp; fq_eq is the same
 // limb comparison), which holds for transcript challenges, field results and the reduced scalars the C-ABI takes.
 // The univariate form (prove_uni_batched_instances, :1046-1130) has no grouping: c advances after every term. It
-// shares the power vectors below.
+// shares the power vectors below and has a plan of its own (pe_plan_uni): its terms have different widths.
 //
 // The plan also lays out the device bound (polyeval.hip): every term that is bound owns S row ranges of `chunk` rows
 // ("slabs" of Rs partial sums each), and the slabs of one group's terms are contiguous, so the column-sum stage adds
@@ -214,6 +214,79 @@ inline PePlan pe_plan_instances(const size_t* nv_list, const Fq* r_list, const s
   std::vector<FqV> r(n);
   for (size_t i = 0, o = 0; i < n; o += r_lens[i++]) r[i] = pe_fit(r_list + o, r_lens[i], nv_list[i]);
   return pe_plan_of(pe_walk_instances(r), r, false, kPeKT);
+}
+// disjoint rounds: polynomial i has np[i] * ni[i] scalars (powers of two, lg np[i] <= rq_len: the caller's check); its
+// point is the last lg np[i] entries of rq, then ry fitted to lg ni[i] entries (:905-921). The instances form with
+// another key and another fit: every term is bound, a repeat's scaled L table makes the group sum LZ_list[idx] += c LZ
+inline PePlan pe_plan_disjoint(const size_t* np, const size_t* ni, size_t n, const Fq* rq, size_t rq_len, const Fq* ry,
+                               size_t ry_len) {
+  std::vector<std::pair<size_t, size_t>> shape(n);
+  std::vector<FqV> r(n);
+  for (size_t i = 0; i < n; i++) {
+    shape[i] = {np[i], ni[i]};
+    r[i].assign(rq + (rq_len - lg2(np[i])), rq + rq_len);
+    const FqV rys = pe_fit(ry, ry_len, lg2(ni[i]));
+    r[i].insert(r[i].end(), rys.begin(), rys.end());
+  }
+  return pe_plan_of(pe_walk_disjoint(shape), r, false, kPeKT);
+}
+
+// The univariate form (prove_uni_batched_instances, :1046-1130) has no walk: term i joins with c_base^i (c advances
+// after every term, the first included) and all terms add into ONE vector of the widest polynomial's R_size, term i
+// into its first Rs_i entries only (:1109-1112). The slabs of a term therefore have a width of their own, and a group
+// of the column-sum stage is a list of terms of different widths (k_pe_sum_ragged, pe_bound.hpp): term t owns S slabs
+// of Rs scalars at part_off. per_term: one output of Rs_i scalars per term instead (the evaluations sum_k Z_i[k] r^k
+// are read from them), each group a list of one.
+struct PeUniTerm {
+  size_t exp = 0;           // its coefficient is c_base^exp: its index
+  size_t nv = 0, Ls = 0, Rs = 0;
+  size_t S = 0, chunk = 0;  // its slabs and the rows per slab
+  size_t part_off = 0;      // first scalar of its slabs in the partial buffer
+  size_t out_off = 0;       // first scalar of the output it adds into
+};
+struct PeUniPlan {
+  std::vector<PeUniTerm> terms;  // term i: coefficient c_base^i
+  size_t R_size = 0;             // of the widest polynomial
+  bool per_term = false;
+  size_t part_len = 0, out_len = 0, xblocks = 0;
+};
+inline PeUniPlan pe_plan_uni(const size_t* nv_list, size_t n, bool per_term) {
+  PeUniPlan p;
+  p.per_term = per_term;
+  for (size_t i = 0; i < n; i++) {
+    PeUniTerm t;
+    t.exp = i;
+    t.nv = nv_list[i], t.Ls = (size_t)1 << (t.nv / 2), t.Rs = (size_t)1 << (t.nv - t.nv / 2);
+    p.R_size = std::max(p.R_size, t.Rs);
+    p.xblocks += (t.Rs + 255) / 256;
+    p.terms.push_back(t);
+  }
+  const size_t want = std::max<size_t>(1, kPeBlocks / std::max<size_t>(1, p.xblocks));  // as pe_layout
+  for (PeUniTerm& t : p.terms) {
+    const size_t S = std::min(t.Ls, want);
+    t.chunk = (t.Ls + S - 1) / S;
+    t.S = (t.Ls + t.chunk - 1) / t.chunk;
+    t.part_off = p.part_len;
+    p.part_len += t.S * t.Rs;
+    if (per_term) {
+      t.out_off = p.out_len;
+      p.out_len += t.Rs;
+    }
+  }
+  if (!per_term) p.out_len = p.R_size;
+  return p;
+}
+// L'_t = c_base^t (r^(Rs_t j))_j of every term: the scaled eq tables' counterpart
+inline std::vector<FqV> pe_uni_scaled_Ls(const Fq& r, const std::vector<size_t>& nv_list, const Fq& c_base) {
+  const PeUniL u = pe_uni_Ls(r, nv_list);
+  std::vector<FqV> Lp(nv_list.size());
+  Fq c = fq_one();
+  for (size_t i = 0; i < nv_list.size(); i++, c = fq_mul(c, c_base)) {
+    Lp[i] = u.L[u.of[i]];
+    if (i)
+      for (Fq& x : Lp[i]) x = fq_mul(x, c);
+  }
+  return Lp;
 }
 
 // bincode(DotProductProofLog) of n = Rs scalars: two point vectors of lg Rs, delta, beta, z1, z2

@@ -5,6 +5,8 @@
 //   PolyEvalProof::prove / verify / verify_plain   :437-528                      spg_poly_eval_prove / _verify(_plain)
 //   prove_batched_points / verify_plain_..         :531-685                      spg_poly_eval_*_batched_points
 //   prove_batched_instances / verify_plain_..      :689-857                      spg_poly_eval_*_batched_instances
+//   .._disjoint_rounds / verify_..                 :861-1044                     spg_pe_prove_disjoint / _verify_disjoint
+//   prove_uni_batched_instances / verify_..        :1046-1203                    spg_pe_prove_uni / _verify_uni, spg_pe_uni_evals
 //
 // The prover's O(2^num_vars) work is the bound L.Z of every polynomial of a call (DensePolynomial::bound, :258-265).
 // One launch pair computes them all from the plan of pe_plan.hpp:
@@ -15,6 +17,8 @@
 // up to kPeKTMax accumulators (the plan gives it kPeKT = 1: the measured tile did not pay, pe_plan.hpp). Job and
 // group descriptors live in device memory: a call's polynomial count is limited by memory alone. Fq sums are exact
 // and canonical, so the result does not depend on the summation order.
+// The univariate form adds polynomials of different widths into one vector; its second launch is k_pe_sum_ragged over
+// per-term slab descriptors (pe_bound_ragged, pe_plan_uni).
 // The Bullet reductions (dotproduct_log_prove) and the verifier's checks (verify.hip) are the whole-proof paths'.
 //
 // SNARK::prove's PolyEvalProof provers on host polynomials live here too (pe_prove.hpp): prove_batched_points,
@@ -39,6 +43,7 @@ struct spg_poly_gens {  // PolyCommitmentGens: gens_n = G_0 .. G_{n-1} with h, g
 namespace spg {
 
 constexpr size_t kWsPeJobs = 124, kWsPeSums = 125, kWsPeL = 126, kWsPePart = 127, kWsPeOut = 128, kWsPeBlinds = 129;
+constexpr size_t kWsPeRagTerms = 130;
 
 // Every L.Z vector of a plan in one launch pair and one download. Z: the polynomial of every term (points form: of
 // term 0, shared by all). Lp: the scaled eq table of every bound term, in term order. out: plan.out_len scalars, group g
@@ -111,6 +116,65 @@ static int pe_bound(spg_ctx* ctx, const PePlan& plan, bool points, const std::ve
     KScope ks(ctx, "pe_bound", zbytes + 64.0 * (double)plan.part_len);
     hipLaunchKernelGGL(k_pe_part, dim3(b0, Smax), dim3(256), 0, s, dj, (uint32_t)jobs.size(), dL, dpart, plan.part_len);
     hipLaunchKernelGGL(k_pe_sum, dim3(c0), dim3(256), 0, s, ds, (uint32_t)sums.size(), dpart, dout, plan.out_len);
+    if (hipGetLastError() != hipSuccess) return set_err(ctx, SPG_E_HIP, "poly eval: bound launch");
+  }
+  out->assign(plan.out_len, fq_zero());
+  return d2h_fq(ctx, dout, out->data(), plan.out_len);  // synchronises: the host vectors above outlive their copies
+}
+
+// The univariate plan's bound, likewise one launch pair and one download whatever the polynomial count: k_pe_part with
+// one kt = 1 job per term, then k_pe_sum_ragged over the plan's groups (all terms into one vector of R_size, or one
+// group per term). Lp: the scaled power table of every term.
+static int pe_bound_ragged(spg_ctx* ctx, const PeUniPlan& plan, const std::vector<const Fq*>& Z,
+                           const std::vector<FqV>& Lp, FqV* out) {
+  const size_t n = plan.terms.size();
+  FqV Lall;
+  std::vector<PeJob> jobs(n);
+  std::vector<PeRagTerm> terms(n);
+  uint32_t b0 = 0, Smax = 1;
+  double zbytes = 0;
+  for (size_t i = 0; i < n; i++) {
+    const PeUniTerm& t = plan.terms[i];
+    PeJob& j = jobs[i];
+    memset(&j, 0, sizeof(j));
+    j.Z = Z[i], j.Rs = t.Rs, j.Ls = (uint32_t)t.Ls, j.chunk = (uint32_t)t.chunk, j.S = (uint32_t)t.S, j.kt = 1;
+    j.offL[0] = Lall.size();
+    j.offP[0] = t.part_off;
+    j.b0 = b0;
+    b0 += (uint32_t)((t.Rs + 255) / 256);
+    Smax = std::max(Smax, j.S);
+    zbytes += 32.0 * (double)t.Ls * (double)t.Rs;
+    Lall.insert(Lall.end(), Lp[i].begin(), Lp[i].end());
+    terms[i] = PeRagTerm{t.part_off, t.Rs, (uint32_t)t.S};
+  }
+  std::vector<PeRagSum> sums;
+  uint32_t c0 = 0;
+  auto add_group = [&](size_t o, size_t Rs, size_t t0, size_t nt) {
+    sums.push_back(PeRagSum{o, Rs, (uint32_t)t0, (uint32_t)nt, c0});
+    c0 += (uint32_t)((Rs + kPeSumCols - 1) / kPeSumCols);
+  };
+  if (plan.per_term)
+    for (size_t i = 0; i < n; i++) add_group(plan.terms[i].out_off, plan.terms[i].Rs, i, 1);
+  else
+    add_group(0, plan.R_size, 0, n);
+  if (b0 != plan.xblocks) return set_err(ctx, SPG_E_ARG, "poly eval: plan and jobs disagree");
+  PeJob* dj = (PeJob*)ws_get(ctx, kWsPeJobs, jobs.size() * sizeof(PeJob) + 64);
+  PeRagSum* ds = (PeRagSum*)ws_get(ctx, kWsPeSums, sums.size() * sizeof(PeRagSum) + 64);
+  PeRagTerm* dt = (PeRagTerm*)ws_get(ctx, kWsPeRagTerms, terms.size() * sizeof(PeRagTerm) + 64);
+  Fq* dL = (Fq*)ws_get(ctx, kWsPeL, Lall.size() * sizeof(Fq) + 64);
+  Fq* dpart = (Fq*)ws_get(ctx, kWsPePart, plan.part_len * sizeof(Fq) + 64);
+  Fq* dout = (Fq*)ws_get(ctx, kWsPeOut, plan.out_len * sizeof(Fq) + 64);
+  if (!dj || !ds || !dt || !dL || !dpart || !dout) return set_err(ctx, SPG_E_NOMEM, "poly eval: bound workspace");
+  hipStream_t s = ctx->stream;
+  SPG_HIP(ctx, hipMemcpyAsync(dj, jobs.data(), jobs.size() * sizeof(PeJob), hipMemcpyHostToDevice, s));
+  SPG_HIP(ctx, hipMemcpyAsync(ds, sums.data(), sums.size() * sizeof(PeRagSum), hipMemcpyHostToDevice, s));
+  SPG_HIP(ctx, hipMemcpyAsync(dt, terms.data(), terms.size() * sizeof(PeRagTerm), hipMemcpyHostToDevice, s));
+  SPG_HIP(ctx, hipMemcpyAsync(dL, Lall.data(), Lall.size() * sizeof(Fq), hipMemcpyHostToDevice, s));
+  {
+    KScope ks(ctx, "pe_bound_ragged", zbytes + 64.0 * (double)plan.part_len);
+    hipLaunchKernelGGL(k_pe_part, dim3(b0, Smax), dim3(256), 0, s, dj, (uint32_t)jobs.size(), dL, dpart, plan.part_len);
+    hipLaunchKernelGGL(k_pe_sum_ragged, dim3(c0), dim3(256), 0, s, ds, (uint32_t)sums.size(), dt, dpart, plan.part_len,
+                       dout, plan.out_len);
     if (hipGetLastError() != hipSuccess) return set_err(ctx, SPG_E_HIP, "poly eval: bound launch");
   }
   out->assign(plan.out_len, fq_zero());
@@ -246,6 +310,60 @@ static int prove_points_impl(spg_ctx* ctx, const spg_poly_gens* pg, const spg_bu
   return rc ? rc : put_bytes(ctx, w, proof, cap, "poly eval prove (points)");
 }
 
+// The instances and disjoint-rounds forms after their plan (whose shapes and polynomials the caller has checked): every
+// term is bound with its eq table, a repeat's scaled by its coefficient, then one proof per group
+static int prove_all_bound(spg_ctx* ctx, const spg_poly_gens* pg, const PePlan& plan, const spg_buf* const* polys,
+                           const size_t* offsets, const FqV& Zr, spg_transcript* tr, spg_random_tape* tape,
+                           uint8_t* proof, size_t cap, size_t* len, const char* what) {
+  const size_t n = plan.terms.size();
+  *len = pe_list_bytes(plan);
+  if (*len > cap) return set_err(ctx, SPG_E_ARG, std::string(what) + ": proof buffer too small");
+  SPG_HIP(ctx, hipSetDevice(ctx->device));
+  ProverGens& g = const_cast<ProverGens&>(pg->g);
+  Tr& t = tr->t;
+  t.protocol("polynomial evaluation proof");
+  const FqV c = pe_coeff_powers(t.challenge("challenge_c"), plan.terms.size() - plan.groups.size());
+  const size_t D = plan.groups.size();
+  std::vector<FqV> Lp(n), Rg(D);
+  std::vector<const Fq*> Zs(n);
+  FqV Zc(D, fq_zero());
+  for (size_t i = 0; i < n; i++) {
+    const PeTerm& tm = plan.terms[i];
+    Zs[i] = polys[i]->d + offsets[i];
+    const size_t ln = tm.nv / 2;
+    Lp[i] = eq_evals_host(FqV(tm.r.begin(), tm.r.begin() + ln));
+    if (tm.exp) {  // L'_i = c L_i: the kernel's group sum is then LZ_idx += c LZ_i
+      for (Fq& x : Lp[i]) x = fq_mul(x, c[tm.exp]);
+      Zc[tm.group] = fq_add(Zc[tm.group], fq_mul(c[tm.exp], Zr[i]));
+    } else {
+      Rg[tm.group] = eq_evals_host(FqV(tm.r.begin() + ln, tm.r.end()));
+      Zc[tm.group] = Zr[i];
+    }
+  }
+  FqV LZ;
+  int rc = pe_bound(ctx, plan, false, Zs, Lp, &LZ);
+  if (rc) return rc;
+  Writer w;
+  rc = prove_groups(ctx, g, plan, LZ, Rg, Zc, t, tape->t, w);
+  return rc ? rc : put_bytes(ctx, w, proof, cap, what);
+}
+
+// the shapes of a disjoint-rounds list, checked before anything else reads them
+static int disjoint_args(spg_ctx* ctx, const spg_poly_gens* pg, const size_t* np_list, const size_t* ni_list, size_t n,
+                         size_t rq_len, const char* what) {
+  auto pow2 = [](size_t x) { return x && !(x & (x - 1)); };
+  for (size_t i = 0; i < n; i++) {
+    if (!pow2(np_list[i]) || !pow2(ni_list[i]))
+      return set_err(ctx, SPG_E_ARG, std::string(what) + ": num_proofs and num_inputs must be powers of two");
+    const size_t nv = lg2(np_list[i]) + lg2(ni_list[i]);
+    if (!nv_ok(nv)) return set_err(ctx, SPG_E_ARG, std::string(what) + ": num_vars must be 1 .. 30");
+    if (lg2(np_list[i]) > rq_len) return set_err(ctx, SPG_E_ARG, std::string(what) + ": rq shorter than lg num_proofs");
+    if (rs_of(nv) > pg->g.n_pc)
+      return set_err(ctx, SPG_E_ARG, std::string(what) + ": polynomial wider than the generators");
+  }
+  return SPG_OK;
+}
+
 // the shapes of an instance list, checked before anything else reads them; *tot_r = scalars of r_list
 static int instances_args(spg_ctx* ctx, const spg_poly_gens* pg, const size_t* nv_list, const size_t* r_lens, size_t n,
                           size_t* tot_r, const char* what) {
@@ -274,38 +392,115 @@ static int prove_instances_impl(spg_ctx* ctx, const spg_poly_gens* pg, const spg
     if (offsets[i] > polys[i]->n || ((size_t)1 << nv_list[i]) > polys[i]->n - offsets[i])
       return set_err(ctx, SPG_E_ARG, "poly eval prove (instances): Z too short");
   }
-  const FqV rs = lds(r_list, tot_r), Zr = lds(Zr_list, n);
-  const PePlan plan = pe_plan_instances(nv_list, rs.data(), r_lens, n);
-  *len = pe_list_bytes(plan);
-  if (*len > cap) return set_err(ctx, SPG_E_ARG, "poly eval prove (instances): proof buffer too small");
+  const FqV rs = lds(r_list, tot_r);
+  return prove_all_bound(ctx, pg, pe_plan_instances(nv_list, rs.data(), r_lens, n), polys, offsets, lds(Zr_list, n), tr,
+                         tape, proof, cap, len, "poly eval prove (instances)");
+}
+
+// prove_batched_instances_disjoint_rounds (:861-960): the same prover over the plan of the (num_proofs, num_inputs) keys
+static int prove_disjoint_impl(spg_ctx* ctx, const spg_poly_gens* pg, const spg_buf* const* polys,
+                               const size_t* offsets, const size_t* np_list, const size_t* ni_list, size_t n,
+                               const uint64_t* rq, size_t rq_len, const uint64_t* ry, size_t ry_len,
+                               const uint64_t* Zr_list, spg_transcript* tr, spg_random_tape* tape, uint8_t* proof,
+                               size_t cap, size_t* len) {
+  if (!ctx || !pg || !polys || !offsets || !np_list || !ni_list || !rq || !ry || !Zr_list || !tr || !tape || !proof ||
+      !len || n == 0)
+    return SPG_E_ARG;
+  int rc = disjoint_args(ctx, pg, np_list, ni_list, n, rq_len, "poly eval prove (disjoint)");
+  if (rc) return rc;
+  for (size_t i = 0; i < n; i++) {
+    if (!polys[i]) return SPG_E_ARG;
+    if (offsets[i] > polys[i]->n || np_list[i] * ni_list[i] > polys[i]->n - offsets[i])
+      return set_err(ctx, SPG_E_ARG, "poly eval prove (disjoint): Z too short");
+  }
+  const FqV q = lds(rq, rq_len), y = lds(ry, ry_len);
+  return prove_all_bound(ctx, pg, pe_plan_disjoint(np_list, ni_list, n, q.data(), rq_len, y.data(), ry_len), polys,
+                         offsets, lds(Zr_list, n), tr, tape, proof, cap, len, "poly eval prove (disjoint)");
+}
+
+// the polynomials of a univariate call, checked before anything else reads them; *max_nv = the widest
+static int uni_args(spg_ctx* ctx, const spg_poly_gens* pg, const spg_buf* const* polys, const size_t* offsets,
+                    const size_t* nv_list, size_t n, size_t* max_nv, const char* what) {
+  *max_nv = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (!polys[i]) return SPG_E_ARG;
+    if (!nv_ok(nv_list[i])) return set_err(ctx, SPG_E_ARG, std::string(what) + ": num_vars must be 1 .. 30");
+    if (offsets[i] > polys[i]->n || ((size_t)1 << nv_list[i]) > polys[i]->n - offsets[i])
+      return set_err(ctx, SPG_E_ARG, std::string(what) + ": Z too short");
+    *max_nv = std::max(*max_nv, nv_list[i]);
+  }
+  if (pg && rs_of(*max_nv) > pg->g.n_pc)
+    return set_err(ctx, SPG_E_ARG, std::string(what) + ": polynomial wider than the generators");
+  return SPG_OK;
+}
+
+// the evaluations the univariate form opens: Z_i(r) = sum_k Z_i[k] r^k = sum_col (L_i.Z_i)[col] r^col with the
+// unscaled power tables, one output per term
+static int uni_evals_impl(spg_ctx* ctx, const spg_buf* const* polys, const size_t* offsets, const size_t* nv_list,
+                          size_t n, const uint64_t* r_mont, uint64_t* Zr_out) {
+  if (!ctx || !polys || !offsets || !nv_list || !r_mont || !Zr_out || n == 0) return SPG_E_ARG;
+  size_t max_nv = 0;
+  int rc = uni_args(ctx, nullptr, polys, offsets, nv_list, n, &max_nv, "poly uni evals");
+  if (rc) return rc;
+  SPG_HIP(ctx, hipSetDevice(ctx->device));
+  const Fq r = ld_fq(r_mont);
+  const std::vector<size_t> nvs(nv_list, nv_list + n);
+  const PeUniPlan plan = pe_plan_uni(nv_list, n, true);
+  const PeUniL u = pe_uni_Ls(r, nvs);
+  std::vector<FqV> Lp(n);
+  std::vector<const Fq*> Zs(n);
+  for (size_t i = 0; i < n; i++) Lp[i] = u.L[u.of[i]], Zs[i] = polys[i]->d + offsets[i];
+  FqV LZ;
+  rc = pe_bound_ragged(ctx, plan, Zs, Lp, &LZ);
+  if (rc) return rc;
+  const FqV R = pe_uni_R(r, max_nv);
+  for (size_t i = 0; i < n; i++) {
+    const PeUniTerm& t = plan.terms[i];
+    Fq e = fq_zero();
+    for (size_t k = 0; k < t.Rs; k++) e = fq_add(e, fq_mul(LZ[t.out_off + k], R[k]));
+    st_fq(Zr_out + 4 * i, e);
+  }
+  return SPG_OK;
+}
+
+// prove_uni_batched_instances (:1046-1130): term i joins with c^i (L'_i = c^i L_i), all into one vector of R_size
+static int prove_uni_impl(spg_ctx* ctx, const spg_poly_gens* pg, const spg_buf* const* polys, const size_t* offsets,
+                          const size_t* nv_list, size_t n, const uint64_t* r_mont, const uint64_t* Zr_list,
+                          spg_transcript* tr, spg_random_tape* tape, uint8_t* proof, size_t cap, size_t* len,
+                          uint8_t* C_Zr) {
+  if (!ctx || !pg || !polys || !offsets || !nv_list || !r_mont || !Zr_list || !tr || !tape || !proof || !len || n == 0)
+    return SPG_E_ARG;
+  size_t max_nv = 0;
+  int rc = uni_args(ctx, pg, polys, offsets, nv_list, n, &max_nv, "poly eval prove (uni)");
+  if (rc) return rc;
+  *len = pe_proof_bytes(rs_of(max_nv));
+  if (*len > cap) return set_err(ctx, SPG_E_ARG, "poly eval prove (uni): proof buffer too small");
   SPG_HIP(ctx, hipSetDevice(ctx->device));
   ProverGens& g = const_cast<ProverGens&>(pg->g);
   Tr& t = tr->t;
   t.protocol("polynomial evaluation proof");
-  const FqV c = pe_coeff_powers(t.challenge("challenge_c"), plan.terms.size() - plan.groups.size());
-  const size_t D = plan.groups.size();
-  std::vector<FqV> Lp(n), Rg(D);
+  const Fq r = ld_fq(r_mont);
+  const FqV Zr = lds(Zr_list, n), R = pe_uni_R(r, max_nv);
+  const Fq c_base = t.challenge("challenge_c");
+  const PeUniPlan plan = pe_plan_uni(nv_list, n, false);
+  const std::vector<FqV> Lp = pe_uni_scaled_Ls(r, std::vector<size_t>(nv_list, nv_list + n), c_base);
   std::vector<const Fq*> Zs(n);
-  FqV Zc(D, fq_zero());
-  for (size_t i = 0; i < n; i++) {
-    const PeTerm& tm = plan.terms[i];
+  Fq Zrc = fq_zero(), c = fq_one();
+  for (size_t i = 0; i < n; i++, c = fq_mul(c, c_base)) {
     Zs[i] = polys[i]->d + offsets[i];
-    const size_t ln = tm.nv / 2;
-    Lp[i] = eq_evals_host(FqV(tm.r.begin(), tm.r.begin() + ln));
-    if (tm.exp) {  // L'_i = c L_i: the kernel's group sum is then LZ_idx += c LZ_i
-      for (Fq& x : Lp[i]) x = fq_mul(x, c[tm.exp]);
-      Zc[tm.group] = fq_add(Zc[tm.group], fq_mul(c[tm.exp], Zr[i]));
-    } else {
-      Rg[tm.group] = eq_evals_host(FqV(tm.r.begin() + ln, tm.r.end()));
-      Zc[tm.group] = Zr[i];
-    }
+    Zrc = fq_add(Zrc, fq_mul(c, Zr[i]));
   }
-  FqV LZ;
-  rc = pe_bound(ctx, plan, false, Zs, Lp, &LZ);
+  FqV LZc;
+  rc = pe_bound_ragged(ctx, plan, Zs, Lp, &LZc);
+  if (rc) return rc;
+  DotProductProofLogP p;
+  Pt cy;
+  rc = dotproduct_log_prove(ctx, g, t, tape->t, LZc, fq_zero(), R, Zrc, fq_zero(), &p, &cy);
   if (rc) return rc;
   Writer w;
-  rc = prove_groups(ctx, g, plan, LZ, Rg, Zc, t, tape->t, w);
-  return rc ? rc : put_bytes(ctx, w, proof, cap, "poly eval prove (instances)");
+  p.ser(w);
+  if (C_Zr) memcpy(C_Zr, cy.b, 32);
+  return put_bytes(ctx, w, proof, cap, "poly eval prove (uni)");
 }
 
 // ---- the whole-proof provers of SNARK::prove, on host polynomials (pe_prove.hpp)
@@ -573,4 +768,83 @@ extern "C" int spg_poly_eval_verify_plain_batched_instances(spg_ctx* ctx, const 
   return tr_status(ctx, t->t,
                    pe_verify_instances(ctx, const_cast<ProverGens&>(g->g), t->t, rl, lds(Zr_list_mont, n), cl,
                                        std::vector<size_t>(num_vars_list, num_vars_list + n), proof, proof_len));
+}
+
+// ---- the disjoint-rounds and univariate forms (spg_pe_*)
+extern "C" int spg_pe_prove_disjoint(spg_ctx* ctx, const spg_poly_gens* g, const spg_buf* const* polys,
+                                     const size_t* offsets, const size_t* num_proofs_list,
+                                     const size_t* num_inputs_list, size_t n, const uint64_t* rq_mont, size_t rq_len,
+                                     const uint64_t* ry_mont, size_t ry_len, const uint64_t* Zr_list_mont,
+                                     spg_transcript* t, spg_random_tape* tape, uint8_t* proof, size_t cap,
+                                     size_t* len) {
+  if (!ctx || !t) return SPG_E_ARG;
+  HostPin pin;
+  return tr_status(ctx, t->t, prove_disjoint_impl(ctx, g, polys, offsets, num_proofs_list, num_inputs_list, n, rq_mont,
+                                                  rq_len, ry_mont, ry_len, Zr_list_mont, t, tape, proof, cap, len));
+}
+// rows and evaluation commitments of n polynomials, as the verifiers take them
+static void ld_comms(const uint8_t* C_Zr_list, const uint8_t* comms, const size_t* comm_lens, size_t n,
+                     std::vector<Pt>* cz, std::vector<std::vector<Pt>>* cl) {
+  *cz = ldpts(C_Zr_list, n);
+  cl->resize(n);
+  for (size_t i = 0, co = 0; i < n; co += comm_lens[i], i++) (*cl)[i] = ldpts(comms + 32 * co, comm_lens[i]);
+}
+extern "C" int spg_pe_verify_disjoint(spg_ctx* ctx, const spg_poly_gens* g, const size_t* num_proofs_list,
+                                      const size_t* num_inputs_list, size_t n, const uint64_t* rq_mont, size_t rq_len,
+                                      const uint64_t* ry_mont, size_t ry_len, const uint8_t* C_Zr_list,
+                                      const uint8_t* comms, const size_t* comm_lens, spg_transcript* t,
+                                      const uint8_t* proof, size_t proof_len) {
+  if (!ctx || !t || !g || !num_proofs_list || !num_inputs_list || !rq_mont || !ry_mont || !C_Zr_list || !comms ||
+      !comm_lens || !proof || n == 0)
+    return SPG_E_ARG;
+  const int rc = disjoint_args(ctx, g, num_proofs_list, num_inputs_list, n, rq_len, "poly eval verify (disjoint)");
+  if (rc) return rc;
+  SPG_HIP(ctx, hipSetDevice(ctx->device));
+  HostPin pin;
+  std::vector<Pt> cz;
+  std::vector<std::vector<Pt>> cl;
+  ld_comms(C_Zr_list, comms, comm_lens, n, &cz, &cl);
+  return tr_status(ctx, t->t,
+                   pe_verify_disjoint(ctx, const_cast<ProverGens&>(g->g), t->t,
+                                      std::vector<size_t>(num_proofs_list, num_proofs_list + n),
+                                      std::vector<size_t>(num_inputs_list, num_inputs_list + n), lds(rq_mont, rq_len),
+                                      lds(ry_mont, ry_len), cz, cl, proof, proof_len));
+}
+extern "C" int spg_pe_uni_evals(spg_ctx* ctx, const spg_buf* const* polys, const size_t* offsets,
+                                const size_t* num_vars_list, size_t n, const uint64_t* r_mont, uint64_t* Zr_out_mont) {
+  if (!ctx) return SPG_E_ARG;
+  HostPin pin;
+  return uni_evals_impl(ctx, polys, offsets, num_vars_list, n, r_mont, Zr_out_mont);
+}
+extern "C" int spg_pe_prove_uni(spg_ctx* ctx, const spg_poly_gens* g, const spg_buf* const* polys,
+                                const size_t* offsets, const size_t* num_vars_list, size_t n, const uint64_t* r_mont,
+                                const uint64_t* Zr_list_mont, spg_transcript* t, spg_random_tape* tape, uint8_t* proof,
+                                size_t cap, size_t* len, uint8_t C_Zr[32]) {
+  if (!ctx || !t) return SPG_E_ARG;
+  HostPin pin;
+  return tr_status(ctx, t->t, prove_uni_impl(ctx, g, polys, offsets, num_vars_list, n, r_mont, Zr_list_mont, t, tape,
+                                             proof, cap, len, C_Zr));
+}
+extern "C" int spg_pe_verify_uni(spg_ctx* ctx, const spg_poly_gens* g, const uint64_t* r_mont,
+                                 const uint8_t* C_Zr_list, const uint8_t* comms, const size_t* comm_lens,
+                                 const size_t* poly_sizes, size_t n, spg_transcript* t, const uint8_t* proof,
+                                 size_t proof_len) {
+  if (!ctx || !t || !g || !r_mont || !C_Zr_list || !comms || !comm_lens || !poly_sizes || !proof || n == 0)
+    return SPG_E_ARG;
+  size_t max_nv = 0;
+  for (size_t i = 0; i < n; i++) {  // nv_i = lg next_pow2(size_i), as the reference reads them
+    const size_t nv = poly_sizes[i] > ((size_t)1 << kPeMaxVars) ? kPeMaxVars + 1 : lg2(npow2(poly_sizes[i]));
+    if (!nv_ok(nv)) return set_err(ctx, SPG_E_ARG, "poly eval verify (uni): num_vars must be 1 .. 30");
+    max_nv = std::max(max_nv, nv);
+  }
+  if (rs_of(max_nv) > g->g.n_pc)
+    return set_err(ctx, SPG_E_ARG, "poly eval verify (uni): polynomial wider than the generators");
+  SPG_HIP(ctx, hipSetDevice(ctx->device));
+  HostPin pin;
+  std::vector<Pt> cz;
+  std::vector<std::vector<Pt>> cl;
+  ld_comms(C_Zr_list, comms, comm_lens, n, &cz, &cl);
+  return tr_status(ctx, t->t,
+                   pe_verify_uni(ctx, const_cast<ProverGens&>(g->g), t->t, ld_fq(r_mont), cz, cl,
+                                 std::vector<size_t>(poly_sizes, poly_sizes + n), proof, proof_len));
 }

@@ -1680,9 +1680,9 @@ extern "C" int spg_snark_verify_public(spg_ctx* ctx, const spg_snark_comp* block
                                                      proof_len));
 }
 
-// ---- PolyEvalProof::verify* one call at a time (pe_verify.hpp; the spg_poly_eval_verify* entries of polyeval.hip): the
-// Verifier members above on proof bytes. Malformed bytes, a wrong proof count, a commitment of the wrong row count and
-// a point that does not decompress are all SPG_E_VERIFY, as in the whole-proof verifiers.
+// ---- PolyEvalProof::verify* one call at a time (pe_verify.hpp; the spg_poly_eval_verify* and spg_pe_verify_* entries of
+// polyeval.hip): the Verifier members above on proof bytes. Malformed bytes, a wrong proof count, a commitment of the
+// wrong row count and a point that does not decompress are all SPG_E_VERIFY, as in the whole-proof verifiers.
 namespace spg {
 template <class Run>
 static int pe_verify_run(spg_ctx* ctx, Tr& t, const char* what, bool parsed, const Run& run) {
@@ -1724,5 +1724,27 @@ int pe_verify_instances(spg_ctx* ctx, ProverGens& g, Tr& t, const std::vector<Fq
   for (const PolyComm& c : comms) cp.push_back(&c);
   return pe_verify_run(ctx, t, "poly eval verify (instances)", !rdr.bad && rdr.o == rdr.n,
                        [&](V& v) { return v.pe_plain_batched_instances(g, ps, r_list, Zr_list, cp, nv_list); });
+}
+int pe_verify_disjoint(spg_ctx* ctx, ProverGens& g, Tr& t, const std::vector<size_t>& np_list,
+                       const std::vector<size_t>& ni_list, const FqV& rq, const FqV& ry, const std::vector<Pt>& C_Zr,
+                       const std::vector<std::vector<Pt>>& comms, const uint8_t* proof, size_t len) {
+  std::vector<DotProductProofLogP> ps;
+  Rd rdr(proof, len);
+  rd(rdr, ps);
+  std::vector<const PolyComm*> cp;
+  for (const PolyComm& c : comms) cp.push_back(&c);
+  return pe_verify_run(ctx, t, "poly eval verify (disjoint)", !rdr.bad && rdr.o == rdr.n,
+                       [&](V& v) { return v.pe_batched_disjoint(g, ps, np_list, ni_list, rq, ry, decs(C_Zr), cp); });
+}
+int pe_verify_uni(spg_ctx* ctx, ProverGens& g, Tr& t, const Fq& r, const std::vector<Pt>& C_Zr,
+                  const std::vector<std::vector<Pt>>& comms, const std::vector<size_t>& sizes, const uint8_t* proof,
+                  size_t len) {
+  DotProductProofLogP p;
+  Rd rdr(proof, len);
+  rd(rdr, p);
+  std::vector<const PolyComm*> cp;
+  for (const PolyComm& c : comms) cp.push_back(&c);
+  return pe_verify_run(ctx, t, "poly eval verify (uni)", !rdr.bad && rdr.o == rdr.n,
+                       [&](V& v) { return v.pe_uni_batched(g, p, r, decs(C_Zr), cp, sizes); });
 }
 }  // namespace spg

@@ -1400,3 +1400,100 @@ def poly_eval_verify_plain_batched_instances(ctx, gens, r_list, Zr_list, comms, 
                                                             nvs, ctypes.c_size_t(n), transcript.handle, _p(pf),
                                                             ctypes.c_size_t(len(proof)))
     return _verify_result(ctx, rc, "spg_poly_eval_verify_plain_batched_instances")
+
+
+# ---- the disjoint-rounds and univariate forms of PolyEvalProof (spg_pe_*, csrc/polyeval.hip)
+def _sizes(v):
+    return (ctypes.c_size_t * max(len(v), 1))(*v)
+
+
+def _cat_comms(C_Zr_list, comms):
+    """(C_Zr blob [n, 32], rows blob, comm_lens)"""
+    cz = [np.frombuffer(bytes(c), dtype=np.uint8) for c in C_Zr_list]
+    cms = [np.ascontiguousarray(c, dtype=np.uint8).reshape(-1, 32) for c in comms]
+    czb = np.ascontiguousarray(np.concatenate(cz)) if cz else np.zeros(32, np.uint8)
+    blob = np.ascontiguousarray(np.concatenate(cms)) if cms else np.zeros((1, 32), np.uint8)
+    if blob.size == 0:
+        blob = np.zeros((1, 32), np.uint8)
+    return czb, blob, _sizes([c.shape[0] for c in cms])
+
+
+def _scalars_or_empty(x):
+    return _scalars(x) if len(x) else np.zeros((1, 4), np.uint64)
+
+
+def pe_prove_disjoint(ctx, gens, polys, num_proofs_list, num_inputs_list, rq, ry, Zr_list, transcript, tape,
+                      offsets=None, cap=None):
+    """PolyEvalProof::prove_batched_instances_disjoint_rounds (src/dense_mlpoly.rs:861-960): polynomial i is
+    polys[i][offsets[i] : offsets[i] + num_proofs_list[i] * num_inputs_list[i]] (Bufs), opened at the last
+    lg num_proofs entries of rq followed by ry fitted to lg num_inputs entries; Zr_list [n, 4]. Returns
+    bincode(Vec<PolyEvalProof>), one proof per distinct (num_proofs, num_inputs)."""
+    n = len(polys)
+    offs = _sizes(offsets if offsets is not None else [0] * n)
+    nps, nis = _sizes(num_proofs_list), _sizes(num_inputs_list)
+    q, y, zr = _scalars_or_empty(rq), _scalars_or_empty(ry), _scalars_or_empty(Zr_list)
+    arr = _buf_array(polys)
+
+    def call(out, c, ln):
+        return lib().spg_pe_prove_disjoint(ctx.handle, gens.handle, arr, offs, nps, nis, ctypes.c_size_t(n), _p(q),
+                                           ctypes.c_size_t(len(rq)), _p(y), ctypes.c_size_t(len(ry)), _p(zr),
+                                           transcript.handle, tape.handle, out, c, ln)
+
+    return _prove_call(ctx, "spg_pe_prove_disjoint", call, cap)
+
+
+def pe_verify_disjoint(ctx, gens, num_proofs_list, num_inputs_list, rq, ry, C_Zr_list, comms, transcript, proof):
+    """PolyEvalProof::verify_batched_instances_disjoint_rounds (src/dense_mlpoly.rs:962-1044): C_Zr_list the n
+    32-byte commitments to the evaluations, comms[i] the [L_i, 32] rows of polynomial i. Returns (ok, reason)."""
+    n = len(comms)
+    q, y = _scalars_or_empty(rq), _scalars_or_empty(ry)
+    czb, blob, cl = _cat_comms(C_Zr_list, comms)
+    pf = _bytes_arr(proof)
+    rc = lib().spg_pe_verify_disjoint(ctx.handle, gens.handle, _sizes(num_proofs_list), _sizes(num_inputs_list),
+                                      ctypes.c_size_t(n), _p(q), ctypes.c_size_t(len(rq)), _p(y),
+                                      ctypes.c_size_t(len(ry)), _p(czb), _p(blob), cl, transcript.handle, _p(pf),
+                                      ctypes.c_size_t(len(proof)))
+    return _verify_result(ctx, rc, "spg_pe_verify_disjoint")
+
+
+def pe_uni_evals(ctx, polys, num_vars_list, r, offsets=None):
+    """the evaluations the univariate form opens (ShiftProofs::prove, src/lib.rs:417-418): [n, 4], row i =
+    sum_k Z_i[k] r^k over polys[i][offsets[i] : offsets[i] + 2^num_vars_list[i]]"""
+    n = len(polys)
+    offs = _sizes(offsets if offsets is not None else [0] * n)
+    out = np.zeros((max(n, 1), 4), dtype=np.uint64)
+    rr = _scalars(r)
+    ctx.check(lib().spg_pe_uni_evals(ctx.handle, _buf_array(polys), offs, _sizes(num_vars_list), ctypes.c_size_t(n),
+                                     _p(rr), _p(out)), "spg_pe_uni_evals")
+    return out[:n]
+
+
+def pe_prove_uni(ctx, gens, polys, num_vars_list, r, Zr_list, transcript, tape, offsets=None, cap=None):
+    """PolyEvalProof::prove_uni_batched_instances (src/dense_mlpoly.rs:1046-1130): every polynomial read as univariate
+    and opened at the one scalar r with the claimed values Zr_list [n, 4]. Returns (bincode(PolyEvalProof),
+    C_Zr_prime)."""
+    n = len(polys)
+    offs = _sizes(offsets if offsets is not None else [0] * n)
+    nvs = _sizes(num_vars_list)
+    rr, zr = _scalars(r), _scalars_or_empty(Zr_list)
+    arr = _buf_array(polys)
+    czr = np.zeros(32, dtype=np.uint8)
+
+    def call(out, c, ln):
+        return lib().spg_pe_prove_uni(ctx.handle, gens.handle, arr, offs, nvs, ctypes.c_size_t(n), _p(rr), _p(zr),
+                                      transcript.handle, tape.handle, out, c, ln, _p(czr))
+
+    proof = _prove_call(ctx, "spg_pe_prove_uni", call, cap)
+    return proof, czr.tobytes()
+
+
+def pe_verify_uni(ctx, gens, r, C_Zr_list, comms, poly_sizes, transcript, proof):
+    """PolyEvalProof::verify_uni_batched_instances (src/dense_mlpoly.rs:1132-1203): poly_sizes as the reference takes
+    them (num_vars_i = lg next_pow2(size_i)). Returns (ok, reason)."""
+    n = len(comms)
+    rr = _scalars(r)
+    czb, blob, cl = _cat_comms(C_Zr_list, comms)
+    pf = _bytes_arr(proof)
+    rc = lib().spg_pe_verify_uni(ctx.handle, gens.handle, _p(rr), _p(czb), _p(blob), cl, _sizes(poly_sizes),
+                                 ctypes.c_size_t(n), transcript.handle, _p(pf), ctypes.c_size_t(len(proof)))
+    return _verify_result(ctx, rc, "spg_pe_verify_uni")
