@@ -13,6 +13,7 @@
 #include "comm.hpp"
 #include "ctx.hpp"
 #include "hpool.hpp"
+#include "knobs.hpp"
 
 namespace spg {
 
@@ -123,7 +124,7 @@ struct Uploader {
     src = s;
     bytes = n;
     // about two chunks per worker, 256 KB .. 4 MB, 64 KB multiples
-    static const size_t fixed = getenv("SPG_H2D_CHUNK_KB") ? (size_t)atol(getenv("SPG_H2D_CHUNK_KB")) << 10 : 0;
+    const size_t fixed = (size_t)knob::h2d_chunk_kb() << 10;
     const size_t want = (n / (2 * lanes.size()) + 65535) & ~(size_t)65535;
     ch = fixed ? std::min(kUpChunk, fixed) : std::min(kUpChunk, std::max<size_t>((size_t)256 << 10, want));
     err = 0;
@@ -162,15 +163,13 @@ int h2d_stream(spg_ctx* c, void* dst, const void* src, size_t bytes) {
   // returns once the caller's bytes are staged). SPG_H2D=1: the upload workers below -- as fast when they run, but 8 more
   // busy threads beside the pool's spinning workers pass the job's CPU quota and the process is throttled for ~9 ms at
   // a time (scripts/upload_probe.py, profiles/r06_upload_probe.txt: 268 MB in 4.7 ms either way, 13-80 ms with stalls)
-  static const bool on = getenv("SPG_H2D") && atoi(getenv("SPG_H2D")) != 0;
-  if (!on) {
+  if (!knob::h2d()) {
     SPG_HIP(c, hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
     return 0;
   }
   if (!c->up) {
     // 8 workers (measured best on the box: 4 / 8 / 16 -> 44 / 50 / 45 GB/s), fewer under a smaller CPU share
-    static const int T0 = getenv("SPG_H2D_THREADS") ? atoi(getenv("SPG_H2D_THREADS")) : 8;
-    const int T = std::max(1, std::min(T0, usable_cpus()));
+    const int T = std::max(1, std::min(knob::h2d_threads(), usable_cpus()));
     c->up = new Uploader();
     if (int rc = c->up->start(c->device, T)) {
       delete c->up;
@@ -178,7 +177,7 @@ int h2d_stream(spg_ctx* c, void* dst, const void* src, size_t bytes) {
       return set_err(c, rc, "upload workers");
     }
   }
-  static const bool trace = getenv("SPG_H2D_TRACE") != nullptr;
+  const bool trace = knob::h2d_trace();
   const auto t0 = std::chrono::steady_clock::now();
   if (int rc = c->up->run((uint8_t*)dst, (const uint8_t*)src, bytes)) return set_err(c, rc, "streamed upload");
   if (trace)
@@ -238,8 +237,7 @@ void dev_cache_put(spg_ctx* c, void* p, size_t bytes) {
 }
 
 void* mapped_get(spg_ctx* c, size_t bytes, void** dev) {
-  static const bool on = !getenv("SPG_MAPPED_BUCKETS") || atoi(getenv("SPG_MAPPED_BUCKETS")) != 0;
-  if (!on) return nullptr;
+  if (!knob::mapped_buckets()) return nullptr;
   if (bytes > c->mapped_bytes) {
     if (c->mapped) {
       hipStreamSynchronize(c->stream);
@@ -300,9 +298,8 @@ void* ws_get(spg_ctx* c, size_t slot, size_t bytes) {
 }
 
 bool failpoint(const spg_ctx* c, const char* site) {
-  static const char* fp = getenv("SPG_FAILPOINT");
-  static const int fr = getenv("SPG_FAILPOINT_RANK") ? atoi(getenv("SPG_FAILPOINT_RANK")) : 0;
-  return fp && strcmp(fp, site) == 0 && c->rank == fr;
+  const char* fp = knob::failpoint();
+  return fp && strcmp(fp, site) == 0 && c->rank == knob::failpoint_rank();
 }
 
 int mbox_wait(spg_ctx* ctx, uint32_t seq, Fq* out, int n) {
@@ -455,8 +452,7 @@ std::vector<int> choose_pool_cpus(int device) {
   // one process alone: the least busy domain first. Several processes of one node started together (torchrun,
   // LOCAL_WORLD_SIZE > 1) would sample each other's start-up load, so they order the domains by core number
   // instead, which every process sees alike, and each takes the entry at its local rank: distinct domains
-  const char* lws = getenv("LOCAL_WORLD_SIZE");
-  if (lws && atoi(lws) > 1)
+  if (knob::local_world_size() > 1)
     std::stable_sort(cand.begin(), cand.end(), [](const std::pair<double, std::vector<int>>& a,
                                                   const std::pair<double, std::vector<int>>& b) { return a.second[0] < b.second[0]; });
   else
@@ -464,8 +460,7 @@ std::vector<int> choose_pool_cpus(int device) {
                                                   const std::pair<double, std::vector<int>>& b) { return a.first < b.first; });
   // torchrun: one process per GPU, or several sharing one in rehearsals. Without LOCAL_RANK the least busy domain:
   // a prover started next to a running one sees that one's spinning workers in the sample and goes elsewhere
-  const char* lr = getenv("LOCAL_RANK");
-  const size_t slot = lr ? (size_t)atoi(lr) : 0;
+  const size_t slot = (size_t)knob::local_rank();
   return cand[slot % cand.size()].second;
 }
 
@@ -484,8 +479,7 @@ void print_copy_counts() {
 }
 hipError_t memcpy_traced(void* dst, const void* src, size_t n, hipMemcpyKind k, hipStream_t s, const char* file,
                          int line) {
-  static const bool on = getenv("SPG_COPY_TRACE") && atoi(getenv("SPG_COPY_TRACE")) != 0;
-  if (on) {
+  if (knob::copy_trace()) {
     static std::mutex mu;
     std::lock_guard<std::mutex> lk(mu);
     const char* f = strrchr(file, '/');
@@ -540,8 +534,7 @@ extern "C" int spg_init(int device, spg_ctx** out) {
   // SPG_PIN (default on): the host pool's workers (created on first use) on one L3 domain (CCD) local to the GPU, the
   // least busy one (spg::choose_pool_cpus); the calling thread joins them only inside prover calls (spg::HostPin)
   // and keeps its own affinity otherwise
-  const char* pin = getenv("SPG_PIN");
-  if ((!pin || atoi(pin) != 0) && spg::pool_cpus().empty()) {
+  if (spg::knob::pin() && spg::pool_cpus().empty()) {
     std::vector<int> cpus = spg::choose_pool_cpus(device);
     if (!cpus.empty()) spg::pool_cpus() = cpus;
   }

@@ -27,6 +27,7 @@
 #include "hcurve.hpp"
 #include "hvec.hpp"
 #include "hpool.hpp"
+#include "knobs.hpp"
 #include "lds.hpp"
 #include "quad.hpp"
 
@@ -39,8 +40,7 @@ namespace spg {
 // sets both.
 static constexpr size_t kCombSmall = 1024;
 static int comb_c(size_t slots) {
-  static const int c = getenv("SPG_COMB_C") ? std::max(10, std::min(13, atoi(getenv("SPG_COMB_C")))) : 0;
-  return c ? c : (slots <= kCombSmall ? 13 : 12);
+  return knob::comb_c() ? knob::comb_c() : (slots <= kCombSmall ? 13 : 12);
 }
 static constexpr int kCombRun = 64;                 // multiples per build lane
 static constexpr size_t kCombMaxR = 65536;          // most generators a table covers
@@ -51,10 +51,8 @@ static constexpr size_t kCombBig = 16384;           // tables of this many gener
 // take c = 13 (SPG_COMB_C_BIG: 12 or 13): 20 windows instead of 22, so 9 % fewer mixed additions per scalar, for a
 // 129 GB table instead of 70 GB; where that does not fit (cap, free HBM) the table falls back to c = 12
 static int comb_c_for(size_t slots) {
-  static const int cw = getenv("SPG_COMB_C_WIDE") ? std::max(9, std::min(10, atoi(getenv("SPG_COMB_C_WIDE")))) : 9;
-  static const int cb = getenv("SPG_COMB_C_BIG") ? std::max(12, std::min(13, atoi(getenv("SPG_COMB_C_BIG")))) : 13;
-  if (slots > kCombWide) return cw;
-  if (slots == kCombBig && !getenv("SPG_COMB_C")) return cb;
+  if (slots > kCombWide) return knob::comb_c_wide();
+  if (slots == kCombBig && !knob::comb_c_is_set()) return knob::comb_c_big();
   return comb_c(slots);
 }
 
@@ -220,10 +218,7 @@ void comb_free(const spg_gens* g) {
   g->comb = spg_gens::Comb();
 }
 
-static bool comb_enabled() {
-  static const bool on = !getenv("SPG_COMB") || atoi(getenv("SPG_COMB")) != 0;
-  return on;
-}
+static bool comb_enabled() { return knob::comb(); }
 
 // returns 0 with *use = a table covering generators [0, need) and h = hgen (hgen < 0: no blinds, any h slot); 1 when
 // the comb path does not apply here (disabled, too wide, over the memory cap, allocation refused, or a table for
@@ -249,15 +244,15 @@ static int comb_ensure(spg_ctx* ctx, const spg_gens* g, size_t need, int hgen, s
   // the device keeps kCombHeadroom free beside it, so co-located provers (several processes on one GPU) cannot starve
   // each other's workspaces into SPG_E_NOMEM: a table that does not fit at the preferred width tries 12,
   // and one that does not fit at all leaves the rows on the buckets
-  static const bool cap_set = getenv("SPG_COMB_GB") != nullptr;
-  static const size_t cap = (size_t)(cap_set ? atof(getenv("SPG_COMB_GB")) : 144.0) * (1ull << 30);
+  const bool cap_set = knob::comb_gb_is_set();
+  const size_t cap = knob::comb_gb();
   // entries padded to one 128-byte line each (SPG_COMB_PAD, default on) where the padded table fits: a 96-byte entry
   // gathered at random straddles two lines two times in three (~2x the algorithmic bytes, PMC-measured)
   // Padded tables up to SPG_COMB_PAD_GB (default 64: the 1024-generator tables, 5.9 GB, and config 2's 2^16-generator
   // one, 62 GB); larger ones stay packed -- the config-5 derefs tables run at the madd peak already, and a 93 GB padded
   // 12-bit fallback beside another process's table left two ranks sharing one GPU without room for their workspaces
-  static const bool pad_on = !getenv("SPG_COMB_PAD") || atoi(getenv("SPG_COMB_PAD")) != 0;
-  static const size_t pad_max = (size_t)(getenv("SPG_COMB_PAD_GB") ? atof(getenv("SPG_COMB_PAD_GB")) : 64.0) * (1ull << 30);
+  const bool pad_on = knob::comb_pad();
+  const size_t pad_max = knob::comb_pad_gb();
   auto table_bytes = [&](int c, int st) { return (size_t)(253 / c + 1) * NS * ((size_t)1 << (c - 1)) * 32 * st; };
   auto fits = [&](size_t bytes) {
     if (g_comb_bytes.load() + bytes > cap) return false;
@@ -376,10 +371,9 @@ int msm_comb(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const Fq* d_sca
   if (rc == 1) return kCombSkip;
   if (rc) return rc;
   const size_t per = n + (d_blinds ? 1 : 0);
-  static const size_t want = getenv("SPG_COMB_WGS") ? (size_t)atol(getenv("SPG_COMB_WGS")) : 2048;
+  const size_t want = (size_t)knob::comb_wgs();
   // window groups per scalar: few rows get up to 4 lanes per scalar (>= 2^17 lanes when there are that few)
-  static const size_t gmax = getenv("SPG_COMB_GMAX") ? (size_t)atol(getenv("SPG_COMB_GMAX")) : 4;
-  static const size_t gmin = getenv("SPG_COMB_GMIN") ? (size_t)atol(getenv("SPG_COMB_GMIN")) : 1;
+  const size_t gmax = (size_t)knob::comb_gmax(), gmin = (size_t)knob::comb_gmin();
   size_t G = gmin == 2 || gmin == 4 ? gmin : 1;
   while (G < gmax && G < 4 && B * per * G < ((size_t)1 << 17)) G *= 2;
   const size_t spw = 256 / G;
@@ -436,7 +430,7 @@ int msm_single_comb(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const Fq
   if (rc) return rc;
   const size_t per = n + (d_blind ? 1 : 0);
   // window groups per scalar (a lane's chain is W / G mixed additions) and workgroups: ~4 waves per SIMD
-  static const size_t gsel = getenv("SPG_BIG_COMB_G") ? (size_t)atol(getenv("SPG_BIG_COMB_G")) : 2;
+  const size_t gsel = (size_t)knob::big_comb_g();
   const size_t G = gsel == 1 || gsel == 2 ? gsel : 4, spw = 256 / G;
   const size_t S = std::max<size_t>(1, (per + spw - 1) / spw);
   void* d_map = nullptr;
@@ -472,7 +466,7 @@ int msm_single_comb(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const Fq
   SPG_HIP(ctx, hipGetLastError());
   SPG_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // the S parts over the pool: contiguous chunks (8-lane IFMA sums where the CPU has them), then their sums here
-  static const bool vec = h::ifma_on() && !(getenv("SPG_VEC_MIN") && atol(getenv("SPG_VEC_MIN")) == 0);
+  const bool vec = h::ifma_on() && knob::vec_min() != 0;
   const int K = (int)std::max<size_t>(1, std::min<size_t>(S / (vec ? 64 : 16), (size_t)pool().size() + 1));
   std::vector<h::HExt> part(K);
   pool().parallel_for(K, [&](int c) {

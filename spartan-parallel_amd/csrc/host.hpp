@@ -23,6 +23,7 @@
 #include "hvec.hpp"
 #include "hpool.hpp"
 #include "keccak.hpp"
+#include "knobs.hpp"
 
 namespace spg {
 
@@ -273,12 +274,11 @@ struct HostGens {
     const size_t threads = (size_t)pool().size() + 1;
     // >= 64 units per slice: with the IFMA sums a slice's run is cheap, and fewer slices mean less burst hand-off
     // (2-rep A/B, SNARK median ms: 8: 16.91 / 16.80, 32: 16.79 / 16.26, 64: 16.32 / 16.38)
-    static const size_t min_slice = getenv("SPG_SLICE_MIN") ? (size_t)atol(getenv("SPG_SLICE_MIN")) : 64;
+    const size_t min_slice = (size_t)knob::slice_min();
     // several small jobs (a DotProductProof's Cy and beta: 96 units) get a slice each, so their encodings (~2.4 us
     // inverse square roots) run side by side instead of one after another on the calling thread (SPG_ENC_SPLIT=0: off)
-    static const bool enc_split = !getenv("SPG_ENC_SPLIT") || atoi(getenv("SPG_ENC_SPLIT")) != 0;
     size_t S = std::max<size_t>(1, std::min(threads, U / min_slice));
-    const bool per_job = enc_split && J > S && J <= threads;
+    const bool per_job = knob::enc_split() && J > S && J <= threads;
     if (per_job) S = J;  // slice s = job s
     auto slice_lo = [&](size_t s) { return per_job ? 32 * tfirst[s] : U * s / S; };
     // slices touching job j: [sfirst[j], slast[j]]
@@ -308,10 +308,10 @@ struct HostGens {
     // ahead is prefetched while this one is added: a small DotProductProofLog's rounds read ~1000 random entries of
     // ~1 MB tables per generator, which mostly miss the caches (host-path proofs 1.63 -> 0.98 ms per SNARK::prove in
     // situ, session r03zm; a standalone micro with warm tables showed no gain). SPG_HOST_PREFETCH=0: off.
-    static const size_t kPf = getenv("SPG_HOST_PREFETCH") ? (size_t)atol(getenv("SPG_HOST_PREFETCH")) : 3;
+    const size_t kPf = (size_t)knob::host_prefetch();
     // with AVX-512 IFMA a job's run of at least kVecMin units goes through the 8-lane sums (hvec.hpp): the entries of
     // its nonzero bytes, 8 accumulators, one reduction (SPG_VEC_MIN: the threshold; 0 = never)
-    static const size_t kVecMin = getenv("SPG_VEC_MIN") ? (size_t)atol(getenv("SPG_VEC_MIN")) : 16;
+    const size_t kVecMin = (size_t)knob::vec_min();
     const bool vec = kVecMin && h::ifma_on();
     pool().parallel_for((int)S, [&](int si) {
       const size_t s = (size_t)si, u0 = slice_lo(s), u1 = slice_lo(s + 1);

@@ -16,6 +16,7 @@
 #include "hostmath.hpp"
 #include "hpool.hpp"
 #include "keccak.hpp"
+#include "knobs.hpp"
 #include "pe_plan.hpp"
 #include "snark_shape.hpp"
 #include "vmsm.hpp"
@@ -498,6 +499,37 @@ long spgh_pe_plan_uni(int per_term, size_t n, const size_t* nv_list, size_t* ter
   }
   tot[0] = p.part_len, tot[1] = p.out_len, tot[2] = p.xblocks, tot[3] = pe_proof_bytes(p.R_size), tot[4] = p.R_size;
   return (long)p.terms.size();
+}
+
+// The environment table (knobs.hpp) as text, one row per line: name, kind, default, lo, hi (the clamp; "-": none),
+// live (0 / 1), description, tab separated. Writes at most cap bytes and returns the length of the whole text.
+size_t spgh_knob_table(char* buf, size_t cap) {
+  auto bound = [](long v) { return v == knob::kNoLo || v == knob::kNoHi ? std::string("-") : std::to_string(v); };
+  std::string s;
+  for (const knob::Row& r : knob::table())
+    s += std::string(r.name) + "\t" + r.kind + "\t" + r.dflt + "\t" + bound(r.lo) + "\t" + bound(r.hi) + "\t" +
+         (r.live ? "1" : "0") + "\t" + r.desc + "\n";
+  if (cap) memcpy(buf, s.data(), std::min(cap, s.size()));
+  return s.size();
+}
+// The parse rule of one kind (knobs.hpp) on text (NULL: unset), with no environment involved. dflt[3], out[3]: the
+// COSTS triple, else entry 0 alone (bools as 0 / 1, GB in bytes, STR: 1 when the text itself came back). Returns 0, or
+// -1 for a kind the table does not know
+int spgh_knob_parse(const char* kind, const char* text, const double* dflt, long lo, long hi, double* out) {
+  const std::string k = kind;
+  if (k == "ON") out[0] = knob::parse_on(text, dflt[0] != 0, lo, hi);
+  else if (k == "OFF") out[0] = knob::parse_off(text, dflt[0] != 0, lo, hi);
+  else if (k == "PRESENT") out[0] = knob::parse_present(text, dflt[0] != 0, lo, hi);
+  else if (k == "INT") out[0] = knob::parse_int(text, (int)dflt[0], lo, hi);
+  else if (k == "LONG") out[0] = (double)knob::parse_long(text, (long)dflt[0], lo, hi);
+  else if (k == "GB") out[0] = (double)knob::parse_gb(text, dflt[0], lo, hi);
+  else if (k == "STR") out[0] = text && knob::parse_str(text, nullptr, lo, hi) == text;
+  else if (k == "COSTS") {
+    const knob::StepCosts c = knob::parse_costs(text, knob::StepCosts{{(int)dflt[0], (int)dflt[1], (int)dflt[2]}}, lo, hi);
+    for (int i = 0; i < 3; i++) out[i] = c.c[i];
+  } else
+    return -1;
+  return 0;
 }
 
 }  // extern "C"

@@ -14,6 +14,7 @@
 #include "ctx.hpp"
 #include "host.hpp"
 #include "hostmath.hpp"
+#include "knobs.hpp"
 #include "sumcheck.hpp"
 
 namespace spg {
@@ -64,8 +65,7 @@ inline void axpy_pool(const std::vector<Axpy>& jobs) {
     n = std::max(n, m);
   }
   // (1024 products are ~25 us on one core, a burst ~3; SPG_AXPY_POOL=0: always on the calling thread)
-  static const bool on = !getenv("SPG_AXPY_POOL") || atoi(getenv("SPG_AXPY_POOL")) != 0;
-  const int C = on && work >= 1024 ? 8 : 1;
+  const int C = knob::axpy_pool() && work >= 1024 ? 8 : 1;
   pool().parallel_for(C, [&](int ch) {
     const size_t lo = n * ch / C, hi = n * (ch + 1) / C;
     for (const Axpy& j : jobs) {
@@ -79,7 +79,7 @@ inline void axpy_pool(const std::vector<Axpy>& jobs) {
 
 struct Laps {  // SPG_TRACE=1: wall-time breakdown of a host orchestration
   const char* title = "R1CSProof::prove";
-  bool on = getenv("SPG_TRACE") != nullptr;
+  bool on = knob::trace_is_set();
   std::chrono::steady_clock::time_point t = std::chrono::steady_clock::now();
   std::vector<std::pair<std::string, double>> acc;
   void lap(const char* name) {
@@ -89,8 +89,7 @@ struct Laps {  // SPG_TRACE=1: wall-time breakdown of a host orchestration
     t = now;
     // SPG_TRACE_EVENTS=1: every lap's end on stderr with its CLOCK_MONOTONIC time (the clock of rocprofv3's kernel
     // trace), so scripts/kernel_gaps.py can name the host phase behind each idle gap of the device
-    static const bool ev = getenv("SPG_TRACE_EVENTS") != nullptr;
-    if (ev)
+    if (knob::trace_events())
       fprintf(stderr, "[spgev] %lld %s:%s %.1f\n",
               (long long)std::chrono::duration_cast<std::chrono::nanoseconds>(now.time_since_epoch()).count(), title,
               name, us);

@@ -30,6 +30,8 @@
 #include <pthread.h>
 #include <sched.h>
 
+#include "knobs.hpp"
+
 namespace spg {
 
 // CPUs the pool should live on (set by spg_init from the GPU's NUMA-local CPU list when SPG_PIN=1): the caller
@@ -80,8 +82,8 @@ inline int usable_cpus() {
     }
     fclose(f);
   }
-  const char* lws = getenv("LOCAL_WORLD_SIZE");
-  if (lws && atoi(lws) > 1) n = std::max(1, n / atoi(lws));
+  const int lws = knob::local_world_size();
+  if (lws > 1) n = std::max(1, n / lws);
   return n < 1 ? 1 : n;
 }
 
@@ -91,8 +93,7 @@ class Pool {
   // sleeps publish_delay_us between storing a burst's function/count and opening it
   explicit Pool(int nthreads, int snapshot_delay_us = 0, int publish_delay_us = 0)
       : delay_us_(snapshot_delay_us), pub_delay_us_(publish_delay_us) {
-    const char* e = getenv("SPG_POOL_SPIN_US");
-    spin_ = std::chrono::microseconds(e ? atoi(e) : 20000);
+    spin_ = std::chrono::microseconds(knob::pool_spin_us());
     const std::vector<int> cpus = pool_cpus();
     for (int i = 0; i < nthreads; i++)
       threads_.emplace_back([this, cpus, i] {
@@ -214,8 +215,7 @@ class Pool {
 
 // workers besides the calling thread
 inline int pool_threads() {
-  const char* e = getenv("SPG_POOL_THREADS");
-  if (e) return atoi(e);
+  if (knob::pool_threads_is_set()) return knob::pool_threads();
   // at most 7 workers + the caller: measured best on the GPU box (16-CPU quota per process; 15 workers were
   // 2-5 ms slower per SNARK::prove, scripts/pool_sweep.sh), and it leaves room for HIP's own threads; fewer
   // when the process' share of CPUs (usable_cpus) is smaller, so co-located provers do not oversubscribe

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "hcurve.hpp"
+#include "knobs.hpp"
 
 namespace spg {
 namespace h {
@@ -28,8 +29,7 @@ namespace h {
 // SPG_HOST_IFMA=0: the scalar additions everywhere
 inline bool ifma_on() {
   static const bool on = __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512ifma") &&
-                         __builtin_cpu_supports("avx512dq") &&
-                         !(getenv("SPG_HOST_IFMA") && atoi(getenv("SPG_HOST_IFMA")) == 0);
+                         __builtin_cpu_supports("avx512dq") && knob::host_ifma();
   return on;
 }
 

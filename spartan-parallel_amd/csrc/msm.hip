@@ -27,6 +27,7 @@
 #include "hcurve.hpp"
 #include "host.hpp"
 #include "keccak.hpp"
+#include "knobs.hpp"
 #include "lds.hpp"
 #include "bullet.hpp"
 #include "quad.hpp"
@@ -284,10 +285,7 @@ static inline double madds_model(double scalars, int c) {
   return scalars * (double)(253 / c + 1) * (1.0 - 1.0 / (double)(1 << c));
 }
 
-static bool use_quad() {
-  static const bool on = !getenv("SPG_SMSM_QUAD") || atoi(getenv("SPG_SMSM_QUAD")) != 0;
-  return on;
-}
+static bool use_quad() { return knob::smsm_quad(); }
 
 // one 256-thread block per MSM. Segment j (bucket values j*m+1 .. j*m+m) contributes
 // T_j + j*m*S_j. Thread t folds the g = S/256 consecutive segments [t*g, t*g+g) into
@@ -627,9 +625,7 @@ int bullet_round_device(spg_ctx* ctx, const spg_gens* g, const Fq* aa_in, const 
 // the comb form's launch shape by MSM size P = n / 2: G quads per scalar (window groups of ceil(22 / G)), BS threads,
 // R points per workgroup (SPG_BCOMB_G / SPG_BCOMB_BS / SPG_BCOMB_R override, for A/B runs)
 static void bullet_comb_shape(int P, int* G, int* BS, int* R) {
-  static const int eg = getenv("SPG_BCOMB_G") ? atoi(getenv("SPG_BCOMB_G")) : 0;
-  static const int ebs = getenv("SPG_BCOMB_BS") ? atoi(getenv("SPG_BCOMB_BS")) : 0;
-  static const int er = getenv("SPG_BCOMB_R") ? atoi(getenv("SPG_BCOMB_R")) : 0;
+  const int eg = knob::bcomb_g(), ebs = knob::bcomb_bs(), er = knob::bcomb_r();
   // same-box A/Bs on the 2^20 SNARK (Bullet device ms per prove; profiles/r04_ab_bullet_shapes.txt): G 4 -> 8 at
   // P = 512: 1.92 -> 1.88; G 8 -> 11 (two dependent quad additions per quad): 1.87 -> 1.81; R 4 -> 8 (one tree level
   // fewer, twice the host-summed parts): 1.89 -> 1.74, R = 16: 1.85
@@ -647,8 +643,7 @@ static void bullet_comb_shape(int P, int* G, int* BS, int* R) {
   if (er >= 1 && er <= *BS / 4 && (er & (er - 1)) == 0) *R = er;
   // the last rounds (P <= SPG_BCOMB_NOTREE): every quad its own part, no LDS tree (one level is a full quad addition,
   // ~2.1 us on the round's latency path, scripts/micro/bullet_comb_phases) for at most 2 x 16 parts per MSM
-  static const int notree = getenv("SPG_BCOMB_NOTREE") ? atoi(getenv("SPG_BCOMB_NOTREE")) : 0;
-  if (P <= notree) *R = *BS / 4;
+  if (P <= knob::bcomb_notree()) *R = *BS / 4;
   // at most kBulletPartsMax parts per MSM (the host staging): fewer points per workgroup for the largest proofs
   const int wgs = (P * *G + *BS / 4 - 1) / (*BS / 4);
   while (*R > 1 && wgs * *R > kBulletPartsMax) *R /= 2;
@@ -658,8 +653,7 @@ int bullet_round_comb(spg_ctx* ctx, const spg_gens* g, const Fq* aa_in, const Fq
                       const uint32_t* gidx, size_t gmax, const Fq& u, const Fq& uinv, int k, int n, int nk,
                       Ext* d_parts, uint32_t* seq_out, int* per_msm) {
   SPG_CHECK(ctx, n >= 2 && (n & (n - 1)) == 0 && nk >= 2 && nk <= n && (n % nk) == 0, "bullet round: bad sizes");
-  static const bool on = !getenv("SPG_BULLET_COMB") || atoi(getenv("SPG_BULLET_COMB")) != 0;
-  if (!on) return 1;
+  if (!knob::bullet_comb()) return 1;
   spg_gens::Comb cb;
   const int rc = comb_get(ctx, g, gmax, &cb);
   if (rc) return rc == 1 ? 1 : rc;
@@ -715,8 +709,7 @@ int bullet_delta_scalars(spg_ctx* ctx, const Fq* cw, int n, const Fq& d, const F
 
 int comb_msm_parts(spg_ctx* ctx, const spg_gens* g, const Fq* d_scalars, const uint32_t* d_idx, size_t gmax, int n,
                    int B, Ext* d_parts, int* per_msm) {
-  static const bool on = !getenv("SPG_BULLET_COMB") || atoi(getenv("SPG_BULLET_COMB")) != 0;
-  if (!on || n < 1) return 1;
+  if (!knob::bullet_comb() || n < 1) return 1;
   spg_gens::Comb cb;
   const int rc = comb_get(ctx, g, gmax, &cb);
   if (rc) return rc == 1 ? 1 : rc;
@@ -800,11 +793,8 @@ __global__ void __launch_bounds__(1024) k_smsm_final_q(const Ext* __restrict__ b
 }
 
 static int pick_small_window(size_t per) {
-  const char* e = getenv("SPG_SMSM_C");
-  if (e) {
-    int c = atoi(e);
-    if (c >= 4 && c <= 9) return c;
-  }
+  const int forced = knob::smsm_c();  // (re-read on every call: scripts/perf_small_msm.py sweeps it in one process)
+  if (forced >= 4 && forced <= 9) return forced;
   // measured on MI355X (scripts/perf_small_msm.py): n = 130 -> c = 7, n = 4098 -> c = 8; the compacted
   // Bullet MSMs (n/2 + 2 = 514 scalars) finish on the host, where 64 buckets per MSM are cheaper than 128
   // (scripts/ab_env.sh SPG_SMSM_C "7 0": 39.7 vs 39.9-40.9 ms per SNARK::prove)
@@ -920,7 +910,7 @@ int msm_small_compressed(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, con
                          uint8_t* d_out) {
   Ext* d_ext = (Ext*)ws_get(ctx, 15, B * sizeof(Ext) + 64);
   if (!d_ext) return set_err(ctx, SPG_E_NOMEM, "small msm output");
-  static const bool trace3 = getenv("SPG_TRACE") && atoi(getenv("SPG_TRACE")) >= 3;
+  const bool trace3 = knob::trace() >= 3;
   hipEvent_t e[3];
   if (trace3) {
     for (auto& x : e) hipEventCreate(&x);
@@ -1023,8 +1013,8 @@ int msm_batch_device(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const F
   const size_t nkeys = B * (size_t)NB;
   const size_t per = n + (d_blinds ? 1 : 0);
   const size_t max_entries = B * per * (size_t)W;
-  static const int item_k = getenv("SPG_ITEM_K") ? std::max(1, atoi(getenv("SPG_ITEM_K"))) : kItemK;
-  static const int seg_m = getenv("SPG_SEG_M") ? std::max(1, atoi(getenv("SPG_SEG_M"))) : kSegM;
+  static_assert(knob::item_k_dflt == kItemK && knob::seg_m_dflt == kSegM, "knobs.hpp defaults");
+  const int item_k = knob::item_k(), seg_m = knob::seg_m();
   const size_t max_items = max_entries / item_k + nkeys + 1;
   SPG_CHECK(ctx, max_entries < 0x7fffffffULL, "msm batch too large");
   SPG_CHECK(ctx, (size_t)kTableRows * (g->n + 1) < 0x7fffffffULL, "generator table too large");
@@ -1048,8 +1038,7 @@ int msm_batch_device(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const F
 
   // many MSMs: one workgroup per MSM sorts its digits in LDS (k_digits_rows; up to 2^15 bucket counters,
   // 128 KiB of the 160 KiB LDS, at c = 16)
-  static const int rows_cmax = getenv("SPG_ROWS_CMAX") ? atoi(getenv("SPG_ROWS_CMAX")) : 16;
-  const bool rows = B >= 64 && c <= rows_cmax;
+  const bool rows = B >= 64 && c <= knob::rows_cmax();
   if (rows) {
     SPG_HIP(ctx, hipMemsetAsync(hist + nkeys, 0, 4, s));
   } else {
@@ -1105,8 +1094,7 @@ int msm_batch_device(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const F
   }
   {
     KScope ks(ctx, "msm_segments");
-    static const size_t seg_quad_max = getenv("SPG_SEG_QUAD_MAX") ? atol(getenv("SPG_SEG_QUAD_MAX")) : 16384;
-    if (use_quad() && B * (size_t)S <= seg_quad_max)
+    if (use_quad() && B * (size_t)S <= (size_t)knob::seg_quad_max())
       hipLaunchKernelGGL(k_segments_q, dim3((unsigned)((4 * B * S + 255) / 256)), dim3(256), 0, s, item_off, partial,
                          segT, segS, (int)B, NB, m);
     else
@@ -1138,8 +1126,8 @@ int msm_batch_device(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const F
       }
       // many MSMs fill the chip with blocks: fewer slots per MSM do less redundant scan work (the Hillis-Steele
       // scan costs SL log SL additions), few MSMs need the shortest dependent chain
-      static const int sl_env = getenv("SPG_FINAL_SL") ? atoi(getenv("SPG_FINAL_SL")) : 0;
-      const int sl = sl_env ? sl_env : (B >= 256 ? 32 : 128);  // B = 1024 rows: 414 -> 155 us (MI355X)
+      // (B = 1024 rows: 414 -> 155 us, MI355X)
+      const int sl = knob::final_sl() ? knob::final_sl() : (B >= 256 ? 32 : 128);
       if (sl == 32)
         hipLaunchKernelGGL(k_final_q<32>, dim3((unsigned)B), dim3(128), 0, s, fT, fS, nullptr, fSn, flog2m, ext);
       else if (sl == 64)
@@ -1284,10 +1272,7 @@ namespace spg {
 int msm_single_big(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const Fq* d_scalars, size_t n,
                    const Fq* d_blind, h::HExt* out);
 }  // namespace spg
-static bool use_big() {
-  static const bool on = !getenv("SPG_MSM_BIG") || atoi(getenv("SPG_MSM_BIG")) != 0;
-  return on;
-}
+static bool use_big() { return knob::msm_big(); }
 
 static int msm_host(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const uint64_t* scalars, size_t n, size_t B,
                     const uint64_t* blinds, uint8_t* out) {
@@ -1446,7 +1431,7 @@ extern "C" int spg_commit_rows(spg_ctx* ctx, const spg_gens* g, const uint64_t* 
 // inverse square roots; else msm_batch_device's device encodings, downloaded. SPG_HALVED_ENC=0: always the latter.
 int spg::msm_rows_host_enc(spg_ctx* ctx, const spg_gens* g, const Fq* d_scalars, size_t n, size_t B,
                            const Fq* d_blinds, long h_index, uint8_t* out, bool timed) {
-  static const bool halve = !getenv("SPG_HALVED_ENC") || atoi(getenv("SPG_HALVED_ENC")) != 0;
+  const bool halve = knob::halved_enc();
   hipStream_t s = ctx->stream;
   const size_t tot = B * (n + (d_blinds ? 1 : 0));
   const bool comb = B >= 64 && (n <= 1024 ? tot >= ((size_t)1 << 14) : (n <= 16384 && tot >= ((size_t)1 << 22)));

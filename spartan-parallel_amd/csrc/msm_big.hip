@@ -27,6 +27,7 @@
 
 #include "ctx.hpp"
 #include "hcurve.hpp"
+#include "knobs.hpp"
 #include "quad.hpp"
 
 namespace spg {
@@ -285,8 +286,7 @@ __global__ void __launch_bounds__(kBigBS, 4) k_big_accum(const Chunk* __restrict
 int big_window() {
   // c = 11 (1024 buckets, 24 windows): measured best for 2^16 points against 12 and 13 (session r03d); a
   // smaller bucket set shortens the group reductions at the end more than its extra windows cost
-  static const int c = getenv("SPG_BIG_C") ? atoi(getenv("SPG_BIG_C")) : 11;
-  return c < 8 ? 8 : (c > 14 ? 14 : c);
+  return knob::big_c();  // (the row clamps it to 8 .. 14)
 }
 
 template <int C>
@@ -295,7 +295,7 @@ int launch_big(spg_ctx* ctx, const spg_gens* g, BigArgs a, Ext* host_groups_dev,
   constexpr int NB = 1 << (C - 1);
   hipStream_t s = ctx->stream;
   const size_t E = (size_t)a.per * W;
-  static const bool lane = !getenv("SPG_BIG_ITEMS") || atoi(getenv("SPG_BIG_ITEMS")) != 0;
+  const bool lane = knob::big_items();
   // chunk size: the mean bucket load rounded up to whole passes of the 64 quads (random scalars: about one chunk per
   // bucket), at least 2 entries per quad; the lane form takes up to 8 entries per lane (a bucket with more -- skewed
   // scalars -- splits into several chunks)
@@ -324,7 +324,7 @@ int launch_big(spg_ctx* ctx, const spg_gens* g, BigArgs a, Ext* host_groups_dev,
     hipLaunchKernelGGL(k_big_scatter<C>, dim3(a.G), dim3(kBigBS), 0, s, a, ch, chunks, first, gcnt, host_groups_dev);
   }
   // SPG_BIG_PROBE=1: per-workgroup phase timestamps of the accumulation (+ group reductions), on stderr
-  static const bool probe_on = getenv("SPG_BIG_PROBE") != nullptr;
+  const bool probe_on = knob::big_probe();
   unsigned long long* pa = nullptr;
   if (probe_on) {
     SPG_HIP(ctx, hipMalloc(&pa, 4 * max_chunks * 8));
@@ -397,8 +397,7 @@ int msm_single_big(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const Fq*
   // measured the comb level with the buckets (0.210-0.213 against 0.204-0.209 ms, profiles/r04_ab_combwgs_bigcomb.txt);
   // with the entries padded to one line and the parts summed on the host's IFMA lanes it is ahead: 0.171-0.179 ms with
   // 4 window groups per scalar, 0.146 ms with 2 (SPG_BIG_COMB_G), against 0.204-0.206 ms (profiles/r05_ab_big_comb.txt)
-  static const bool comb_on = !getenv("SPG_BIG_COMB") || atoi(getenv("SPG_BIG_COMB")) != 0;
-  if (comb_on && !ctx->comb_off && n >= ((size_t)1 << 14)) {
+  if (knob::big_comb() && !ctx->comb_off && n >= ((size_t)1 << 14)) {
     const int rc = msm_single_comb(ctx, g, gen_offset, d_scalars, n, d_blind, out);
     if (rc != 1) return rc;
   }
@@ -415,7 +414,7 @@ int msm_single_big(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const Fq*
   a.h_index = (int)g->n;
   a.n1 = (int)(g->n + 1);
   // digit blocks: SPG_BIG_SPT scalars per thread (default 1), at most 512 blocks (the histogram matrix is NB x G)
-  static const int spt = getenv("SPG_BIG_SPT") ? std::max(1, atoi(getenv("SPG_BIG_SPT"))) : 1;
+  const int spt = knob::big_spt();
   a.G = std::max(1, std::min(512, (per + spt * kBigBS - 1) / (spt * kBigBS)));
   a.spb = (per + a.G - 1) / a.G;
   int ng = 0, rc = 0;

@@ -28,6 +28,7 @@
 
 #include "ctx.hpp"
 #include "hcurve.hpp"
+#include "knobs.hpp"
 #include "quad.hpp"
 #include "vmsm.hpp"
 
@@ -275,8 +276,7 @@ __global__ void __launch_bounds__(kVBS, 4) k_vmsm_accum(const VChunk* __restrict
 // below this many points per MSM the sum runs on the host pool; 0: every size through the kernels.
 // SPG_VMSM_HOST_MAX is read once per process; spg_set_vmsm_host_max overrides it for one context.
 size_t vmsm_host_max(const spg_ctx* ctx) {
-  static const size_t v = getenv("SPG_VMSM_HOST_MAX") ? (size_t)atol(getenv("SPG_VMSM_HOST_MAX")) : 64;
-  return ctx->vmsm_host_max >= 0 ? (size_t)ctx->vmsm_host_max : v;
+  return ctx->vmsm_host_max >= 0 ? (size_t)ctx->vmsm_host_max : (size_t)knob::vmsm_host_max();
 }
 
 // the device pipeline: B MSMs (MSM b: lens[b] points from offs[b], scalars d_s[soff_b ..) concatenated), out: B x 32
@@ -301,7 +301,8 @@ int vmsm_device(spg_ctx* ctx, const spg_points* P, const size_t* offs, const siz
   }
   SPG_CHECK(ctx, E < 0x7fffffffULL && K < 0x7fffffffULL, "variable-base MSM too large");
   // chunk size: up to 4 entries per lane (a bucket with more -- skewed scalars -- splits into several chunks)
-  static const uint32_t ch = getenv("SPG_VMSM_CH") ? (uint32_t)std::max(1, atoi(getenv("SPG_VMSM_CH"))) : 4 * kVBS;
+  static_assert(knob::vmsm_ch_dflt == 4 * kVBS, "knobs.hpp default");
+  const uint32_t ch = (uint32_t)knob::vmsm_ch();
   const size_t max_chunks = E / ch + K + 1;
   VArgs a{};
   a.scalars = d_s;

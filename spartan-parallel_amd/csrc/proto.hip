@@ -11,6 +11,7 @@
 #include <memory>
 
 #include "hostpoly.hpp"
+#include "knobs.hpp"
 
 #include "proto.hpp"
 
@@ -34,7 +35,7 @@ h::HExt commit_host(ProverGens& g, const KeyView& k, const FqV& x, const Fq& bli
 // SPG_TRACE >= 2: cumulative host time and count of the sigma-protocol commitments (printed by SNARK::prove)
 CommitStats g_commit_stats;
 std::vector<Pt> commit_batch(ProverGens& g, const std::vector<CJob>& jobs) {
-  static const bool tr2 = getenv("SPG_TRACE") && atoi(getenv("SPG_TRACE")) >= 2;
+  const bool tr2 = knob::trace() >= 2;
   const auto t0 = tr2 ? std::chrono::steady_clock::now() : std::chrono::steady_clock::time_point();
   struct Done {
     bool on;
@@ -204,7 +205,7 @@ DotProductProofP dotproduct_prove(ProverGens& g, const KeyView& k1, const KeyVie
 
 // B fixed-base MSMs of n host scalars each over generator indices already on the device (d_idx: B x n)
 // SPG_TRACE >= 2: where a Bullet round's time goes (accumulated over a process, printed per DotProductProofLog)
-static Laps g_msm_laps{"DotProductProofLog::prove (cumulative)", getenv("SPG_TRACE") && atoi(getenv("SPG_TRACE")) >= 2};
+static Laps g_msm_laps{"DotProductProofLog::prove (cumulative)", knob::trace() >= 2};
 
 static h::HExt hext_small_mul(h::HExt P, unsigned k) {
   h::HExt r = h::hext_identity();
@@ -220,7 +221,7 @@ void bucket_finals(const Ext* bk, size_t B, int NB, Pt* out, const h::HExt* extr
   // sum over chunks of acc + lo * run. Chunks spread one MSM's 2 NB dependent additions over the pool;
   // the last chunk of an MSM to finish (countdown) adds the chunks and encodes, all in one burst.
   // chunks per set: one burst wave over the pool (B sets x K chunks ~ threads; at least 2 buckets per chunk)
-  static const int kmax = getenv("SPG_FINALS_K") ? std::max(1, atoi(getenv("SPG_FINALS_K"))) : 8;
+  const int kmax = knob::finals_k();
   const int threads = pool().size() + 1;
   int K = NB >= 64 ? std::max(1, std::min(kmax, threads / (int)std::max<size_t>(B, 1))) : 1;
   while (NB % K) K--;
@@ -256,7 +257,7 @@ void bucket_finals(const Ext* bk, size_t B, int NB, Pt* out, const h::HExt* extr
 static void parts_finals(const Ext* bk, size_t B, size_t per, Pt* out, const h::HExt* extra) {
   const int threads = pool().size() + 1;
   // chunks of >= 8 parts (>= 48 with the 8-lane IFMA sums, whose lanes want several points each)
-  static const bool vec = h::ifma_on() && !(getenv("SPG_VEC_MIN") && atol(getenv("SPG_VEC_MIN")) == 0);
+  const bool vec = h::ifma_on() && knob::vec_min() != 0;
   const size_t cmin = vec ? 48 : 8;
   const int K = (int)std::max<size_t>(1, std::min<size_t>(per / cmin, (size_t)threads / std::max<size_t>(B, 1)));
   std::vector<h::HExt> part(B * K);
@@ -495,7 +496,7 @@ int dotproduct_log_prove(spg_ctx* ctx, ProverGens& g, Tr& t, Tape& tape, const F
                          const Fq& y, const Fq& blind_y, DotProductProofLogP* out, Pt* Cy_out) {
   g_msm_laps.lap("outside_bullet");
   // SPG_TRACE >= 3: this proof's own laps (the difference of the cumulative ones), one line per proof
-  static const bool per_proof = getenv("SPG_TRACE") && atoi(getenv("SPG_TRACE")) >= 3;
+  const bool per_proof = knob::trace() >= 3;
   const std::vector<std::pair<std::string, double>> laps0 = per_proof ? g_msm_laps.acc : decltype(laps0)();
   t.protocol("dot product proof (log)");
   size_t n = x.size();
@@ -514,15 +515,13 @@ int dotproduct_log_prove(spg_ctx* ctx, ProverGens& g, Tr& t, Tape& tape, const F
   // instead of a device round trip. Early in round 6 (comb rounds ~17 us) 16 beat 32; once the host proof had its
   // Cy / beta off the chain, side-by-side encodings and the two-chain Fp carries, 32 beat 16 in 9 of 10 alternations
   // (median -0.5 to -0.9 ms) and tied 64, and 128 lost (profiles/r06_ab_bullet_host_max.txt).
-  static const size_t host_max = getenv("SPG_BULLET_HOST_MAX") ? (size_t)atol(getenv("SPG_BULLET_HOST_MAX")) : 32;
-  const bool on_host = n <= host_max;
+  const bool on_host = n <= (size_t)knob::bullet_host_max();
   // generator indices G_0..G_{n-1}, G_1, h for B = 2 MSMs, uploaded once for all rounds
   const size_t n2 = n + 2;
   uint32_t* d_idx = nullptr;
   using HostJob = std::pair<std::vector<size_t>, FqV>;
-  static const bool dev_rounds = !getenv("SPG_BULLET_DEV") || atoi(getenv("SPG_BULLET_DEV")) != 0;
-  static const bool ahead = !getenv("SPG_BULLET_AHEAD") || atoi(getenv("SPG_BULLET_AHEAD")) != 0;
-  const bool dev_path = dev_rounds && !on_host && n >= 2 && (n & (n - 1)) == 0;
+  const bool ahead = knob::bullet_ahead();
+  const bool dev_path = knob::bullet_dev() && !on_host && n >= 2 && (n & (n - 1)) == 0;
   std::vector<uint32_t> idx2;
   if (!on_host) {
     idx2.resize(2 * n2);
@@ -555,7 +554,7 @@ int dotproduct_log_prove(spg_ctx* ctx, ProverGens& g, Tr& t, Tape& tape, const F
   // Cy = y.commit(blind_y, gens_1) depends on no challenge: it is computed beside Cx (in Cx's host burst, or on the
   // pool while the device computes Cx) instead of in a burst of its own after it; the transcript still takes Cx first
   // (SPG_DOTLOG_EARLY=0: Cy and beta in bursts of their own, in transcript order)
-  static const bool early = !getenv("SPG_DOTLOG_EARLY") || atoi(getenv("SPG_DOTLOG_EARLY")) != 0;
+  const bool early = knob::dotlog_early();
   Pt Cy;
   bool cy_done = false;
   auto cy_job = [&]() -> HostJob {
@@ -639,8 +638,7 @@ int dotproduct_log_prove(spg_ctx* ctx, ProverGens& g, Tr& t, Tape& tape, const F
   bool beta_done = false;
   g_msm_laps.lap("bullet_prep");
   // delta's scalars d cw_j on the device from the rounds' own cw (no host fold of cw, no upload; SPG_DELTA_DEV=0: host)
-  static const bool delta_dev = !getenv("SPG_DELTA_DEV") || atoi(getenv("SPG_DELTA_DEV")) != 0;
-  static const bool delta_comb = !getenv("SPG_DELTA_COMB") || atoi(getenv("SPG_DELTA_COMB")) != 0;
+  const bool delta_dev = knob::delta_dev(), delta_comb = knob::delta_comb();
   DevFinal dfin;
   const bool use_dfin = mbk && delta_comb && delta_dev;
   if (mbk) {
@@ -693,8 +691,7 @@ int dotproduct_log_prove(spg_ctx* ctx, ProverGens& g, Tr& t, Tape& tape, const F
     t.point("R", pts[1]);
     Fq u = t.challenge("u");
     Fq uinv;
-    static const bool overlap = !getenv("SPG_BULLET_OVERLAP") || atoi(getenv("SPG_BULLET_OVERLAP")) != 0;
-    if (n < 256 || !overlap) {
+    if (n < 256 || !knob::bullet_overlap()) {
       uinv = fq_inv(u);
       for (size_t i = 0; i < nh; i++) {
         aa[i] = fq_add(fq_mul(aa[i], u), fq_mul(uinv, aa[i + nh]));

@@ -16,6 +16,7 @@
 
 #include "comm.hpp"
 #include "hostpoly.hpp"
+#include "knobs.hpp"
 #include "pe_plan.hpp"
 #include "proto.hpp"
 #include "lds.hpp"
@@ -358,46 +359,9 @@ __global__ void __launch_bounds__(256) k_sum_segments(const Fq* __restrict__ par
 // ------------------------------------------------------------------------------------ host helpers
 // (eq tables, UniPoly::from_evals, short MLE evaluations: hostmath.hpp)
 
-// the prover's switches and limits (environment, read once per process)
-struct R1csKnobs {
-  bool tape_ahead;     // SPG_TAPE_AHEAD: ZKRounds computes every round's randomness-only points in one burst at init
-  bool sc_fuse;        // SPG_SC_FUSE: a round's fold rides in the next round's evaluation (sumcheck.hip, FOLD kernels);
-                       // 0 restores the separate fold launch
-  bool z_tiled;        // SPG_Z_TILED: k_z_fill_tiled when every instance's row is whole 256-element tiles
-  bool z_side;         // SPG_Z_SIDE: the Z fill runs on the second stream beside phase 1 (ZFill); 0 fills it in order
-  size_t z_after;      // SPG_Z_AFTER (4): the phase-1 round whose evaluation the side-stream Z fill is queued after
-  bool spmv_tiled;     // SPG_SPMV_TILED: k_spmv<true> when every instance's q rows are whole 256-row tiles
-  bool p1_pair;        // SPG_P1_PAIR: two phase-1 rounds per launch (k_phase1_pair); 0: one per launch
-  size_t p1_pair_max;  // SPG_P1_PAIR_MAX (8192, at most kP1PairMax): points of a phase-1 pair's second round
-  bool sigma_ahead;    // SPG_SIGMA_AHEAD: every point of the three sigma protocols in one host burst ahead of the
-                       // transcript sequence; 0: each protocol commits on its own
-  bool q_bound_all;    // SPG_Q_BOUND_ALL: every q fold of Z in one pass (k_pqx_bound_q); 0: one launch per challenge
-  bool p2_pair;        // SPG_P2_PAIR: two phase-2 y rounds per launch (k_phase2_pair); 0: one per launch
-  size_t p2_pair_max;  // SPG_P2_PAIR_MAX (8192, at most kP1PairMax): elements of a phase-2 pair
-  bool wit_in_place;   // SPG_WIT_IN_PLACE: witness parts resident on this device are read in place, not copied
-};
-static const R1csKnobs& r1cs_knobs() {
-  static const R1csKnobs kn = [] {
-    auto on = [](const char* name) { return !getenv(name) || atoi(getenv(name)) != 0; };
-    auto num = [](const char* name, size_t dflt) { return getenv(name) ? (size_t)atol(getenv(name)) : dflt; };
-    R1csKnobs k;
-    k.tape_ahead = on("SPG_TAPE_AHEAD");
-    k.sc_fuse = on("SPG_SC_FUSE");
-    k.z_tiled = on("SPG_Z_TILED");
-    k.z_side = on("SPG_Z_SIDE");
-    k.z_after = num("SPG_Z_AFTER", 4);
-    k.spmv_tiled = on("SPG_SPMV_TILED");
-    k.p1_pair = on("SPG_P1_PAIR");
-    k.p1_pair_max = std::min<size_t>(kP1PairMax, num("SPG_P1_PAIR_MAX", 8192));
-    k.sigma_ahead = on("SPG_SIGMA_AHEAD");
-    k.q_bound_all = on("SPG_Q_BOUND_ALL");
-    k.p2_pair = on("SPG_P2_PAIR");
-    k.p2_pair_max = std::min<size_t>(kP1PairMax, num("SPG_P2_PAIR_MAX", 8192));
-    k.wit_in_place = on("SPG_WIT_IN_PLACE");
-    return k;
-  }();
-  return kn;
-}
+// (the prover's switches: knobs.hpp) a pair's size limits, within the buffers sized by kP1PairMax
+static size_t p1_pair_max() { return std::min<size_t>(kP1PairMax, (size_t)knob::p1_pair_max()); }
+static size_t p2_pair_max() { return std::min<size_t>(kP1PairMax, (size_t)knob::p2_pair_max()); }
 
 // ZK sumcheck round bookkeeping shared by phase 1 and phase 2 (sumcheck.rs:1247-1370).
 // The RandomTape is a transcript that only ever absorbs labels, so the values a round draws do not depend on
@@ -422,7 +386,7 @@ struct ZKRounds {
     blinds_evals = tape.vec("blinds_evals", rounds);
     claim = c;
     blind_claim = b;
-    ahead = r1cs_knobs().tape_ahead && rounds > 0 && g.gens_4.G.size() == 4;
+    ahead = knob::tape_ahead() && rounds > 0 && g.gens_4.G.size() == 4;
     if (!ahead) {
       comm_claim = commit_batch(g, {CJob(g.gens_1, {c}, b)})[0];
       return;
@@ -749,7 +713,6 @@ struct Prover {
   int exchange(const void* send, size_t bytes, std::vector<uint8_t>& recv);
   int gather_first(const std::vector<const PqxDev*>& tabs, std::vector<std::vector<Fq>>& full);
 
-  const R1csKnobs& kn = r1cs_knobs();
   Shape sh;
   Carry cy;
   Laps lp;
@@ -937,7 +900,7 @@ int Prover::run_stages() {
 
   ZFill zf;
   int rc = setup_tables(zf);
-  if (!rc && !kn.z_side) rc = zf.queue();
+  if (!rc && !knob::z_side()) rc = zf.queue();
   if (rc) return rc;
   lp.lap("setup");
   cy.partials = (Fq*)ws_get(ctx, WS_PART, std::max(3 * (size_t)kScGridMax, kP1PairMax) * sizeof(Fq) + 64);
@@ -990,7 +953,7 @@ int Prover::setup_tables(ZFill& zf) {
   ZDesc* dz = nullptr;
   SpDesc* dsd = nullptr;
   double visits = 0;
-  bool z_tiled = kn.z_tiled, spmv_tiled = kn.spmv_tiled;
+  bool z_tiled = knob::z_tiled(), spmv_tiled = knob::spmv_tiled();
   int rc = 0;
   {
     std::vector<ZDesc> zd(PLn);
@@ -1037,12 +1000,12 @@ int Prover::setup_tables(ZFill& zf) {
     if (rc) return rc;
   }
   zf.c = ctx, zf.dz = dz, zf.dsec = dsec, zf.n = (int)PLn, zf.nws = (int)nws;
-  zf.Z = cy.Zp.d, zf.total = ztot, zf.tiled = z_tiled, zf.side = kn.z_side;
+  zf.Z = cy.Zp.d, zf.total = ztot, zf.tiled = z_tiled, zf.side = knob::z_side();
   // ---- tau tables (identical on every rank)
   FqV tau_p = t.challenges("challenge_tau_p", np);
   FqV tau_q = t.challenges("challenge_tau_q", nq);
   FqV tau_x = t.challenges("challenge_tau_x", nx);
-  if (getenv("SPG_DEBUG_TR")) fprintf(stderr, "[prove] r1cs P=%zu np=%zu nq=%zu nx=%zu tau_x0 %08x\n", (size_t)P, (size_t)np, (size_t)nq, (size_t)nx, tau_x[0].l[0]);
+  if (knob::debug_tr()) fprintf(stderr, "[prove] r1cs P=%zu np=%zu nq=%zu nx=%zu tau_x0 %08x\n", (size_t)P, (size_t)np, (size_t)nq, (size_t)nx, tau_x[0].l[0]);
   cy.Ap = (Fq*)ws_get(ctx, WS_TP, (sizeof(Fq) << np) + 64);
   cy.Aq = (Fq*)ws_get(ctx, WS_TQ, (sizeof(Fq) << nq) + 64);
   cy.Ax = (Fq*)ws_get(ctx, WS_TX, (sizeof(Fq) << nx) + 64);
@@ -1108,7 +1071,7 @@ int Prover::p1_to_compact(Phase1& s) {
 // SPG_P1_PAIR_MAX (default 8192) points: the latency-bound rounds. Unsharded proofs only (a sharded round sums 3
 // scalars over the ranks, a pair would sum 15).
 bool Prover::p1_pair_ok(const Phase1& s, size_t j) const {
-  if (!kn.p1_pair || !s.Aq2 || nranks != 1 || j + 1 >= s.rounds || s.T != &cy.Az) return false;
+  if (!knob::p1_pair() || !s.Aq2 || nranks != 1 || j + 1 >= s.rounds || s.T != &cy.Az) return false;
   const int m = p1_mode(j);
   if (m == MODE_P || p1_mode(j + 1) != m) return false;
   size_t dom = 0;
@@ -1118,7 +1081,7 @@ bool Prover::p1_pair_ok(const Phase1& s, size_t j) const {
     if (N < 4 || N != Nl) return false;
     dom += m == MODE_X ? s.sc_np[p] * (N / 4) : (N / 4) * s.sc_nc[p];
   }
-  return dom > 0 && dom <= kn.p1_pair_max;
+  return dom > 0 && dom <= p1_pair_max();
 }
 // rounds j, j + 1 in one launch; nf = 1: round j - 1's pending fold (fp), 2: the previous pair's (r1, r2)
 int Prover::p1_launch_pair(Phase1& s, size_t j, int nf, const FoldPlan* fp, const Fq& r1, const Fq& r2) {
@@ -1253,7 +1216,7 @@ int Prover::p1_round_single(Phase1& s, size_t j, ZFill& zf) {
   const int mode = p1_mode(j);
   Fq e[3];
   int rc = eval_wait(ctx, e);
-  if (!rc && j == kn.z_after) rc = zf.queue();  // round j is done and round j + 1 not yet queued
+  if (!rc && j == (size_t)knob::z_after()) rc = zf.queue();  // round j is done and round j + 1 not yet queued
   if (!rc && j == 1 && failpoint(ctx, "r1cs_round")) rc = set_err(ctx, SPG_E_HIP, "failpoint r1cs_round");
   if (!rc && mode != MODE_P) rc = sum_ranks(e);
   if (rc) return rc;
@@ -1292,7 +1255,7 @@ int Prover::p1_round_pair(Phase1& s, size_t j, ZFill& zf) {
   static const char* const laps[3] = {"p1_eval", "p1_host", "p1_fold"};
   Fq ev[15];
   int rc = pair_wait(ctx, ev);
-  if (!rc && (j == kn.z_after || j + 1 == kn.z_after)) rc = zf.queue();
+  if (!rc && (j == (size_t)knob::z_after() || j + 1 == (size_t)knob::z_after())) rc = zf.queue();
   if (!rc && (j == 1 || j + 1 == 1) && failpoint(ctx, "r1cs_round")) rc = set_err(ctx, SPG_E_HIP, "failpoint r1cs_round");
   if (rc) return rc;
   return round_pair_arm(s, j, ev, laps, &Prover::p1_launch_next);
@@ -1306,7 +1269,7 @@ int Prover::run_phase1(ZFill& zf, FqV& r_all) {
   s.sc_np = sh.l_proofs, s.sc_nc = sh.l_cons;
   s.T = &cy.Az, s.TB = cy.Bz, s.TC = cy.Cz;
   s.Aq = cy.Aq, s.Ax = cy.Ax, s.Ap_l = cy.Ap + p0;
-  if (kn.sc_fuse) {
+  if (knob::sc_fuse()) {
     s.Aq2 = (Fq*)ws_get(ctx, WS_TQ2, (sizeof(Fq) << nq) + 64);
     s.Ax2 = (Fq*)ws_get(ctx, WS_TX2, (sizeof(Fq) << nx) + 64);
     if (!s.Aq2 || !s.Ax2) return set_err(ctx, SPG_E_NOMEM, "eq tables");
@@ -1343,18 +1306,19 @@ void Prover::sigma1() {
   const Fq blind_expected1 = fq_mul(tau_claim, fq_sub(prod_blind, cy.Cz_blind));
   const Fq claim_post1 = fq_mul(fq_sub(prod, Cz_claim), tau_claim);
   Sigma1Pre sp;
-  if (kn.sigma_ahead)
+  if (knob::sigma_ahead())
     sigma1_points(g, g.gens_1, tape, Cz_claim, cy.Cz_blind, Az_claim, cy.Az_blind, Bz_claim, cy.Bz_blind, prod,
                   prod_blind, claim_post1, blind_expected1, claim_post1, cy.blind_post1, &sp);
-  pf.pok = knowledge_prove(g, g.gens_1, t, tape, Cz_claim, cy.Cz_blind, &cy.comm_Cz, kn.sigma_ahead ? sp.k : nullptr);
+  pf.pok = knowledge_prove(g, g.gens_1, t, tape, Cz_claim, cy.Cz_blind, &cy.comm_Cz,
+                           knob::sigma_ahead() ? sp.k : nullptr);
   pf.prod = product_prove(g, g.gens_1, t, tape, Az_claim, cy.Az_blind, Bz_claim, cy.Bz_blind, prod, prod_blind,
-                          &cy.comm_Az, &cy.comm_Bz, &cy.comm_prod, kn.sigma_ahead ? sp.p : nullptr);
+                          &cy.comm_Az, &cy.comm_Bz, &cy.comm_prod, knob::sigma_ahead() ? sp.p : nullptr);
   t.point("comm_Az_claim", cy.comm_Az);
   t.point("comm_Bz_claim", cy.comm_Bz);
   t.point("comm_Cz_claim", cy.comm_Cz);
   t.point("comm_prod_Az_Bz_claims", cy.comm_prod);
   pf.eq1 = equality_prove(g, g.gens_1, t, tape, claim_post1, blind_expected1, claim_post1, cy.blind_post1,
-                          kn.sigma_ahead ? sp.e : nullptr);
+                          knob::sigma_ahead() ? sp.e : nullptr);
 }
 
 // phase 2's inputs: the claim, ABC = r_A A + r_B B + r_C C at rx (k_abc), Z joined and bound at rq_rev, eq(rp)
@@ -1400,7 +1364,7 @@ int Prover::phase2_prep(ZFill& zf) {
   // Z.bound_poly_vars_rq(rq_rev): every q fold in one pass over Z against eq(rq_rev), or one fold launch per
   // challenge, each a read-write pass over the live rows
   const FqV& rq_rev = cy.rq_rev;
-  if (kn.q_bound_all && rq_rev.size() >= 2) {
+  if (knob::q_bound_all() && rq_rev.size() >= 2) {
     Fq* eq_q = (Fq*)ws_get(ctx, WS_EQQ, (sizeof(Fq) << rq_rev.size()) + 64);
     if (!eq_q) return set_err(ctx, SPG_E_NOMEM, "eq(rq)");
     rc = eq_table(ctx, rq_rev, eq_q);
@@ -1462,7 +1426,7 @@ bool Prover::p2_pair_ok(const Phase2& s, size_t j, bool fold_pending) const {
   const bool single = sh.single;
   const PqxDev &ABC = cy.ABC, &Zp = cy.Zp;
   // (one ABC shared by every instance folds through its ping-pong buffer, as the fused single rounds do)
-  if (!kn.p2_pair || (single && !s.ABC2) || nranks != 1 || j + 1 >= sh.ny || s.TA != &ABC || s.TZ != &Zp ||
+  if (!knob::p2_pair() || (single && !s.ABC2) || nranks != 1 || j + 1 >= sh.ny || s.TA != &ABC || s.TZ != &Zp ||
       ABC.zlen != (single ? 1 : Zp.zlen))
     return false;
   auto live = [&](size_t n) { return fold_pending && n > 1 ? n / 2 : n; };
@@ -1472,7 +1436,7 @@ bool Prover::p2_pair_ok(const Phase2& s, size_t j, bool fold_pending) const {
     if (N < 4 || live(ABC.num_inputs[single ? 0 : p]) != N || s.sc_ni[p] != N) return false;
     dom += s.W2 * (N / 4);
   }
-  return dom > 0 && dom <= kn.p2_pair_max;
+  return dom > 0 && dom <= p2_pair_max();
 }
 // y rounds j, j + 1 in one launch; nf = 2: the previous pair's folds (r1, r2) ride in it
 int Prover::p2_launch_pair(Phase2& s, int nf, const Fq& r1, const Fq& r2) {
@@ -1594,7 +1558,7 @@ int Prover::run_phase2() {
   // one ABC serving every instance is folded into ABC2 by a fused round (then the two swap). The fused fold writes it
   // from the points of local instance 0 (global p0): only when that instance spans ABC's whole width (num_inputs[0])
   // -- a sharded rank whose first instance is narrower takes the separate fold
-  s.fuse2 = kn.sc_fuse && (!sh.single || num_inputs[p0] == num_inputs[0]);
+  s.fuse2 = knob::sc_fuse() && (!sh.single || num_inputs[p0] == num_inputs[0]);
   if (s.fuse2 && sh.single) {
     s.ABC2 = (Fq*)ws_get(ctx, WS_ABC2, cy.ABC.total * sizeof(Fq) + 64);
     if (!s.ABC2) return set_err(ctx, SPG_E_NOMEM, "ABC");
@@ -2153,7 +2117,7 @@ int witness_from_parts(spg_ctx* ctx, const std::vector<WPart>& secs, spg_r1cs_wi
     }
     return a.type == hipMemoryTypeDevice && a.device == ctx->device;
   };
-  const bool in_place = r1cs_knobs().wit_in_place;
+  const bool in_place = knob::wit_in_place();
   std::vector<std::vector<char>> dev(secs.size());
   size_t host_total = 0;
   for (size_t w = 0; w < secs.size(); w++)

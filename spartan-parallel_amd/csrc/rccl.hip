@@ -19,6 +19,7 @@
 #include <string>
 
 #include "ctx.hpp"
+#include "knobs.hpp"
 
 namespace spg {
 
@@ -123,7 +124,7 @@ int rccl_allgather(void* user, const void* send, size_t bytes, void* recv) {
   if ((hipMemcpyAsync)(c->h_buf + c->cap, d_recv, bytes * (size_t)c->nranks, hipMemcpyDeviceToHost, s) != hipSuccess)
     return -1;
   // bounded wait: a peer that died leaves the collective pending forever
-  static const long timeout_s = getenv("SPG_RCCL_TIMEOUT_S") ? std::max(1L, atol(getenv("SPG_RCCL_TIMEOUT_S"))) : 600L;
+  const long timeout_s = knob::rccl_timeout_s();
   const auto t0 = std::chrono::steady_clock::now();
   for (;;) {
     const hipError_t e = hipStreamQuery(s);

@@ -18,6 +18,7 @@
 #include <algorithm>
 
 #include "hostpoly.hpp"
+#include "knobs.hpp"
 #include "pe_plan.hpp"
 #include "pe_prove.hpp"
 #include "proto.hpp"
@@ -121,7 +122,7 @@ int sat_prove(spg_ctx* ctx, spg_r1cs_gens* gens, spg_r1cs_inst* inst, size_t P, 
               SatOut* out) {
   Laps lp;
   lp.title = "sat_prove";
-  lp.on = lp.on && atoi(getenv("SPG_TRACE")) >= 2;
+  lp.on = lp.on && knob::trace() >= 2;
   int rc = witness_from_parts(ctx, secs, W);
   if (rc) return rc;
   lp.lap("witness_from_parts");
@@ -186,18 +187,6 @@ void append_r1cs_comm(const spg_snark_comp* C, size_t g, Tr& t) {
   spark_comm_append(C->sparks[g], t);
 }
 
-int env_int(const char* name, int dflt) {
-  const char* s = getenv(name);
-  return s ? atoi(s) : dflt;
-}
-struct SnarkKnobs {  // the environment switches of SNARK::prove, read once per prove
-  const bool debug_snark = getenv("SPG_DEBUG_SNARK") != nullptr, debug_tr = getenv("SPG_DEBUG_TR") != nullptr;
-  const int trace = env_int("SPG_TRACE", 0);
-  const bool copy_trace = env_int("SPG_COPY_TRACE", 0) != 0;
-  const bool halved_enc = env_int("SPG_HALVED_ENC", 1) != 0;  // early comb rows encoded on the host from halved points
-  const bool cq_side = env_int("SPG_CQ_SIDE", 1) != 0;        // the commit queue's other rows on the second stream
-};
-
 struct SecInfo {  // sizes + data pointers for merges (ProverWitnessSecInfo::merge / concat, lib.rs:546-604)
   std::vector<size_t> num_proofs, num_inputs;
   std::vector<const Fq*> src;  // host or device data of each instance
@@ -242,7 +231,6 @@ struct CQ {
     size_t len;
     std::vector<Pt>* out;
   };
-  const SnarkKnobs& kn;
   std::vector<Item> items;
   // Early group: device-resident polynomials (the block witnesses) whose rows are committed by one batch MSM
   // launched before the host builds the permutation witnesses, so the device works while the host does;
@@ -257,7 +245,6 @@ struct CQ {
   std::vector<std::vector<Pt>> rows;
   std::vector<RowJob> jobs;
   RowsPending pend;
-  explicit CQ(const SnarkKnobs& k) : kn(k) {}
 
   // the Hyrax row width of a polynomial of `len` scalars: 2^(nv - nv / 2)
   static size_t row_width(size_t len) { return (size_t)1 << (lg2(len) - lg2(len) / 2); }
@@ -295,7 +282,7 @@ struct CQ {
     // the comb rows with halved scalars: flush() encodes the points' doubles on the host in one batch (~50 us on the
     // pool for 1024 rows) instead of a k_compress_ext launch (~140 us of dependent squarings per lane)
     // slot 95 (94 is unused)
-    Ext* ext = kn.halved_enc && total / R >= kHalvedMin ? (Ext*)ws_get(ctx, 95, sizeof(Ext) * (total / R) + 64) : nullptr;
+    Ext* ext = knob::halved_enc() && total / R >= kHalvedMin ? (Ext*)ws_get(ctx, 95, sizeof(Ext) * (total / R) + 64) : nullptr;
     int rc = ext ? msm_comb(ctx, g.dev, 0, d, R, total / R, nullptr, nullptr, -1, ext, true) : kCombSkip;
     if (rc == kCombSkip) {
       ext = nullptr;
@@ -388,11 +375,11 @@ struct CQ {
     // commit_rows' latency path, whose workspace slots, mapped buckets and staging the batch pipeline of the early
     // MSM never touches; wider rows stay on the main stream.
     static const size_t kSideMaxR = 256;
-    bool side = kn.cq_side && early_L > 0;
+    bool side = knob::cq_side() && early_L > 0;
     for (size_t R : widths) side = side && R <= kSideMaxR;
     Laps lp;
     lp.title = "commit queue flush";
-    lp.on = lp.on && kn.trace >= 2;
+    lp.on = lp.on && knob::trace() >= 2;
     if (side) SPG_HIP(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_pre, 0));
     const hipStream_t rows_stream = side ? ctx->stream2 : ctx->stream;
     int rc;
@@ -728,7 +715,6 @@ struct SnarkProver {
   ProverGens& g;
   const spg_snark_inputs& a;
   const size_t niu, num_ios;
-  const SnarkKnobs kn;
   const SnarkShape sh;
   Laps lp;
   CQ cq;
@@ -749,7 +735,7 @@ struct SnarkProver {
               spg_r1cs_gens* vg, spg_transcript* tr, spg_random_tape* tp)
       : ctx(c), block(b), pairwise(pw), perm_root(pr), W(wit), vars_gens(vg), transcript(tr), tape_h(tp), t(tr->t),
         tape(tp->t), g(vg->g), a(wit->a), niu(a.num_inputs_unpadded), num_ios(a.num_ios),
-        sh(a, wit->nproofs.data(), wit->nvars.data(), wit->phy_ops.data(), wit->vir_ops.data()), cq(kn), bw(sh.P),
+        sh(a, wit->nproofs.data(), wit->nvars.data(), wit->phy_ops.data(), wit->vir_ops.data()), bw(sh.P),
         c_bv(sh.P), Wt(c->wt_cache) {
     lp.title = "SNARK::prove";
     ctx->wt_cache = nullptr;
@@ -760,7 +746,7 @@ struct SnarkProver {
   }
 
   void fp(const char* where) {  // SPG_DEBUG_SNARK: a fingerprint of the transcript's state
-    if (!kn.debug_snark || t.cb) return;  // (a fork of a caller-backed transcript cannot be taken)
+    if (!knob::debug_snark() || t.cb) return;  // (a fork of a caller-backed transcript cannot be taken)
     Tr c = t;
     Fq x = c.challenge("dbg");
     fprintf(stderr, "fp %s %08x\n", where, x.l[0]);
@@ -852,8 +838,8 @@ int SnarkProver::launch_early_commits() {
 void SnarkProver::draw_challenges() {
   tau = t.challenge("challenge_tau");
   r = t.challenge("challenge_r");
-  if (kn.debug_tr) fprintf(stderr, "[prove] tau %08x r %08x\n", tau.l[0], r.l[0]);
-  if (kn.debug_snark) fprintf(stderr, "snark tau %08x %08x r %08x\n", tau.l[0], tau.l[1], r.l[0]);
+  if (knob::debug_tr()) fprintf(stderr, "[prove] tau %08x r %08x\n", tau.l[0], r.l[0]);
+  if (knob::debug_snark()) fprintf(stderr, "snark tau %08x %08x r %08x\n", tau.l[0], tau.l[1], r.l[0]);
   perm_w0 = spg::perm_w0(tau, r, niu, num_ios);
   w0.rows[0] = {perm_w0};
   w0.queue(cq);
@@ -868,7 +854,7 @@ void SnarkProver::gen_perm_exec() {
     w3[q][5] = w2[q][1];
   });
   perm_chain(w3, 2, column(w3, 1));
-  if (kn.debug_snark)
+  if (knob::debug_snark())
     for (size_t q = 0; q < 2; q++)
       for (size_t i = 0; i < num_ios; i++) fprintf(stderr, "pe_w2[%zu][%zu] %08x\n", q, i, w2[q][i].l[0]);
   pe.set(0, std::move(w2), std::move(w3));
@@ -1164,7 +1150,7 @@ int SnarkProver::prove_io() {
 // the trace lines of the whole prove, then the proof into the caller's buffer
 int SnarkProver::finish(uint8_t* proof, size_t proof_cap, size_t* proof_len) {
   lp.print();
-  if (kn.trace >= 2) {
+  if (knob::trace() >= 2) {
     fprintf(stderr, "[spg] sigma-protocol commitments: %zu calls, %zu commitments, %.0f us on the host\n",
                     g_commit_stats.calls, g_commit_stats.points, g_commit_stats.us);
     g_commit_stats = CommitStats();
@@ -1174,7 +1160,7 @@ int SnarkProver::finish(uint8_t* proof, size_t proof_cap, size_t* proof_len) {
     bursts0 = pool().bursts();
     keccak0 = keccak_count();
   }
-  if (kn.copy_trace) print_copy_counts();
+  if (knob::copy_trace()) print_copy_counts();
   *proof_len = w.out.size();
   if (!proof || w.out.size() > proof_cap) return set_err(ctx, SPG_E_ARG, "proof buffer too small");
   memcpy(proof, w.out.data(), w.out.size());
@@ -1214,7 +1200,7 @@ extern "C" int spg_snark_prove(spg_ctx* ctx, spg_snark_comp* block, spg_snark_co
   if (!ctx || !transcript) return SPG_E_ARG;
   // SPG_TRACE: the whole call's wall time (the laps end at the io proofs; this adds the proof copy-out and the
   // release of the prove's host state)
-  static const bool tr = getenv("SPG_TRACE") != nullptr;
+  const bool tr = knob::trace_is_set();
   const auto t0 = std::chrono::steady_clock::now();
   int rc;
   {

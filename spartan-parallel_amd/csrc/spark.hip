@@ -24,6 +24,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "hostpoly.hpp"
+#include "knobs.hpp"
 #include "proto.hpp"
 #include "layer.hpp"
 #include "lds.hpp"
@@ -242,11 +243,11 @@ ProverGens gens_view(spg_gens* dev, size_t nv) {
 // field inversion each (hext_double_and_compress_batch: ~25 products per point instead of a ~265-step inverse square
 // root on a GPU lane or a host core), at any count
 static int encode_points(spg_ctx* ctx, const Ext* d_ext, size_t B, Pt* out, uint8_t* d_out, bool halved = false) {
-  static const size_t host_max = getenv("SPG_HOST_ENC_MAX") ? (size_t)atol(getenv("SPG_HOST_ENC_MAX")) : 384;
+  const size_t host_max = (size_t)knob::host_enc_max();
   if (halved) {
     Ext* h = (Ext*)enc_stage_get(ctx, B * sizeof(Ext));
     if (!h) return set_err(ctx, SPG_E_NOMEM, "encoding staging");
-    static const bool tr3 = getenv("SPG_TRACE") && atoi(getenv("SPG_TRACE")) >= 3;
+    const bool tr3 = knob::trace() >= 3;
     const auto t0 = std::chrono::steady_clock::now();
     SPG_HIP(ctx, hipMemcpyAsync(h, d_ext, B * sizeof(Ext), hipMemcpyDeviceToHost, ctx->stream));
     SPG_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -286,8 +287,7 @@ static int encode_points(spg_ctx* ctx, const Ext* d_ext, size_t B, Pt* out, uint
 // (proto.hpp); SPG_HALVED_ENC=0 keeps the device / lone encodings everywhere)
 static int rows_to_points(spg_ctx* ctx, ProverGens& g, const Fq* d_Z, size_t R, size_t L, Ext* d_ext, bool* halved,
                           bool want) {
-  static const bool on = !getenv("SPG_HALVED_ENC") || atoi(getenv("SPG_HALVED_ENC")) != 0;
-  const bool halve = on && want;
+  const bool halve = knob::halved_enc() && want;
   *halved = false;
   if (L >= 64 && L * R >= ((size_t)1 << 14)) {
     const int rc = msm_comb(ctx, g.dev, 0, d_Z, R, L, nullptr, nullptr, -1, d_ext, halve);
@@ -309,7 +309,7 @@ int commit_rows(spg_ctx* ctx, ProverGens& g, const Fq* d_Z, size_t R, size_t L, 
                              : std::max<size_t>(1, std::min<size_t>(L, ((size_t)1 << 24) / R));
   uint8_t* d_out = (uint8_t*)ws_get(ctx, kWsCommit, 32 * chunk + 64);
   if (!d_out) return set_err(ctx, SPG_E_NOMEM, "commit out");
-  static const bool trace2 = getenv("SPG_TRACE") && atoi(getenv("SPG_TRACE")) >= 2;
+  const bool trace2 = knob::trace() >= 2;
   // SPG_HOST_COMMIT_MAX (default 0: off): row batches of at most this many scalars are committed on the host pool against
   // the generators' fixed-base byte tables (HostGens, built once per generator set): the scalars come down (<= 32 KB)
   // and 32 mixed additions per scalar spread over the pool, instead of a device bucket launch, its host finals and a
@@ -317,8 +317,7 @@ int commit_rows(spg_ctx* ctx, ProverGens& g, const Fq* d_Z, size_t R, size_t L, 
   // 115 against 86 us, profiles/r05_ab_host_commit.txt). Off: a generator's table is built on its first use (11-24 ms
   // for the 8- and 16-generator rows of config 4's first proof), and config 4 measured 4.03 against 3.86 ms with it
   // (ABBA, profiles/r05_ab_host_commit_c4.txt)
-  static const size_t host_commit_max =
-      getenv("SPG_HOST_COMMIT_MAX") ? (size_t)atol(getenv("SPG_HOST_COMMIT_MAX")) : 0;
+  const size_t host_commit_max = (size_t)knob::host_commit_max();
   for (size_t r0 = 0; r0 < L; r0 += chunk) {
     size_t nb = std::min(chunk, L - r0);
     auto t0 = std::chrono::steady_clock::now();
@@ -568,7 +567,7 @@ int tree_build(spg_ctx* ctx, Fq* tree, size_t nc, size_t M, Fq* tops) {
   hipStream_t s = ctx->stream;
   KScope ks(ctx, "spark_product_tree", 96.0 * nc * M / 2);
   // levels of more than kTopHalf products per circuit: one grid-wide launch each; the rest and the tops: k_tree_top
-  static const size_t kTopHalf = getenv("SPG_TREE_TOP") ? (size_t)atol(getenv("SPG_TREE_TOP")) : 1024;
+  const size_t kTopHalf = (size_t)knob::tree_top();
   size_t k = 0;
   for (; k + 1 < lg2(M) && (M >> (k + 1)) > kTopHalf; k++) {
     size_t ok = 2 * M - 2 * (M >> k), ok1 = 2 * M - 2 * (M >> (k + 1));
@@ -609,8 +608,7 @@ int dotp_evaluate(spg_ctx* ctx, const std::vector<Triple>& dotp, size_t n, Fq* o
 // workgroups and block size of a fused layer round over W = nt * len elements: one workgroup up to kOneWgMax
 // elements (no ticket), else about kEltPerThread elements per thread over 256-thread workgroups
 static void layer_grid(size_t W, unsigned* K, int* BS) {
-  static const size_t one_wg = getenv("SPG_LAYER_ONEWG") ? (size_t)atoi(getenv("SPG_LAYER_ONEWG")) : 512;
-  static const size_t ept = getenv("SPG_LAYER_EPT") ? (size_t)std::max(1, atoi(getenv("SPG_LAYER_EPT"))) : 2;
+  const size_t one_wg = (size_t)knob::layer_onewg(), ept = (size_t)knob::layer_ept();
   if (W <= 64) {
     *K = 1;
     *BS = 64;
@@ -639,65 +637,47 @@ static void lagrange4(const Fq& r, Fq L[4]) {
   L[3] = fq_mul(fq_mul(a01, a2), inv6);
 }
 
-// the launch forms' switches and limits (environment, read once)
-struct LayerKnobs {
-  bool quad, ends_on, pair_on, triple_on;
-  size_t wide_min;    // thread-elements from which a round takes the throughput form
-  size_t pair_max;    // elements (16 lanes each) of a paired launch
-  size_t triple_max;  // elements (a wave each, four per workgroup) of a tripled launch: 64 partials per workgroup
-  int pair_bs;        // 64: paired launches over 64-thread workgroups (more of them)
-  int step_cost[3];   // relative wall of a launched single / paired / tripled round trip, for the launch plan
+// (the launch forms' switches: knobs.hpp) what the launch plan asks in every cell of its table, read once: the two
+// switches, the size from which a round takes the throughput form, and the limits the buffers put on the launches.
+// A paired launch of E elements (16 lanes each) stores 16 partials per workgroup of BSp / 16 elements into `part` (3 x
+// 2048 scalars): 16 E / BSp * 16 <= 6144, so E <= 6144 with 256-thread workgroups and E <= 1536 with 64-thread ones;
+// a tripled launch takes a wave per element, four per workgroup, 64 partials per workgroup
+struct LayerLimits {
+  bool pair_on = knob::layer_pair(), triple_on = knob::layer_triple();
+  size_t wide_min = (size_t)knob::wide_min();
+  size_t pair_max = std::min<size_t>((size_t)knob::pair_max(), knob::pair_bs() == 64 ? 1536 : 6144);
+  size_t triple_max = std::min<size_t>((size_t)knob::triple_max(), 384);
 };
-static const LayerKnobs& layer_knobs() {
-  static const LayerKnobs kn = [] {
-    auto on = [](const char* name) { return !getenv(name) || atoi(getenv(name)) != 0; };
-    auto num = [](const char* name, size_t dflt) { return getenv(name) ? (size_t)atol(getenv(name)) : dflt; };
-    LayerKnobs k;
-    k.quad = on("SPG_LAYER_QUAD");
-    k.ends_on = on("SPG_LAYER_ENDS");
-    k.pair_on = on("SPG_LAYER_PAIR");
-    k.triple_on = on("SPG_LAYER_TRIPLE");
-    k.wide_min = num("SPG_WIDE_MIN", (size_t)1 << 19);
-    k.pair_bs = getenv("SPG_PAIR_BS") ? atoi(getenv("SPG_PAIR_BS")) : 0;
-    // a paired launch of E elements stores 16 partials per workgroup of BSp / 16 elements into `part` (3 x 2048
-    // scalars): 16 E / BSp * 16 <= 6144, so E <= 6144 with 256-thread workgroups and E <= 1536 with 64-thread ones
-    k.pair_max = std::min<size_t>(num("SPG_PAIR_MAX", 4096), k.pair_bs == 64 ? 1536 : 6144);
-    k.triple_max = std::min<size_t>(num("SPG_TRIPLE_MAX", 384), 384);
-    k.step_cost[0] = 18, k.step_cost[1] = 25, k.step_cost[2] = 30;
-    if (const char* e = getenv("SPG_STEP_COSTS"))
-      sscanf(e, "%d,%d,%d", &k.step_cost[0], &k.step_cost[1], &k.step_cost[2]);
-    return k;
-  }();
-  return kn;
-}
 
 // The launch plan. Two rounds in one launch (k_layer_pair): small rounds of an unsharded layer (`multi`), every
 // element's 16 lanes within pair_max elements, the last pair's corners within the mailbox; three (k_layer_triple): a
 // wave per element within triple_max elements, the last triple's corners within the mailbox. nt triples in ngroups
 // thread groups; k rounds left.
-static bool pair_ok(const LayerKnobs& kn, size_t nt, size_t ngroups, bool multi, size_t k) {
-  return kn.pair_on && multi && k >= 2 && (nt << (k - 2)) <= kn.pair_max && 15 + 12 * nt <= kMboxScalars &&
-         ngroups * ((size_t)1 << (k - 1)) < kn.wide_min;
+static bool pair_ok(const LayerLimits& lim, size_t nt, size_t ngroups, bool multi, size_t k) {
+  return lim.pair_on && multi && k >= 2 && (nt << (k - 2)) <= lim.pair_max && 15 + 12 * nt <= kMboxScalars &&
+         ngroups * ((size_t)1 << (k - 1)) < lim.wide_min;
 }
-static bool triple_ok(const LayerKnobs& kn, size_t nt, size_t ngroups, bool multi, size_t k) {
-  return kn.triple_on && multi && k >= 3 && (nt << (k - 3)) <= kn.triple_max && 64 + 24 * nt <= kMboxScalars &&
-         ngroups * ((size_t)1 << (k - 1)) < kn.wide_min;
+static bool triple_ok(const LayerLimits& lim, size_t nt, size_t ngroups, bool multi, size_t k) {
+  return lim.triple_on && multi && k >= 3 && (nt << (k - 3)) <= lim.triple_max && 64 + 24 * nt <= kMboxScalars &&
+         ngroups * ((size_t)1 << (k - 1)) < lim.wide_min;
 }
 // Single rounds first, then pairs, then triples (a pair leaves two pending folds, which only a pair or a triple
 // applies; a triple three, which only a triple applies), the cheapest by step_cost. Returns the rounds of the first
 // launch from k rounds left with `npend` folds pending, 0 when no plan finishes the layer.
-static int plan_step(const LayerKnobs& kn, size_t nt, size_t ngroups, bool multi, size_t k, int npend) {
+static int plan_step(size_t nt, size_t ngroups, bool multi, size_t k, int npend) {
   const int inf = 1 << 28, mode = npend >= 3 ? 2 : (npend == 2 ? 1 : 0);  // 0: free, 1: after a pair, 2: after a triple
+  static const LayerLimits lim;
+  static const knob::StepCosts cost = knob::step_costs();
   std::vector<std::array<int, 3>> best(k + 1), first(k + 1);
   for (size_t j = 0; j <= k; j++)
     for (int md = 0; md < 3; md++) {
       int b = j == 0 ? 0 : inf, f = 0;
-      if (j >= 1 && md == 0 && best[j - 1][0] < inf && kn.step_cost[0] + best[j - 1][0] < b)
-        b = kn.step_cost[0] + best[j - 1][0], f = 1;
-      if (md <= 1 && pair_ok(kn, nt, ngroups, multi, j) && best[j - 2][1] < inf && kn.step_cost[1] + best[j - 2][1] < b)
-        b = kn.step_cost[1] + best[j - 2][1], f = 2;
-      if (triple_ok(kn, nt, ngroups, multi, j) && best[j - 3][2] < inf && kn.step_cost[2] + best[j - 3][2] < b)
-        b = kn.step_cost[2] + best[j - 3][2], f = 3;
+      if (j >= 1 && md == 0 && best[j - 1][0] < inf && cost.c[0] + best[j - 1][0] < b)
+        b = cost.c[0] + best[j - 1][0], f = 1;
+      if (md <= 1 && pair_ok(lim, nt, ngroups, multi, j) && best[j - 2][1] < inf && cost.c[1] + best[j - 2][1] < b)
+        b = cost.c[1] + best[j - 2][1], f = 2;
+      if (triple_ok(lim, nt, ngroups, multi, j) && best[j - 3][2] < inf && cost.c[2] + best[j - 3][2] < b)
+        b = cost.c[2] + best[j - 3][2], f = 3;
       best[j][md] = b;
       first[j][md] = f;
     }
@@ -767,11 +747,10 @@ static int round_single(const LayerEnv& E, LayerState& S, size_t log_len, bool l
                         bool* done) {
   spg_ctx* ctx = E.ctx;
   hipStream_t s = ctx->stream;
-  const LayerKnobs& kn = layer_knobs();
   if (S.npend > 1) return set_err(ctx, SPG_E_ARG, "single layer round after a paired one");
   log_len--;
   const size_t len = (size_t)1 << log_len, nt = S.nt, ngroups = S.ngroups, nc = E.nc;
-  const bool pending = S.npend == 1, wide = ngroups * len >= kn.wide_min;
+  const bool pending = S.npend == 1, wide = ngroups * len >= (size_t)knob::wide_min();
   const Triple* dtr = E.dtr();
   const Fq* dcoef = E.dcoef();
   Fq *cin = E.cbuf[S.cur], *cout = E.cbuf[S.cur ^ 1];
@@ -789,7 +768,7 @@ static int round_single(const LayerEnv& E, LayerState& S, size_t log_len, bool l
     KScope ks(ctx, "spark_layer_round", layer_bytes, 0.0, fqm_w);
     hipLaunchKernelGGL(k_layer_round_wide<256>, dim3(K), dim3(256), 0, s, dtr, dcoef, (int)nc, (int)nt, (int)log_len,
                        pending ? 1 : 0, S.r[0], cin, cout, E.part, ctx->d_counter, ctx->d_mbox, ++ctx->mbox_seq);
-  } else if (kn.quad) {  // a quad per element, about one element per quad
+  } else if (knob::layer_quad()) {  // a quad per element, about one element per quad
     const size_t Wd = nt * len;
     BS = Wd <= 16 ? 64 : 256;
     K = (unsigned)std::min<size_t>((Wd * 4 + BS - 1) / BS, 2048);
@@ -799,16 +778,17 @@ static int round_single(const LayerEnv& E, LayerState& S, size_t log_len, bool l
   // the layer's last round in one workgroup also posts every vector's two entries: the host then folds the
   // final claims with the round's challenge, and no close launch (another round trip) follows
   const bool ends =
-      close_after && log_len == 0 && kn.quad && K == 1 && 3 + 6 * nt <= kMboxScalars && !wide && kn.ends_on;
+      close_after && log_len == 0 && knob::layer_quad() && K == 1 && 3 + 6 * nt <= kMboxScalars && !wide &&
+      knob::layer_ends();
   if (!wide) {
     // Fq products per element: lanes 0..2 fold their vector's two entries (6) and form k A B C at their point (9)
     KScope ks(ctx, "spark_layer_round", layer_bytes, 0.0, (double)nt * (double)len * (pending ? 15.0 : 9.0));
     const int lg = (int)log_len, df = pending ? 1 : 0;
     const uint32_t seq = ++ctx->mbox_seq;
-    if (kn.quad && BS == 64)
+    if (knob::layer_quad() && BS == 64)
       hipLaunchKernelGGL(k_layer_round_q<64>, dim3(K), dim3(64), 0, s, dtr, dcoef, (int)nt, lg, df, S.r[0], cin, cout,
                          E.part, ctx->d_counter, ctx->d_mbox, seq, nullptr, ends ? 1 : 0);
-    else if (kn.quad)
+    else if (knob::layer_quad())
       hipLaunchKernelGGL(k_layer_round_q<256>, dim3(K), dim3(256), 0, s, dtr, dcoef, (int)nt, lg, df, S.r[0], cin, cout,
                          E.part, ctx->d_counter, ctx->d_mbox, seq, nullptr, ends ? 1 : 0);
     else if (BS == 64)
@@ -851,7 +831,7 @@ static int round_pair(const LayerEnv& E, LayerState& S, size_t log_len, FqV* fin
   if (S.npend > 2) return set_err(ctx, SPG_E_ARG, "paired layer round after a tripled one");
   const int lgj = (int)log_len - 1;  // round j's half length 2^lgj; round j + 1's 2^(lgj - 1)
   const size_t nt = S.nt, h = (size_t)1 << (lgj - 1), lanes = 16 * nt * h;
-  const int BSp = lanes <= 64 || layer_knobs().pair_bs == 64 ? 64 : 256;
+  const int BSp = lanes <= 64 || knob::pair_bs() == 64 ? 64 : 256;
   const unsigned Kp = (unsigned)((lanes + BSp - 1) / BSp);
   const bool ends = log_len == 2;  // the layer's last pair posts every vector's 2 x 2 corners
   const int nf = S.npend;
@@ -1046,10 +1026,9 @@ static int run_rounds(const LayerEnv& E, LayerState& S, size_t log_len, bool loc
     S.shared = true;
     return comm_sum_fq(E.ctx, E.sh, status, none, 3);
   }
-  const LayerKnobs& kn = layer_knobs();
-  const bool multi = kn.quad && !local && close_after;
+  const bool multi = knob::layer_quad() && !local && close_after;
   while (log_len > 0) {
-    const int step = plan_step(kn, S.nt, S.ngroups, multi, log_len, S.npend);
+    const int step = plan_step(S.nt, S.ngroups, multi, log_len, S.npend);
     if (step == 0) return set_err(E.ctx, SPG_E_ARG, "layer rounds: no launch plan");
     bool done = false;
     const int rc = step == 3   ? round_triple(E, S, log_len, fin, &done)
@@ -1070,7 +1049,7 @@ static int layer_setup(const LayerEnv& E, const std::vector<Triple>& tr, const F
   spg_ctx* ctx = E.ctx;
   KBlob blob;  // 2.3 KB on the stack (contexts on other threads prove concurrently)
   const size_t blob_bytes = E.tr_bytes + coeffs.size() * sizeof(Fq);
-  const bool in_args = blob_bytes <= sizeof(blob.w) && !getenv("SPG_LAYER_DESC_COPY");
+  const bool in_args = blob_bytes <= sizeof(blob.w) && !knob::layer_desc_copy();
   if (in_args) {
     memset(blob.w, 0, E.tr_bytes);
     memcpy(blob.w, tr.data(), tr.size() * sizeof(Triple));

@@ -13,6 +13,7 @@
 #include <string.h>
 
 #include "cube.hpp"
+#include "knobs.hpp"
 #include "lds.hpp"
 #include "qsum.hpp"
 #include "sumcheck.hpp"
@@ -1086,14 +1087,12 @@ __global__ void __launch_bounds__(256) k_phase2_fold2x(P2PairArgs A) {
 // ---------------------------------------------------------------- host launchers
 // round evaluations over at most this many domain points take the quad form (SPG_SC_QUAD_MAX; 0 = never): below it
 // the chip is not full and a point's chain of products sets the time
-static size_t sc_quad_max() {
-  static const size_t m = getenv("SPG_SC_QUAD_MAX") ? (size_t)atol(getenv("SPG_SC_QUAD_MAX")) : ((size_t)1 << 16);
-  return m;
-}
+static size_t sc_quad_max() { return (size_t)knob::sc_quad_max(); }
 // workgroups of a round's evaluation: one per 256 threads of work, at most SPG_SC_GRID (default 1024, <= kScGridMax:
 // the partials buffer)
 static int grid_for(uint32_t total) {
-  static const int cap = getenv("SPG_SC_GRID") ? std::max(1, std::min(kScGridMax, atoi(getenv("SPG_SC_GRID")))) : 1024;
+  static_assert(kScGridMax == 4096, "the SPG_SC_GRID row of knobs.hpp clamps to kScGridMax");
+  const int cap = knob::sc_grid();
   int nb = (int)((total + 255) / 256);
   if (nb > cap) nb = cap;
   return nb < 1 ? 1 : nb;
@@ -1118,7 +1117,7 @@ int dev_eq_table(spg_ctx* ctx, const Fq* r, int ell, Fq* out, const KBlob* blob,
   const KBlob& bl = blob ? *blob : none;
   uint32_t* bd = (uint32_t*)blob_dst;
   // SPG_EQ_LDS=0 restores the one-lane-per-entry kernel (A/B switch)
-  static const bool lds_on = !getenv("SPG_EQ_LDS") || atoi(getenv("SPG_EQ_LDS")) != 0;
+  const bool lds_on = knob::eq_lds();
   auto launch = [&](const FqArg32& ra, Fq* o, size_t cnt, bool with_blob) {
     const dim3 g((unsigned)((cnt + 255) / 256));
     if (lds_on) {
@@ -1153,8 +1152,7 @@ int dev_eq_table(spg_ctx* ctx, const Fq* r, int ell, Fq* out, const KBlob* blob,
 }
 
 int dev_eq_tables(spg_ctx* ctx, const EqJob* jobs, int nj) {
-  static const bool lds_on = !getenv("SPG_EQ_LDS") || atoi(getenv("SPG_EQ_LDS")) != 0;
-  static const bool multi_on = !getenv("SPG_EQ_MULTI") || atoi(getenv("SPG_EQ_MULTI")) != 0;
+  const bool lds_on = knob::eq_lds(), multi_on = knob::eq_multi();
   EqTablesArg a;
   a.nj = 0;
   uint32_t blocks = 0;
@@ -1264,9 +1262,8 @@ int phase1_eval(spg_ctx* ctx, const PqxDev& T, int mode, size_t proof_len, size_
   const bool quad = dom <= sc_quad_max();
   const int nb = quad ? grid_for((uint32_t)(4 * dom)) : grid_for((uint32_t)dom);
   // x-mode rounds over rows of >= 128 points: the row-factored kernel, J points per lane (SPG_P1_ROWS=0: off)
-  static const bool rows_on = !getenv("SPG_P1_ROWS") || atoi(getenv("SPG_P1_ROWS")) != 0;
   int J = 0;
-  if (rows_on && !quad && mode == MODE_X && (!fold || fold->arg.fmode == MODE_X)) {
+  if (knob::p1_rows() && !quad && mode == MODE_X && (!fold || fold->arg.fmode == MODE_X)) {
     size_t mn = ~(size_t)0;
     for (size_t p = 0; p < P; p++) mn = std::min(mn, (size_t)v[p].sc_ni);
     J = mn >= 512 ? 8 : (mn >= 256 ? 4 : (mn >= 128 ? 2 : 0));

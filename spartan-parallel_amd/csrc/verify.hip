@@ -20,6 +20,7 @@
 #include <string>
 
 #include "hostpoly.hpp"
+#include "knobs.hpp"
 #include "pe_plan.hpp"
 #include "proto.hpp"
 #include "snark_shape.hpp"
@@ -332,10 +333,7 @@ struct V {
   // ---- row-commitment MSMs sum_i L_i C_i (PolyEvalProof::verify*): the host Pippenger above, or with
   // SPG_VERIFY_VMSM=1 (read once; default off) the variable-base pipeline of msm_var.hip -- a polynomial's
   // commitments upload once and the L vectors of one batch go through spg_msm_var_batch
-  static bool vmsm_on() {
-    static const bool on = getenv("SPG_VERIFY_VMSM") && atoi(getenv("SPG_VERIFY_VMSM")) != 0;
-    return on;
-  }
+  static bool vmsm_on() { return knob::verify_vmsm(); }
   std::vector<HExt> row_msms_dev(const std::vector<const FqV*>& Ls, const PolyComm& comm) {
     std::vector<HExt> out(Ls.size(), h::hext_identity());
     if (comm.empty() || Ls.empty()) return out;
@@ -734,7 +732,7 @@ struct SnarkVerifier : V {
     const size_t np = lg2(npow2(n)), nq = lg2(max_np), nx = lg2(num_cons), nw = lg2(nws), ny = lg2(max_ni);
     const FqV tau_p = t.challenges("challenge_tau_p", np), tau_q = t.challenges("challenge_tau_q", nq),
               tau_x = t.challenges("challenge_tau_x", nx);
-    if (getenv("SPG_DEBUG_TR")) fprintf(stderr, "[verify] r1cs n=%zu np=%zu nq=%zu nx=%zu tau_x0 %08x\n", n, np, nq, nx, tau_x[0].l[0]);
+    if (knob::debug_tr()) fprintf(stderr, "[verify] r1cs n=%zu np=%zu nq=%zu nx=%zu tau_x0 %08x\n", n, np, nq, nx, tau_x[0].l[0]);
     const Pt claim1 = compress(commit1(g, g.gens_1, fq_zero(), fq_zero()));
     Pt post1;
     FqV rx_all;
@@ -1087,7 +1085,7 @@ struct SnarkCheck {
   bool append_commitments() {
     auto app = [&](const PolyComm& c) { append_polycomm(t, "poly_commitment", c); };
     const Fq tau = t.challenge("challenge_tau"), r = t.challenge("challenge_r");
-    if (getenv("SPG_DEBUG_TR")) fprintf(stderr, "[verify] tau %08x r %08x\n", tau.l[0], r.l[0]);
+    if (knob::debug_tr()) fprintf(stderr, "[verify] tau %08x r %08x\n", tau.l[0], r.l[0]);
     c_w0 = commit_vec(v.ctx, gpc, perm_w0(tau, r, niu, num_ios));
     app(c_w0);
     app(pf.perm_exec_comm_w2_list);

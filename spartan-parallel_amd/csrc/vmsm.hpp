@@ -60,6 +60,7 @@ SPG_HD Niels vmsm_niels_affine(const Ext& P) {
 
 #include "hcurve.hpp"
 #include "hpool.hpp"
+#include "knobs.hpp"
 
 namespace spg {
 
@@ -71,7 +72,7 @@ namespace spg {
 // above their neighbours at every swept size and no such model has that dip: c = 8 is best at 2^16, 2^17 and 2^18 and
 // within 1 % of the best at 2^19, c = 11 at 2^20 (and stays above it: not swept). SPG_VMSM_C forces c.
 inline int vmsm_choose_c(size_t N, size_t B) {
-  static const int forced = getenv("SPG_VMSM_C") ? atoi(getenv("SPG_VMSM_C")) : 0;
+  const int forced = knob::vmsm_c();
   if (forced) return forced < kVmsmCMin ? kVmsmCMin : (forced > kVmsmCMax ? kVmsmCMax : forced);
   const size_t n = N / (B ? B : 1);
   if (n < ((size_t)1 << 12)) return 4;
