@@ -134,9 +134,24 @@ int spg_pqx_new(spg_ctx* ctx, const uint64_t* z_mont, size_t num_instances, cons
                 size_t max_num_proofs, size_t num_witness_secs, const size_t* num_inputs, size_t max_num_inputs,
                 spg_pqx** out);
 int spg_pqx_free(spg_ctx* ctx, spg_pqx* h);
+/* DensePolynomialPqx::new_rev (:67-111) on z in the standard (p, q, w, x) order, the layout spg_r1cs_multiply_vec_block
+ * takes as z_mat: the table holds Z[p][rev(q)][w][rev(x)] = z[p][q][w][x], rev_bits over lg num_proofs[p] and
+ * lg num_inputs[p] bits; num_witness_secs sections are stored and the table's section count is the next power of two
+ * (:106). Limits as spg_pqx_new. The reordering runs on the device; the _buf form reads the shape's total scalars at
+ * `offset` of a resident vector (past its end: SPG_E_ARG) and makes no host copy. */
+int spg_pqx_new_rev(spg_ctx* ctx, const uint64_t* z_mont, size_t num_instances, const size_t* num_proofs,
+                    size_t max_num_proofs, size_t num_witness_secs, const size_t* num_inputs, size_t max_num_inputs,
+                    spg_pqx** out);
+int spg_pqx_new_rev_buf(spg_ctx* ctx, const spg_buf* z, size_t offset, size_t num_instances, const size_t* num_proofs,
+                        size_t max_num_proofs, size_t num_witness_secs, const size_t* num_inputs,
+                        size_t max_num_inputs, spg_pqx** out);
 /* bound_poly(r, mode) (:180-289): mode 1 = first p variable, 2 = q, 3 = w, 4 = x; mode 1 before every q and x
  * variable is bound is SPG_E_ARG (the reference's assert_eq! in bound_poly_p, :206-207) */
 int spg_pqx_bound(spg_ctx* ctx, spg_pqx* h, const uint64_t* r_mont, int mode);
+/* bound_poly_vars_rq (:300-304): n calls of spg_pqx_bound(.., mode 2) with rq[0], rq[1], .. in order; n larger than
+ * the q variables left (lg max_num_proofs) is SPG_E_ARG. With n >= 2, one pass over the table against eq(rq) instead of
+ * n; an instance left with one row keeps the sum in row 0 and its other rows as they were. */
+int spg_pqx_bound_rq(spg_ctx* ctx, spg_pqx* h, const uint64_t* rq_mont, size_t n);
 /* evaluate(r_p, r_q, r_w, r_x) (:320-333): a clone bound by r_x, r_w, r_q, r_p, then index(0, 0, 0, 0) */
 int spg_pqx_evaluate(spg_ctx* ctx, const spg_pqx* h, const uint64_t* rp, size_t np, const uint64_t* rq, size_t nq,
                      const uint64_t* rw, size_t nw, const uint64_t* rx, size_t nx, uint64_t* out_mont);
@@ -151,11 +166,14 @@ int spg_pqx_download(spg_ctx* ctx, const spg_pqx* h, uint64_t* z_mont);
  * z[p][q][c / max_num_inputs][c % max_num_inputs], zero past num_inputs[p] -- into three new DensePolynomialPqx tables
  * Az, Bz, Cz in new_rev order (num_proofs, max_num_proofs; num_cons, max_num_cons of the instance; one w section).
  * num_proofs[p] and the instance's num_cons are powers of two; 1..8 witness sections. */
-/* One x or q round of the R1CS proof's phase-1 sumcheck (prove_cubic_with_additive_term_disjoint_rounds,
+/* One x, q or p round of the R1CS proof's phase-1 sumcheck (prove_cubic_with_additive_term_disjoint_rounds,
  * src/sumcheck.rs:1173-1245, comb A (B C - D)): out3 = (eval_point_0, eval_point_2, eval_point_3) over the eq
  * factors Ap, Aq, Ax in their current lengths (instance_len = |Ap|; an x round (mode 4) has cons_len = |Ax| / 2, a q
- * round (mode 2, once |Ax| = 1) proof_len = |Aq| / 2) and the tables B, C, D (one shape, one witness section) in
- * their current state. The caller then binds Ax or Aq (spg_buf_bound_top) and B, C, D (spg_pqx_bound) with r_j. */
+ * round (mode 2, once |Ax| = 1) proof_len = |Aq| / 2, a p round (mode 1, once |Ax| = |Aq| = 1 and with |Ap| >= 2)
+ * instance_len = |Ap| / 2: the loop runs over p < min(instance_len, instances), the high half is Ap[p + instance_len]
+ * and the tables' instance p + num_instances / 2, zero where it does not exist) and the tables B, C, D (one shape,
+ * one witness section) in their current state. The caller then binds Ax, Aq or Ap (spg_buf_bound_top) and B, C, D
+ * (spg_pqx_bound) with r_j. Mode 1 with x or q variables left is SPG_E_ARG. */
 int spg_phase1_round_evals(spg_ctx* ctx, const spg_buf* Ap, const spg_buf* Aq, const spg_buf* Ax, const spg_pqx* B,
                            const spg_pqx* C, const spg_pqx* D, int mode, uint64_t* out3_mont);
 /* One y (mode 4), w (mode 3) or p (mode 1) round of the R1CS proof's phase-2 sumcheck (prove_cubic_disjoint_rounds,
@@ -169,6 +187,59 @@ int spg_r1cs_multiply_vec_block(spg_ctx* ctx, const struct spg_r1cs_inst* inst, 
                                 const size_t* num_proofs, size_t max_num_proofs, const size_t* num_inputs,
                                 size_t max_num_inputs, size_t num_witness_secs, const uint64_t* z_mont, spg_pqx** Az,
                                 spg_pqx** Bz, spg_pqx** Cz);
+/* R1CSInstance::compute_eval_table_sparse_disjoint_rounds (src/r1csinstance.rs:484-534, src/sparse_mlpoly.rs:524-541)
+ * on evals_rx = eq(rx) (at least max_num_cons scalars): three new tables A, B, C of P' instances, P' the handle's own
+ * matrix count (1 for a shared instance: "Length of output follows self.num_instances NOT num_instances"), each
+ * DensePolynomialPqx::new(evals_M, [1; P'], 1, num_inputs[..P'], max_num_inputs): entry [p][0][w][i] =
+ * sum_{e in M_p, col_e = w max_num_inputs + i} evals_rx[row_e] val_e, x in natural order. num_instances is the
+ * handle's count unless that is 1; next_pow2(num_witness_secs) max_num_inputs = num_vars; num_inputs[p] powers of two
+ * <= max_num_inputs; 1..8 sections (else SPG_E_ARG). An entry whose column lies outside [w max_num_inputs,
+ * w max_num_inputs + num_inputs[p]) for every w < num_witness_secs makes the reference index past its vector; here
+ * it contributes nothing, as in spg_r1cs_prove. */
+int spg_r1cs_eval_tables(spg_ctx* ctx, const struct spg_r1cs_inst* inst, size_t num_instances, size_t num_witness_secs,
+                         size_t max_num_inputs, const size_t* num_inputs, const spg_buf* evals_rx, spg_pqx** A,
+                         spg_pqx** B, spg_pqx** C);
+/* prove_abc_gen (src/r1csproof.rs:430-465): r_A A + r_B B + r_C C of the tables above put through new_rev (x
+ * bit-reversed), in one pass; what spg_r1cs_prove builds before phase 2. Same arguments and checks. */
+int spg_r1cs_abc_poly(spg_ctx* ctx, const struct spg_r1cs_inst* inst, size_t num_instances, size_t num_witness_secs,
+                      size_t max_num_inputs, const size_t* num_inputs, const spg_buf* evals_rx, const uint64_t* rA_mont,
+                      const uint64_t* rB_mont, const uint64_t* rC_mont, spg_pqx** ABC);
+/* The two ZK sumchecks of R1CSProof::prove and their verifier on caller tables. gens supplies gens_1 and gens_4 of
+ * R1CSSumcheckGens (src/r1csproof.rs:54-69); claim / blind_claim NULL mean zero (phase one passes &ZERO). The tables
+ * are bound in place, as the reference's &mut arguments: afterwards every eq vector has length 1 and every table
+ * len() == 1. proof receives bincode(ZKSumcheckInstanceProof); *len = 24 + 328 rounds whether or not it fits, and a
+ * cap below that is SPG_E_ARG with transcript, tape and tables untouched, as is every other SPG_E_ARG. r receives the
+ * challenges, blind_post = blinds_evals[last]. Zero rounds is SPG_E_ARG (the reference would index blinds_evals[-1]).
+ * Single-rank: spg_set_comm does not shard these.
+ * spg_zk_phase1_prove = prove_cubic_with_additive_term_disjoint_rounds (src/sumcheck.rs:1067-1380) with comb
+ * A (B C - D) as prove_phase_one calls it (src/r1csproof.rs:83-130): nx x rounds, nq q rounds, np p rounds over
+ * |Ax| = 2^nx, |Aq| = 2^nq, |Ap| = 2^np >= instances and unbound B, C, D of one shape and one witness section with
+ * max_num_inputs = 2^nx, max_num_proofs = 2^nq (num_cons / num_proofs of the reference are the tables' own sizes);
+ * claims4 = (Ap[0] Aq[0] Ax[0], B, C, D at index (0, 0, 0, 0)). */
+struct spg_r1cs_gens;
+struct spg_random_tape;
+int spg_zk_phase1_prove(spg_ctx* ctx, const struct spg_r1cs_gens* gens, const uint64_t* claim_mont,
+                        const uint64_t* blind_claim_mont, size_t nx, size_t nq, size_t np, spg_buf* Ap, spg_buf* Aq,
+                        spg_buf* Ax, spg_pqx* B, spg_pqx* C, spg_pqx* D, struct spg_transcript* t,
+                        struct spg_random_tape* tape, uint8_t* proof, size_t cap, size_t* len, uint64_t* r_mont,
+                        uint64_t* claims4_mont, uint64_t* blind_post_mont);
+/* spg_zk_phase2_prove = prove_cubic_disjoint_rounds (src/sumcheck.rs:788-1065) with comb A B C (src/r1csproof.rs:
+ * 132-174): ny y rounds, nw w rounds, np p rounds over |eq| = 2^np >= instances, ABC (one instance when single_inst,
+ * else one per instance; not bound in the p rounds when single) and Z, both with q bound (spg_pqx_bound_rq) and y, w
+ * unbound: max_num_inputs = 2^ny, num_witness_secs = 2^nw; num_witness_secs is the reference's argument (the sections
+ * that exist). claims3 = (eq[0], ABC, Z at index (0, 0, 0, 0)). */
+int spg_zk_phase2_prove(spg_ctx* ctx, const struct spg_r1cs_gens* gens, const uint64_t* claim_mont,
+                        const uint64_t* blind_claim_mont, size_t ny, size_t nw, size_t np, int single_inst,
+                        size_t num_witness_secs, spg_buf* eq, spg_pqx* ABC, spg_pqx* Z, struct spg_transcript* t,
+                        struct spg_random_tape* tape, uint8_t* proof, size_t cap, size_t* len, uint64_t* r_mont,
+                        uint64_t* claims3_mont, uint64_t* blind_post_mont);
+/* ZKSumcheckInstanceProof::verify (src/sumcheck.rs:94-189): 0 with comm_claim_post (the last comm_eval) and the
+ * num_rounds challenges in r, or SPG_E_VERIFY -- malformed, truncated or trailing bytes, a round-count mismatch and a
+ * point that does not decompress included, as in spg_snark_verify. degree_bound other than 3 is SPG_E_ARG (both call
+ * sites pass 3, and gens_4 holds 4 generators), as is num_rounds = 0. */
+int spg_zk_sumcheck_verify(spg_ctx* ctx, const struct spg_r1cs_gens* gens, const uint8_t* comm_claim, size_t num_rounds,
+                           size_t degree_bound, struct spg_transcript* t, const uint8_t* proof, size_t proof_len,
+                           uint8_t* comm_claim_post, uint64_t* r_mont);
 /* -- memory checking and the grand-product argument on caller vectors (csrc/prodc.hip): what SparseMatPolyEvalProof
  * runs between its commitments (Layers::new, ProductLayerProof::prove; src/sparse_mlpoly.rs:689-736, 1105-1356), one
  * call at a time. Single-rank: spg_set_comm does not shard these. */

@@ -21,6 +21,7 @@
 #include "proto.hpp"
 #include "lds.hpp"
 #include "sumcheck.hpp"
+#include "zk_rounds.hpp"
 
 
 // R1CSInstance resident in HBM: per matrix instance p, CSR of A_p, B_p, C_p (SpMV) and one merged CSC
@@ -220,10 +221,14 @@ struct AbcDesc {
 };
 
 // ABC[p][w][x_rev] = sum_{M in A,B,C} r_M * sum_{e in M_p, col_e = w*Y + x} eq_rx[row_e] * val_e
+// SPLIT (spg_r1cs_eval_tables): the three per-matrix sums themselves, A[p][w][x] into ABC, B's into outB, C's into
+// outC, x in natural order (DensePolynomialPqx::new, not new_rev), no weights
+template <bool SPLIT>
 __global__ void __launch_bounds__(256) k_abc(const AbcDesc* __restrict__ ad, int Pm, const MatDesc* __restrict__ md,
                                              const uint32_t* __restrict__ colptr, const uint32_t* __restrict__ crow,
                                              const Fq* __restrict__ cval, const Fq* __restrict__ eq, uint32_t Y,
-                                             Fq rA, Fq rB, Fq rC, Fq* __restrict__ ABC, uint64_t total) {
+                                             Fq rA, Fq rB, Fq rC, Fq* __restrict__ ABC, Fq* __restrict__ outB,
+                                             Fq* __restrict__ outC, uint64_t total) {
   uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x;
   if (t >= total) return;
   int p = find_desc(ad, Pm, t);
@@ -240,6 +245,13 @@ __global__ void __launch_bounds__(256) k_abc(const AbcDesc* __restrict__ ad, int
     if (tag == 0) acc[0] = fq_add(acc[0], v);
     else if (tag == 1) acc[1] = fq_add(acc[1], v);
     else acc[2] = fq_add(acc[2], v);
+  }
+  if (SPLIT) {
+    const size_t o = d.out_off + (size_t)w * d.ni + i;
+    ABC[o] = acc[0];
+    outB[o] = acc[1];
+    outC[o] = acc[2];
+    return;
   }
   Fq r = fq_add(fq_add(fq_mul(rA, acc[0]), fq_mul(rB, acc[1])), fq_mul(rC, acc[2]));
   ABC[d.out_off + (size_t)w * d.ni + brev(i, d.lg_ni)] = r;
@@ -363,108 +375,7 @@ __global__ void __launch_bounds__(256) k_sum_segments(const Fq* __restrict__ par
 static size_t p1_pair_max() { return std::min<size_t>(kP1PairMax, (size_t)knob::p1_pair_max()); }
 static size_t p2_pair_max() { return std::min<size_t>(kP1PairMax, (size_t)knob::p2_pair_max()); }
 
-// ZK sumcheck round bookkeeping shared by phase 1 and phase 2 (sumcheck.rs:1247-1370).
-// The RandomTape is a transcript that only ever absorbs labels, so the values a round draws do not depend on
-// the proof: init() draws blinds_poly / blinds_evals as the reference does, then reads every round's
-// DotProductProof randomness (d_vec, r_delta, r_beta) from a copy of the tape at that position and computes,
-// in one host burst, the points that depend on randomness alone (blind * h terms, delta). The rounds then
-// commit only their data-dependent terms, and the tape continues from the copy's final state after the last
-// round (no other draw happens between the rounds), so proofs are byte-identical.
-struct ZKRounds {
-  FqV blinds_poly, blinds_evals;
-  Fq claim, blind_claim;
-  Pt comm_claim;
-  ZKSumcheckP out;
-  FqV poly;
-  Pt comm_poly;
-  std::vector<DotPre> pre;
-  std::vector<h::HExt> hp, he;  // blinds_poly[j] * h (gens_4), blinds_evals[j] * h (gens_1)
-  Tape tape_end{"", fq_zero()};
-  bool ahead = false;
-  void init(ProverGens& g, Tape& tape, size_t rounds, const Fq& c, const Fq& b) {
-    blinds_poly = tape.vec("blinds_poly", rounds);
-    blinds_evals = tape.vec("blinds_evals", rounds);
-    claim = c;
-    blind_claim = b;
-    ahead = knob::tape_ahead() && rounds > 0 && g.gens_4.G.size() == 4;
-    if (!ahead) {
-      comm_claim = commit_batch(g, {CJob(g.gens_1, {c}, b)})[0];
-      return;
-    }
-    tape_end = tape;
-    pre.resize(rounds);
-    for (size_t j = 0; j < rounds; j++) {
-      pre[j].d = tape_end.vec("d_vec", 4);
-      pre[j].r_delta = tape_end.scalar("r_delta");
-      pre[j].r_beta = tape_end.scalar("r_beta");
-    }
-    hp.resize(rounds);
-    he.resize(rounds);
-    // jobs: comm_claim, then per round blinds_poly h4, blinds_evals h1, r_beta h1, delta (d G4 + r_delta h4)
-    std::vector<std::pair<std::vector<size_t>, FqV>> jobs;
-    jobs.push_back({{g.gens_1.G[0], g.gens_1.h}, {c, b}});
-    for (size_t j = 0; j < rounds; j++) {
-      jobs.push_back({{g.gens_4.h}, {blinds_poly[j]}});
-      jobs.push_back({{g.gens_1.h}, {blinds_evals[j]}});
-      jobs.push_back({{g.gens_1.h}, {pre[j].r_beta}});
-      std::vector<size_t> idx(g.gens_4.G.begin(), g.gens_4.G.end());
-      idx.push_back(g.gens_4.h);
-      FqV sc = pre[j].d;
-      sc.push_back(pre[j].r_delta);
-      jobs.push_back({idx, sc});
-    }
-    g.host.run(jobs, nullptr, [&](size_t k, const h::HExt& sum) {
-      if (k == 0) {
-        comm_claim = compress(sum);
-        return;
-      }
-      const size_t j = (k - 1) / 4;
-      switch ((k - 1) % 4) {
-        case 0: hp[j] = sum; break;
-        case 1: he[j] = sum; break;
-        case 2: pre[j].rbh = sum; break;
-        default: pre[j].delta = compress(sum);
-      }
-    });
-  }
-  // commit the round polynomial and draw r_j
-  Fq begin(ProverGens& g, Tr& t, size_t j, const Fq e[3]) {
-    Fq ev[4] = {e[0], fq_sub(claim, e[0]), e[1], e[2]};
-    poly = uni_from_evals3(ev);
-    if (ahead)
-      comm_poly = g.host.commit_many_plus({{g.gens_4.G, poly}}, &hp[j])[0];
-    else
-      comm_poly = commit_batch(g, {CJob(g.gens_4, poly, blinds_poly[j])})[0];
-    t.point("comm_poly", comm_poly);
-    out.comm_polys.push_back(comm_poly);
-    return t.challenge("challenge_nextround");
-  }
-  void finish(ProverGens& g, Tr& t, Tape& tape, size_t j, const Fq& r_j) {
-    Fq eval = uni_eval(poly, r_j);
-    Pt comm_eval = ahead ? g.host.commit_many_plus({{{g.gens_1.G[0]}, {eval}}}, &he[j])[0]
-                         : commit_batch(g, {CJob(g.gens_1, {eval}, blinds_evals[j])})[0];
-    t.point("comm_claim_per_round", comm_claim);
-    t.point("comm_eval", comm_eval);
-    FqV w = t.challenges("combine_two_claims_to_one", 2);
-    Fq target = fq_add(fq_mul(w[0], claim), fq_mul(w[1], eval));
-    Fq blind_sc = j == 0 ? blind_claim : blinds_evals[j - 1];
-    Fq blind = fq_add(fq_mul(w[0], blind_sc), fq_mul(w[1], blinds_evals[j]));
-    size_t n = poly.size();
-    FqV a(n);
-    Fq pw = fq_one();
-    for (size_t k = 0; k < n; k++) {
-      Fq a_sc = k == 0 ? fq_dbl(fq_one()) : fq_one();
-      a[k] = fq_add(fq_mul(w[0], a_sc), fq_mul(w[1], pw));
-      pw = fq_mul(pw, r_j);
-    }
-    out.proofs.push_back(dotproduct_prove(g, g.gens_1, g.gens_4, t, tape, poly, blinds_poly[j], a, target, blind,
-                                          &comm_poly, ahead ? &pre[j] : nullptr));
-    if (ahead && j + 1 == pre.size()) tape = tape_end;  // past every round's draws
-    claim = eval;
-    comm_claim = comm_eval;
-    out.comm_evals.push_back(comm_eval);
-  }
-};
+// (ZKRounds, the ZK sumcheck round bookkeeping shared by phase 1 and phase 2: zk_rounds.hpp)
 
 // workspace slots used here (msm.hip uses 0..12, proto.hip 20..22)
 enum {
@@ -1354,8 +1265,9 @@ int Prover::phase2_prep(ZFill& zf) {
     if (!rc) rc = flush_desc();
     if (rc) return rc;
     KScope ks(ctx, "eval_table_abc", 32.0 * btot + 4.0 * btot + 68.0 * visits);
-    hipLaunchKernelGGL(k_abc, dim3(blocks_for(btot)), dim3(256), 0, ctx->stream, dad, (int)Abn, cy.dmd, inst.d_colptr,
-                       inst.d_crow, inst.d_cval, cy.eq_rx, (uint32_t)Y, r_A, r_B, r_C, ABC.d, (uint64_t)btot);
+    hipLaunchKernelGGL(k_abc<false>, dim3(blocks_for(btot)), dim3(256), 0, ctx->stream, dad, (int)Abn, cy.dmd,
+                       inst.d_colptr, inst.d_crow, inst.d_cval, cy.eq_rx, (uint32_t)Y, r_A, r_B, r_C, ABC.d,
+                       (Fq*)nullptr, (Fq*)nullptr, (uint64_t)btot);
     SPG_HIP(ctx, hipGetLastError());
   }
   rc = zf.queue();  // (phase 1 had no rounds)
@@ -2490,5 +2402,116 @@ extern "C" int spg_r1cs_multiply_vec_block(spg_ctx* ctx, const spg_r1cs_inst* in
   *Az = outs[0];
   *Bz = outs[1];
   *Cz = outs[2];
+  return SPG_OK;
+}
+
+// R1CSInstance::compute_eval_table_sparse_disjoint_rounds (src/r1csinstance.rs:484-534, src/sparse_mlpoly.rs:524-541)
+// and prove_abc_gen (src/r1csproof.rs:430-465) as seams on a caller's eq(rx): k_abc over the handle's own matrices,
+// into new spg_pqx tables of one proof row. split: A, B, C apart, x in natural order (DensePolynomialPqx::new);
+// else r_A A + r_B B + r_C C in new_rev order, what the prover's phase2_prep builds.
+static int abc_tables(spg_ctx* ctx, const char* what, const spg_r1cs_inst* inst, size_t num_instances,
+                      size_t num_witness_secs, size_t max_num_inputs, const size_t* num_inputs, const spg_buf* evals_rx,
+                      bool split, const Fq& rA, const Fq& rB, const Fq& rC, spg_pqx** outs) {
+  const std::string w(what);
+  // r1csinstance.rs:498-500, sparse_mlpoly.rs:532
+  if (num_instances == 0 || !(inst->num_instances == 1 || inst->num_instances == num_instances))
+    return set_err(ctx, SPG_E_ARG, w + ": the instance holds 1 or num_instances matrices");
+  if (num_witness_secs == 0 || num_witness_secs > 8) return set_err(ctx, SPG_E_ARG, w + ": 1..8 witness sections");
+  if (!is_pow2(max_num_inputs) || npow2(num_witness_secs) * max_num_inputs != inst->num_vars)
+    return set_err(ctx, SPG_E_ARG, w + ": next_pow2(num_witness_secs) * max_num_inputs must equal num_vars");
+  if (evals_rx->n < inst->max_num_cons) return set_err(ctx, SPG_E_ARG, w + ": evals_rx shorter than max_num_cons");
+  const size_t Pm = inst->num_instances;
+  for (size_t p = 0; p < Pm; p++)
+    if (!is_pow2(num_inputs[p]) || num_inputs[p] > max_num_inputs)
+      return set_err(ctx, SPG_E_ARG, w + ": num_inputs[p] must be powers of two <= max_num_inputs");
+  const std::vector<size_t> cols(num_inputs, num_inputs + Pm);
+  PqxDev shape = pqx_shape(std::vector<size_t>(Pm, 1), num_witness_secs, cols, npow2(Pm), 1, npow2(num_witness_secs),
+                           max_num_inputs);
+  const size_t total = shape.total;
+  if (total >= ((size_t)1 << 31)) return set_err(ctx, SPG_E_ARG, w + ": at most 2^31 entries");
+  std::vector<AbcDesc> ad(Pm);
+  std::vector<MatDesc> md(Pm);
+  for (size_t p = 0; p < Pm; p++) {
+    ad[p].dom_off = ad[p].out_off = shape.off[p];
+    ad[p].pi = (uint32_t)p;
+    ad[p].ni = (uint32_t)num_inputs[p];
+    ad[p].lg_ni = (uint32_t)lg2(num_inputs[p]);
+    ad[p].pad = 0;
+    for (int m = 0; m < 3; m++) md[p].rp[m] = inst->rp_off[3 * p + m];
+    md[p].cp = inst->cp_off[p];
+  }
+  const int n_out = split ? 3 : 1;
+  spg_pqx* h[3] = {nullptr, nullptr, nullptr};
+  void* d_desc = nullptr;
+  const size_t b_ad = Pm * sizeof(AbcDesc), b_md = Pm * sizeof(MatDesc);
+  int rc = 0;
+  if (hipMalloc(&d_desc, b_ad + b_md + 64) != hipSuccess) rc = set_err(ctx, SPG_E_NOMEM, w);
+  for (int k = 0; k < n_out && !rc; k++) {
+    h[k] = new spg_pqx();
+    h[k]->T = shape;
+    if (hipMalloc(&h[k]->T.d, total * sizeof(Fq) + 64) != hipSuccess) rc = set_err(ctx, SPG_E_NOMEM, w + " outputs");
+  }
+  if (!rc) {
+    std::vector<uint8_t> blob(b_ad + b_md);
+    memcpy(blob.data(), ad.data(), b_ad);
+    memcpy(blob.data() + b_ad, md.data(), b_md);
+    uint8_t* dd = (uint8_t*)d_desc;
+    if (hipMemcpy(dd, blob.data(), blob.size(), hipMemcpyHostToDevice) != hipSuccess)
+      rc = set_err(ctx, SPG_E_HIP, w + " upload");
+    if (!rc && total) {
+      timer_start(ctx);
+      const dim3 grid(blocks_for(total));
+      if (split)
+        hipLaunchKernelGGL(k_abc<true>, grid, dim3(256), 0, ctx->stream, (const AbcDesc*)dd, (int)Pm,
+                           (const MatDesc*)(dd + b_ad), inst->d_colptr, inst->d_crow, inst->d_cval, evals_rx->d,
+                           (uint32_t)max_num_inputs, rA, rB, rC, h[0]->T.d, h[1]->T.d, h[2]->T.d, (uint64_t)total);
+      else
+        hipLaunchKernelGGL(k_abc<false>, grid, dim3(256), 0, ctx->stream, (const AbcDesc*)dd, (int)Pm,
+                           (const MatDesc*)(dd + b_ad), inst->d_colptr, inst->d_crow, inst->d_cval, evals_rx->d,
+                           (uint32_t)max_num_inputs, rA, rB, rC, h[0]->T.d, (Fq*)nullptr, (Fq*)nullptr,
+                           (uint64_t)total);
+      timer_stop(ctx);
+      if (hipGetLastError() != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
+        rc = set_err(ctx, SPG_E_HIP, w + " launch");
+      float ms = 0.f;
+      if (!rc && hipEventElapsedTime(&ms, ctx->ev0, ctx->ev1) == hipSuccess) ctx->last_us = ms * 1000.0;
+    }
+  }
+  hipFree(d_desc);
+  if (rc) {
+    for (spg_pqx* x : h)
+      if (x) {
+        hipFree(x->T.d);
+        delete x;
+      }
+    return rc;
+  }
+  for (int k = 0; k < n_out; k++) outs[k] = h[k];
+  return SPG_OK;
+}
+
+extern "C" int spg_r1cs_eval_tables(spg_ctx* ctx, const spg_r1cs_inst* inst, size_t num_instances,
+                                    size_t num_witness_secs, size_t max_num_inputs, const size_t* num_inputs,
+                                    const spg_buf* evals_rx, spg_pqx** A, spg_pqx** B, spg_pqx** C) {
+  if (!ctx || !inst || !num_inputs || !evals_rx || !A || !B || !C) return SPG_E_ARG;
+  spg_pqx* outs[3];
+  const int rc = abc_tables(ctx, "r1cs_eval_tables", inst, num_instances, num_witness_secs, max_num_inputs, num_inputs,
+                            evals_rx, true, fq_zero(), fq_zero(), fq_zero(), outs);
+  if (rc) return rc;
+  *A = outs[0];
+  *B = outs[1];
+  *C = outs[2];
+  return SPG_OK;
+}
+
+extern "C" int spg_r1cs_abc_poly(spg_ctx* ctx, const spg_r1cs_inst* inst, size_t num_instances, size_t num_witness_secs,
+                                 size_t max_num_inputs, const size_t* num_inputs, const spg_buf* evals_rx,
+                                 const uint64_t* rA, const uint64_t* rB, const uint64_t* rC, spg_pqx** ABC) {
+  if (!ctx || !inst || !num_inputs || !evals_rx || !rA || !rB || !rC || !ABC) return SPG_E_ARG;
+  spg_pqx* outs[3];
+  const int rc = abc_tables(ctx, "r1cs_abc_poly", inst, num_instances, num_witness_secs, max_num_inputs, num_inputs,
+                            evals_rx, false, ld_fq(rA), ld_fq(rB), ld_fq(rC), outs);
+  if (rc) return rc;
+  *ABC = outs[0];
   return SPG_OK;
 }

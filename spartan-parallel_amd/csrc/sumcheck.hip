@@ -791,6 +791,30 @@ __global__ void __launch_bounds__(256) k_pqx_bound_q(PqxArgs a, const Fq* __rest
   if (g == 0 && live) T[base] = acc;
 }
 
+// The same sum for a prefix of the q variables (spg_pqx_bound_rq with fewer challenges than an instance has row
+// bits): an instance of np = 2^k rows, k > nq, keeps np' = np / 2^nq rows, out(s', w, x) = sum_{t < 2^nq} E[t]
+// T[t np' + s'][w][x] (t's bits, most significant first, are the row index's top bits: fold j binds the top live bit
+// with r_j); an instance with k <= nq ends in one row as above. One lane per output (d.sc_np live rows x d.step_q
+// sections x d.sc_ni columns); an output reads only the rows congruent to s' mod np' and writes the first of them, so
+// the sum goes in place.
+__global__ void __launch_bounds__(256) k_pqx_bound_q_prefix(PqxArgs a, const Fq* __restrict__ E, int nq, uint32_t total,
+                                                            Fq* __restrict__ T) {
+  const uint32_t t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= total) return;
+  const int p = find_inst(a, t);
+  const PqxInst& d = pinst(a, p);
+  const uint32_t loc = t - d.dom_off, cols = d.sc_ni, nw = d.step_q, rows_out = d.sc_np;
+  const uint32_t x = loc % cols, w = (loc / cols) % nw, s = loc / (cols * nw);
+  const uint32_t terms = d.np / rows_out;  // 2^min(nq, k)
+  int lgt = 0;
+  while ((1u << lgt) < terms) lgt++;
+  const int se = nq - lgt;
+  const size_t row = (size_t)d.anw * d.ani, base = pqx_off(d) + (size_t)s * row + (size_t)w * d.ani + x;
+  Fq acc = fq_zero();
+  for (uint32_t k = 0; k < terms; k++) acc = fq_add(acc, fq_mul(E[(size_t)k << se], T[base + (size_t)k * rows_out * row]));
+  T[base] = acc;
+}
+
 // ---------------------------------------------------------------- plain cubic (product trees), A*B*C
 __global__ void __launch_bounds__(256) k_cubic_eval(const Fq* __restrict__ A, const Fq* __restrict__ B,
                                                     const Fq* __restrict__ C, uint32_t len, Fq* __restrict__ partials,
@@ -1689,6 +1713,41 @@ int pqx_bound_q_all(spg_ctx* ctx, PqxDev& T, const Fq* E, size_t nq) {
     else if (G == 64) hipLaunchKernelGGL(k_pqx_bound_q<64>, grid, dim3(256), 0, ctx->stream, a, E, (int)nq, T.d);
     else if (G == 128) hipLaunchKernelGGL(k_pqx_bound_q<128>, grid, dim3(256), 0, ctx->stream, a, E, (int)nq, T.d);
     else hipLaunchKernelGGL(k_pqx_bound_q<256>, grid, dim3(256), 0, ctx->stream, a, E, (int)nq, T.d);
+    SPG_HIP(ctx, hipGetLastError());
+  }
+  return 0;
+}
+
+int pqx_bound_q_prefix(spg_ctx* ctx, PqxDev& T, const Fq* E, size_t nq) {
+  PqxArgs a;
+  std::vector<PqxInst> v;
+  pqx_fill_args(T, a, v);  // the sizes before the folds
+  const size_t P = std::min(T.num_instances, T.zlen);
+  a.P = (int)P;
+  if (nq == 0 || nq > 31 || (T.max_num_proofs >> nq) == 0)
+    return set_err(ctx, SPG_E_ARG, "q bound: more challenges than q variables");
+  size_t dom = 0, reads = 0;
+  std::vector<size_t> after(T.num_proofs);
+  for (size_t p = 0; p < P; p++) {
+    PqxInst& d = v[p];
+    const size_t nw = std::min(T.num_witness_secs, T.anw[p]), cols = T.num_inputs[p];
+    after[p] = std::max<size_t>(T.num_proofs[p] >> nq, 1);
+    d.dom_off = (uint32_t)dom;
+    d.sc_np = (uint32_t)after[p];
+    d.sc_ni = (uint32_t)cols;
+    d.step_q = (uint32_t)nw;
+    dom += after[p] * nw * cols;
+    reads += T.num_proofs[p] * nw * cols;
+  }
+  if (dom >= ((size_t)1 << 32)) return set_err(ctx, SPG_E_ARG, "q bound: domain");
+  T.max_num_proofs >>= nq;  // the bookkeeping of nq pqx_prepare(MODE_Q) calls
+  T.num_proofs = after;
+  int rc = pqx_pack(ctx, v, a, kWsPqxA);
+  if (rc) return rc;
+  if (dom) {
+    KScope ks(ctx, "sc_fold_q_prefix", 32.0 * (double)(reads + dom));
+    hipLaunchKernelGGL(k_pqx_bound_q_prefix, dim3((unsigned)((dom + 255) / 256)), dim3(256), 0, ctx->stream, a, E,
+                       (int)nq, (uint32_t)dom, T.d);
     SPG_HIP(ctx, hipGetLastError());
   }
   return 0;

@@ -1746,3 +1746,30 @@ int pe_verify_uni(spg_ctx* ctx, ProverGens& g, Tr& t, const Fq& r, const std::ve
                        [&](V& v) { return v.pe_uni_batched(g, p, r, decs(C_Zr), cp, sizes); });
 }
 }  // namespace spg
+
+// ZKSumcheckInstanceProof::verify (src/sumcheck.rs:94-189) on proof bytes, for a caller that keeps the rest of
+// R1CSProof::verify: the Verifier member the whole-proof verifiers run, with the same verdicts on malformed bytes
+extern "C" int spg_zk_sumcheck_verify(spg_ctx* ctx, const spg_r1cs_gens* gens, const uint8_t* comm_claim,
+                                      size_t num_rounds, size_t degree_bound, spg_transcript* t, const uint8_t* proof,
+                                      size_t proof_len, uint8_t* comm_claim_post, uint64_t* r_mont) {
+  if (!ctx || !gens || !comm_claim || !t || (!proof && proof_len) || !comm_claim_post || (!r_mont && num_rounds))
+    return SPG_E_ARG;
+  if (degree_bound != 3)  // both call sites pass 3 (src/r1csproof.rs:733, 829); gens_4 holds 4 generators
+    return set_err(ctx, SPG_E_ARG, "spg_zk_sumcheck_verify: degree_bound must be 3");
+  if (num_rounds == 0) return set_err(ctx, SPG_E_ARG, "spg_zk_sumcheck_verify: 1 or more rounds");
+  ProverGens& g = const_cast<spg_r1cs_gens*>(gens)->g;
+  if (g.gens_4.G.size() != 4 || g.gens_1.G.empty())
+    return set_err(ctx, SPG_E_ARG, "spg_zk_sumcheck_verify: generators without gens_1 / gens_4");
+  ZKSumcheckP p;
+  Rd rdr(proof, proof_len);
+  rd(rdr, p);
+  Pt claim, post;
+  memcpy(claim.b, comm_claim, 32);
+  FqV r;
+  const int rc = pe_verify_run(ctx, t->t, "ZK sumcheck verify", !rdr.bad && rdr.o == rdr.n,
+                               [&](V& v) { return v.zk_sumcheck(g, p, claim, num_rounds, &post, &r); });
+  if (rc) return tr_status(ctx, t->t, rc);
+  memcpy(comm_claim_post, post.b, 32);
+  for (size_t j = 0; j < r.size(); j++) st_fq(r_mont + 4 * j, r[j]);
+  return tr_status(ctx, t->t, SPG_OK);
+}

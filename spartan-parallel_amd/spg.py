@@ -305,13 +305,30 @@ class Buf:
             pass
 
 
+def _z_of_shape(z, num_proofs, num_witness_secs, num_inputs, what):
+    """z as [n, 4] limbs, its length checked against the shape's total before native code reads that many scalars
+    (a shorter array would be read past its end; whether the shape itself is valid is the native call's to say)"""
+    a = _scalars(z)
+    assert len(num_proofs) == len(num_inputs), f"{what}: num_proofs and num_inputs differ in length"
+    total = sum(int(q) * int(num_witness_secs) * int(x) for q, x in zip(num_proofs, num_inputs))
+    assert a.shape[0] >= total, f"{what}: z holds {a.shape[0]} scalars, the shape needs {total}"
+    return a
+
+
+def _pqx_from_handle(ctx, h, P, n):
+    """a Pqx over a native handle of P instances and n allocated scalars"""
+    t = Pqx.__new__(Pqx)
+    t.ctx, t._h, t.P, t.n = ctx, h, P, n
+    return t
+
+
 class Pqx:
     """DensePolynomialPqx (src/custom_dense_mlpoly.rs:22-359) resident in HBM (spg_pqx_*): z holds instance p's
     num_proofs[p] x num_witness_secs x num_inputs[p] scalars in (q_rev, w, x_rev) order, instances concatenated."""
 
     def __init__(self, ctx, z, num_proofs, max_num_proofs, num_witness_secs, num_inputs, max_num_inputs):
         self.ctx = ctx
-        a = _scalars(z)
+        a = _z_of_shape(z, num_proofs, num_witness_secs, num_inputs, "Pqx")
         self.P = len(num_proofs)
         self.n = a.shape[0]
         np_ = np.asarray(num_proofs, dtype=np.uint64)
@@ -320,6 +337,36 @@ class Pqx:
         ctx.check(lib().spg_pqx_new(ctx.handle, _p(a), ctypes.c_size_t(self.P), _p(np_), ctypes.c_size_t(max_num_proofs),
                                     ctypes.c_size_t(num_witness_secs), _p(ni_), ctypes.c_size_t(max_num_inputs),
                                     ctypes.byref(self._h)), "spg_pqx_new")
+
+    @classmethod
+    def new_rev(cls, ctx, z, num_proofs, max_num_proofs, num_witness_secs, num_inputs, max_num_inputs, offset=0):
+        """DensePolynomialPqx::new_rev (src/custom_dense_mlpoly.rs:67-111) of z in the standard (p, q, w, x) order,
+        reordered on the device. z: host scalars (spg_pqx_new_rev), or a Buf read at `offset` with no host copy
+        (spg_pqx_new_rev_buf)."""
+        P = len(num_proofs)
+        assert P == len(num_inputs), "Pqx.new_rev: num_proofs and num_inputs differ in length"
+        np_ = np.asarray(num_proofs, dtype=np.uint64)
+        ni_ = np.asarray(num_inputs, dtype=np.uint64)
+        t = cls.__new__(cls)
+        t.ctx, t.P, t._h = ctx, P, ctypes.c_void_p()
+        t.n = sum(int(q) * int(num_witness_secs) * int(x) for q, x in zip(num_proofs, num_inputs))
+        shape = (ctypes.c_size_t(P), _p(np_), ctypes.c_size_t(max_num_proofs), ctypes.c_size_t(num_witness_secs), _p(ni_),
+                 ctypes.c_size_t(max_num_inputs), ctypes.byref(t._h))
+        if isinstance(z, Buf):
+            ctx.check(lib().spg_pqx_new_rev_buf(ctx.handle, z.handle, ctypes.c_size_t(offset), *shape),
+                      "spg_pqx_new_rev_buf")
+        else:
+            assert offset == 0, "Pqx.new_rev: offset is for a Buf"
+            a = _z_of_shape(z, num_proofs, num_witness_secs, num_inputs, "Pqx.new_rev")
+            ctx.check(lib().spg_pqx_new_rev(ctx.handle, _p(a), *shape), "spg_pqx_new_rev")
+        return t
+
+    def bound_rq(self, rq):
+        """bound_poly_vars_rq (src/custom_dense_mlpoly.rs:300-304): bound(rq[0], 2), bound(rq[1], 2), .. in order; one
+        pass over the table for two or more challenges"""
+        a = _scalars(rq) if len(rq) else np.zeros((1, 4), dtype=np.uint64)
+        self.ctx.check(lib().spg_pqx_bound_rq(self.ctx.handle, self._h, _p(a), ctypes.c_size_t(len(rq))),
+                       "spg_pqx_bound_rq")
 
     def bound(self, r, mode):
         """bound_poly(r, mode): 1 = p, 2 = q, 3 = w, 4 = x (src/custom_dense_mlpoly.rs:180-199)"""
@@ -693,6 +740,7 @@ class R1CSInst:
 
     def __init__(self, ctx, cinst):
         self.ctx = ctx
+        self.num_instances = int(cinst.num_instances)  # the handle's own matrix count (1: shared by every instance)
         self._h = ctypes.c_void_p()
         ctx.check(lib().spg_r1cs_inst_new(ctx.handle, ctypes.byref(cinst), ctypes.byref(self._h)), "spg_r1cs_inst_new")
 
@@ -730,7 +778,7 @@ def r1cs_multiply_vec_block(ctx, inst, num_proofs, max_num_proofs, num_inputs, m
     """R1CSInstance::multiply_vec_block (src/r1csinstance.rs:363-436) -> (Az, Bz, Cz) as resident Pqx tables; z holds
     instance p's num_proofs[p] x num_witness_secs x num_inputs[p] scalars, instances concatenated"""
     P = len(num_proofs)
-    a = _scalars(z)
+    a = _z_of_shape(z, num_proofs, num_witness_secs, num_inputs, "r1cs_multiply_vec_block")
     np_ = np.asarray(num_proofs, dtype=np.uint64)
     ni_ = np.asarray(num_inputs, dtype=np.uint64)
     hs = [ctypes.c_void_p() for _ in range(3)]
@@ -749,6 +797,95 @@ def r1cs_multiply_vec_block(ctx, inst, num_proofs, max_num_proofs, num_inputs, m
         t.n = int(sum(int(x) * int(y) for x, y in zip(npf, nin)))
         out.append(t)
     return tuple(out)
+
+
+def _abc_args(ctx, inst, num_instances, num_witness_secs, max_num_inputs, num_inputs, evals_rx):
+    """the shared arguments of the eval-table entries, the output tables' instance count and their scalars"""
+    Pm = inst.num_instances
+    assert len(num_inputs) >= max(Pm, 1), "num_inputs: one entry per instance"
+    ni_ = np.asarray(num_inputs, dtype=np.uint64)
+    n = sum(int(num_witness_secs) * int(x) for x in num_inputs[:Pm])
+    return ni_, Pm, n, (ctx.handle, inst.handle, ctypes.c_size_t(num_instances), ctypes.c_size_t(num_witness_secs),
+                        ctypes.c_size_t(max_num_inputs), _p(ni_), evals_rx.handle)
+
+
+def r1cs_eval_tables(ctx, inst, num_instances, num_witness_secs, max_num_inputs, num_inputs, evals_rx):
+    """R1CSInstance::compute_eval_table_sparse_disjoint_rounds (src/r1csinstance.rs:484-534) on evals_rx (a Buf, eq(rx)):
+    (A, B, C) as resident Pqx tables of the handle's own matrix count (1 for a shared instance), one proof row, x in
+    natural order"""
+    keep, Pm, n, args = _abc_args(ctx, inst, num_instances, num_witness_secs, max_num_inputs, num_inputs, evals_rx)
+    hs = [ctypes.c_void_p() for _ in range(3)]
+    ctx.check(lib().spg_r1cs_eval_tables(*args, *[ctypes.byref(h) for h in hs]), "spg_r1cs_eval_tables")
+    return tuple(_pqx_from_handle(ctx, h, Pm, n) for h in hs)
+
+
+def r1cs_abc_poly(ctx, inst, num_instances, num_witness_secs, max_num_inputs, num_inputs, evals_rx, rA, rB, rC):
+    """prove_abc_gen (src/r1csproof.rs:430-465): r_A A + r_B B + r_C C of r1cs_eval_tables in new_rev order, one Pqx"""
+    keep, Pm, n, args = _abc_args(ctx, inst, num_instances, num_witness_secs, max_num_inputs, num_inputs, evals_rx)
+    h = ctypes.c_void_p()
+    ctx.check(lib().spg_r1cs_abc_poly(*args, _p(_scalars(rA)), _p(_scalars(rB)), _p(_scalars(rC)), ctypes.byref(h)),
+              "spg_r1cs_abc_poly")
+    return _pqx_from_handle(ctx, h, Pm, n)
+
+
+def zk_proof_len(num_rounds):
+    """bytes of bincode(ZKSumcheckInstanceProof) with num_rounds cubic rounds"""
+    return 24 + 328 * num_rounds
+
+
+def _zk_prove(ctx, what, fn, head, tail, rounds, n_claims, cap):
+    n = ctypes.c_size_t(0)
+    cap = zk_proof_len(rounds) if cap is None else cap
+    out = np.zeros(max(cap, 1), dtype=np.uint8)
+    r = np.zeros((max(rounds, 1), 4), dtype=np.uint64)
+    claims = np.zeros((n_claims, 4), dtype=np.uint64)
+    blind = np.zeros(4, dtype=np.uint64)
+    rc = fn(*head, *tail, _p(out), ctypes.c_size_t(cap), ctypes.byref(n), _p(r), _p(claims), _p(blind))
+    ctx.last_len = int(n.value)
+    ctx.check(rc, what)
+    return out[:n.value].tobytes(), r[:rounds], claims, blind
+
+
+def zk_phase1_prove(ctx, gens, nx, nq, np_, Ap, Aq, Ax, B, C, D, transcript, tape, claim=None, blind_claim=None,
+                    cap=None):
+    """ZKSumcheckInstanceProof::prove_cubic_with_additive_term_disjoint_rounds (src/sumcheck.rs:1067-1380) with comb
+    A (B C - D): Ap, Aq, Ax (Bufs) and B, C, D (Pqx) are bound in place. Returns (proof bytes, r [rounds, 4],
+    claims [4, 4] = (Ap Aq Ax, B, C, D), blinds_evals[last]); ctx.last_len keeps *len."""
+    c, b = _opt(claim), _opt(blind_claim)
+    head = (ctx.handle, gens.handle, _optp(c), _optp(b), ctypes.c_size_t(nx), ctypes.c_size_t(nq), ctypes.c_size_t(np_))
+    tail = (Ap.handle, Aq.handle, Ax.handle, B._h, C._h, D._h, transcript.handle, tape.handle)
+    res = _zk_prove(ctx, "spg_zk_phase1_prove", lib().spg_zk_phase1_prove, head, tail, nx + nq + np_, 4, cap)
+    Ap.n, Aq.n, Ax.n = 1, 1, 1
+    return res
+
+
+def zk_phase2_prove(ctx, gens, ny, nw, np_, single_inst, num_witness_secs, eq, ABC, Z, transcript, tape, claim=None,
+                    blind_claim=None, cap=None):
+    """ZKSumcheckInstanceProof::prove_cubic_disjoint_rounds (src/sumcheck.rs:788-1065) with comb A B C: eq (a Buf),
+    ABC and Z (Pqx, q bound) are bound in place. Returns (proof bytes, r, claims [3, 4] = (eq, ABC, Z),
+    blinds_evals[last])."""
+    c, b = _opt(claim), _opt(blind_claim)
+    head = (ctx.handle, gens.handle, _optp(c), _optp(b), ctypes.c_size_t(ny), ctypes.c_size_t(nw), ctypes.c_size_t(np_),
+            ctypes.c_int(1 if single_inst else 0), ctypes.c_size_t(num_witness_secs))
+    tail = (eq.handle, ABC._h, Z._h, transcript.handle, tape.handle)
+    res = _zk_prove(ctx, "spg_zk_phase2_prove", lib().spg_zk_phase2_prove, head, tail, ny + nw + np_, 3, cap)
+    eq.n = 1
+    return res
+
+
+def zk_sumcheck_verify(ctx, gens, comm_claim, num_rounds, transcript, proof, degree_bound=3):
+    """ZKSumcheckInstanceProof::verify (src/sumcheck.rs:94-189): (accepted, comm_claim_post [32 bytes], r
+    [num_rounds, 4], the failed check's name)"""
+    cc = np.frombuffer(bytes(comm_claim), dtype=np.uint8).copy()
+    assert cc.shape[0] == 32, "comm_claim: a 32-byte compressed point"
+    pb = _bytes_arr(proof)
+    post = np.zeros(32, dtype=np.uint8)
+    r = np.zeros((max(num_rounds, 1), 4), dtype=np.uint64)
+    rc = lib().spg_zk_sumcheck_verify(ctx.handle, gens.handle, _p(cc), ctypes.c_size_t(num_rounds),
+                                      ctypes.c_size_t(degree_bound), transcript.handle, _p(pb),
+                                      ctypes.c_size_t(len(proof)), _p(post), _p(r))
+    ok, why = _verify_result(ctx, rc, "spg_zk_sumcheck_verify")
+    return ok, post.tobytes(), r[:num_rounds], why
 
 
 # ---- memory checking and the grand-product argument on device vectors (csrc/prodc.hip)
