@@ -33,8 +33,22 @@ extern "C" {
 #define SPG_E_VERIFY -6    /* a proof did not verify (spg_last_error names the failed check) */
 #define SPG_E_CALLBACK -7  /* a caller-provided transcript callback returned non-zero */
 
+/* Opaque handles: every one is created, used and freed through the functions below. */
 typedef struct spg_ctx spg_ctx;
 typedef struct spg_gens spg_gens;
+typedef struct spg_buf spg_buf;
+typedef struct spg_pqx spg_pqx;
+typedef struct spg_prodc spg_prodc;
+typedef struct spg_points spg_points;
+typedef struct spg_transcript spg_transcript;
+typedef struct spg_random_tape spg_random_tape;
+typedef struct spg_poly_gens spg_poly_gens;
+typedef struct spg_r1cs_gens spg_r1cs_gens;
+typedef struct spg_r1cs_inst spg_r1cs_inst;
+typedef struct spg_r1cs_witness spg_r1cs_witness;
+typedef struct spg_spark spg_spark;
+typedef struct spg_snark_comp spg_snark_comp; /* ComputationCommitment + ComputationDecommitment */
+typedef struct spg_snark_wit spg_snark_wit;   /* SNARK::prove run-time inputs, resident in HBM */
 
 /* ---- context ------------------------------------------------------------------------------- */
 int spg_init(int device, spg_ctx** out);
@@ -95,7 +109,6 @@ int spg_set_comb(spg_ctx* ctx, int on);
 
 /* ---- device-resident scalar vectors (HBM) ----------------------------------------------------
  * Tables the prover keeps resident between calls (witness polynomials, sumcheck tables). */
-typedef struct spg_buf spg_buf;
 int spg_buf_upload(spg_ctx* ctx, const uint64_t* scalars_mont, size_t n, spg_buf** out);
 int spg_buf_download(spg_ctx* ctx, const spg_buf* b, uint64_t* scalars_mont);
 size_t spg_buf_len(const spg_buf* b);
@@ -124,12 +137,11 @@ int spg_cubic_round_evals(spg_ctx* ctx, const spg_buf* A, const spg_buf* B, cons
  * num_rounds CompressedUniPoly (3 scalars each: the coefficients without the linear term), r the num_rounds
  * challenges, claims (A[0], B[0], C[0]) after the last round */
 int spg_prove_cubic(spg_ctx* ctx, const uint64_t* claim_mont, size_t num_rounds, spg_buf* A, spg_buf* B, spg_buf* C,
-                    struct spg_transcript* t, uint64_t* polys_mont, uint64_t* r_mont, uint64_t* claims_mont);
+                    spg_transcript* t, uint64_t* polys_mont, uint64_t* r_mont, uint64_t* claims_mont);
 /* DensePolynomialPqx (src/custom_dense_mlpoly.rs:22-359), the ragged (p, q_rev, w, x_rev) table of the R1CS proof,
  * resident in HBM. spg_pqx_new = DensePolynomialPqx::new (:45-64) on z_mat already in (p, q_rev, w, x_rev) order:
  * instance p's num_proofs[p] x num_witness_secs x num_inputs[p] scalars row-major, instances one after another
  * (num_proofs[p], num_inputs[p] powers of two <= the maxima, which are powers of two; < 2^31 scalars in all). */
-typedef struct spg_pqx spg_pqx;
 int spg_pqx_new(spg_ctx* ctx, const uint64_t* z_mont, size_t num_instances, const size_t* num_proofs,
                 size_t max_num_proofs, size_t num_witness_secs, const size_t* num_inputs, size_t max_num_inputs,
                 spg_pqx** out);
@@ -182,8 +194,7 @@ int spg_phase1_round_evals(spg_ctx* ctx, const spg_buf* Ap, const spg_buf* Aq, c
  * current state; num_witness_secs is the reference's argument. The caller binds A (p rounds) and ABC, Z with r_j. */
 int spg_phase2_round_evals(spg_ctx* ctx, const spg_buf* A, const spg_pqx* ABC, const spg_pqx* Z, int mode,
                            int single_inst, size_t num_witness_secs, uint64_t* out3_mont);
-struct spg_r1cs_inst;
-int spg_r1cs_multiply_vec_block(spg_ctx* ctx, const struct spg_r1cs_inst* inst, size_t num_instances,
+int spg_r1cs_multiply_vec_block(spg_ctx* ctx, const spg_r1cs_inst* inst, size_t num_instances,
                                 const size_t* num_proofs, size_t max_num_proofs, const size_t* num_inputs,
                                 size_t max_num_inputs, size_t num_witness_secs, const uint64_t* z_mont, spg_pqx** Az,
                                 spg_pqx** Bz, spg_pqx** Cz);
@@ -196,12 +207,12 @@ int spg_r1cs_multiply_vec_block(spg_ctx* ctx, const struct spg_r1cs_inst* inst, 
  * <= max_num_inputs; 1..8 sections (else SPG_E_ARG). An entry whose column lies outside [w max_num_inputs,
  * w max_num_inputs + num_inputs[p]) for every w < num_witness_secs makes the reference index past its vector; here
  * it contributes nothing, as in spg_r1cs_prove. */
-int spg_r1cs_eval_tables(spg_ctx* ctx, const struct spg_r1cs_inst* inst, size_t num_instances, size_t num_witness_secs,
+int spg_r1cs_eval_tables(spg_ctx* ctx, const spg_r1cs_inst* inst, size_t num_instances, size_t num_witness_secs,
                          size_t max_num_inputs, const size_t* num_inputs, const spg_buf* evals_rx, spg_pqx** A,
                          spg_pqx** B, spg_pqx** C);
 /* prove_abc_gen (src/r1csproof.rs:430-465): r_A A + r_B B + r_C C of the tables above put through new_rev (x
  * bit-reversed), in one pass; what spg_r1cs_prove builds before phase 2. Same arguments and checks. */
-int spg_r1cs_abc_poly(spg_ctx* ctx, const struct spg_r1cs_inst* inst, size_t num_instances, size_t num_witness_secs,
+int spg_r1cs_abc_poly(spg_ctx* ctx, const spg_r1cs_inst* inst, size_t num_instances, size_t num_witness_secs,
                       size_t max_num_inputs, const size_t* num_inputs, const spg_buf* evals_rx, const uint64_t* rA_mont,
                       const uint64_t* rB_mont, const uint64_t* rC_mont, spg_pqx** ABC);
 /* The two ZK sumchecks of R1CSProof::prove and their verifier on caller tables. gens supplies gens_1 and gens_4 of
@@ -216,34 +227,31 @@ int spg_r1cs_abc_poly(spg_ctx* ctx, const struct spg_r1cs_inst* inst, size_t num
  * |Ax| = 2^nx, |Aq| = 2^nq, |Ap| = 2^np >= instances and unbound B, C, D of one shape and one witness section with
  * max_num_inputs = 2^nx, max_num_proofs = 2^nq (num_cons / num_proofs of the reference are the tables' own sizes);
  * claims4 = (Ap[0] Aq[0] Ax[0], B, C, D at index (0, 0, 0, 0)). */
-struct spg_r1cs_gens;
-struct spg_random_tape;
-int spg_zk_phase1_prove(spg_ctx* ctx, const struct spg_r1cs_gens* gens, const uint64_t* claim_mont,
+int spg_zk_phase1_prove(spg_ctx* ctx, const spg_r1cs_gens* gens, const uint64_t* claim_mont,
                         const uint64_t* blind_claim_mont, size_t nx, size_t nq, size_t np, spg_buf* Ap, spg_buf* Aq,
-                        spg_buf* Ax, spg_pqx* B, spg_pqx* C, spg_pqx* D, struct spg_transcript* t,
-                        struct spg_random_tape* tape, uint8_t* proof, size_t cap, size_t* len, uint64_t* r_mont,
+                        spg_buf* Ax, spg_pqx* B, spg_pqx* C, spg_pqx* D, spg_transcript* t,
+                        spg_random_tape* tape, uint8_t* proof, size_t cap, size_t* len, uint64_t* r_mont,
                         uint64_t* claims4_mont, uint64_t* blind_post_mont);
 /* spg_zk_phase2_prove = prove_cubic_disjoint_rounds (src/sumcheck.rs:788-1065) with comb A B C (src/r1csproof.rs:
  * 132-174): ny y rounds, nw w rounds, np p rounds over |eq| = 2^np >= instances, ABC (one instance when single_inst,
  * else one per instance; not bound in the p rounds when single) and Z, both with q bound (spg_pqx_bound_rq) and y, w
  * unbound: max_num_inputs = 2^ny, num_witness_secs = 2^nw; num_witness_secs is the reference's argument (the sections
  * that exist). claims3 = (eq[0], ABC, Z at index (0, 0, 0, 0)). */
-int spg_zk_phase2_prove(spg_ctx* ctx, const struct spg_r1cs_gens* gens, const uint64_t* claim_mont,
+int spg_zk_phase2_prove(spg_ctx* ctx, const spg_r1cs_gens* gens, const uint64_t* claim_mont,
                         const uint64_t* blind_claim_mont, size_t ny, size_t nw, size_t np, int single_inst,
-                        size_t num_witness_secs, spg_buf* eq, spg_pqx* ABC, spg_pqx* Z, struct spg_transcript* t,
-                        struct spg_random_tape* tape, uint8_t* proof, size_t cap, size_t* len, uint64_t* r_mont,
+                        size_t num_witness_secs, spg_buf* eq, spg_pqx* ABC, spg_pqx* Z, spg_transcript* t,
+                        spg_random_tape* tape, uint8_t* proof, size_t cap, size_t* len, uint64_t* r_mont,
                         uint64_t* claims3_mont, uint64_t* blind_post_mont);
 /* ZKSumcheckInstanceProof::verify (src/sumcheck.rs:94-189): 0 with comm_claim_post (the last comm_eval) and the
  * num_rounds challenges in r, or SPG_E_VERIFY -- malformed, truncated or trailing bytes, a round-count mismatch and a
  * point that does not decompress included, as in spg_snark_verify. degree_bound other than 3 is SPG_E_ARG (both call
  * sites pass 3, and gens_4 holds 4 generators), as is num_rounds = 0. */
-int spg_zk_sumcheck_verify(spg_ctx* ctx, const struct spg_r1cs_gens* gens, const uint8_t* comm_claim, size_t num_rounds,
-                           size_t degree_bound, struct spg_transcript* t, const uint8_t* proof, size_t proof_len,
+int spg_zk_sumcheck_verify(spg_ctx* ctx, const spg_r1cs_gens* gens, const uint8_t* comm_claim, size_t num_rounds,
+                           size_t degree_bound, spg_transcript* t, const uint8_t* proof, size_t proof_len,
                            uint8_t* comm_claim_post, uint64_t* r_mont);
 /* -- memory checking and the grand-product argument on caller vectors (csrc/prodc.hip): what SparseMatPolyEvalProof
  * runs between its commitments (Layers::new, ProductLayerProof::prove; src/sparse_mlpoly.rs:689-736, 1105-1356), one
  * call at a time. Single-rank: spg_set_comm does not shard these. */
-struct spg_transcript;
 /* Layers::build_hash_layer (src/sparse_mlpoly.rs:612-687): hash(addr, val, ts) = ts r_hash^2 + val r_hash + addr -
  * r_multiset. eval_table, audit_ts: num_mem_cells scalars; addrs[k], derefs[k], read_ts[k]: num_ops scalars each,
  * k < n (n >= 1; both sizes powers of two). init[i] = hash(i, eval_table[i], 0), audit[i] = hash(i, eval_table[i],
@@ -256,7 +264,6 @@ int spg_hash_layer(spg_ctx* ctx, const spg_buf* eval_table, const spg_buf* const
  * (src/product_tree.rs:18-58) for nc polynomials of one power-of-two length M >= 2 (the inputs are left unchanged);
  * spg_prodc_evaluate = evaluate (:58-65) of every circuit (nc scalars); spg_prodc_layer = left_vec[layer],
  * right_vec[layer] of circuit c (M >> (layer + 1) scalars each, layer < log2 M), for inspection. */
-typedef struct spg_prodc spg_prodc;
 int spg_prodc_new(spg_ctx* ctx, const spg_buf* const* polys, size_t nc, spg_prodc** out);
 int spg_prodc_free(spg_ctx* ctx, spg_prodc* p);
 int spg_prodc_shape(const spg_prodc* p, size_t* nc, size_t* num_leaves);
@@ -274,7 +281,7 @@ int spg_prodc_layer(spg_ctx* ctx, const spg_prodc* p, size_t c, size_t layer, ui
 int spg_prove_cubic_batched(spg_ctx* ctx, const uint64_t* claim_mont, size_t num_rounds, spg_buf* const* A_par,
                             spg_buf* const* B_par, size_t n_par, spg_buf* C_par, spg_buf* const* A_seq,
                             spg_buf* const* B_seq, spg_buf* const* C_seq, size_t n_seq, const uint64_t* coeffs_mont,
-                            struct spg_transcript* t, uint64_t* polys_mont, uint64_t* r_mont, uint64_t* claims_par_mont,
+                            spg_transcript* t, uint64_t* polys_mont, uint64_t* r_mont, uint64_t* claims_par_mont,
                             uint64_t* claims_seq_mont);
 /* ProductCircuitEvalProofBatched::prove (src/product_tree.rs:260-396) over `prod` and nd dot-product circuits
  * (dotp[3k .. 3k+2] = left, right, weight of circuit k, M/2 scalars each, bound in place: one scalar each afterwards).
@@ -282,7 +289,7 @@ int spg_prove_cubic_batched(spg_ctx* ctx, const uint64_t* claim_mont, size_t num
  * nothing is run and prod stays usable); rand: log2(M) scalars. 3 (nc + nd) + 1 scalars must fit the mailbox (2047).
  * `prod` is consumed: its layers hold bound values afterwards, as the reference's &mut circuits do; only
  * spg_prodc_free is defined on it after this call. */
-int spg_prodc_prove_batched(spg_ctx* ctx, spg_prodc* prod, spg_buf* const* dotp, size_t nd, struct spg_transcript* t,
+int spg_prodc_prove_batched(spg_ctx* ctx, spg_prodc* prod, spg_buf* const* dotp, size_t nd, spg_transcript* t,
                             uint8_t* proof, size_t cap, size_t* len, uint64_t* rand_mont, size_t* rand_len);
 
 /* ---- generators ------------------------------------------------------------------------------
@@ -329,7 +336,6 @@ int spg_points_sum_compress(const uint8_t* parts, size_t k, uint8_t out[32]);
  * points (the verifier's sum_i L_i C_i over Hyrax row commitments, comm_vars_at_ry, Bullet's Gamma_hat) or someone
  * else's generators met once. No 2^k P rows or comb tables are built: a handle costs 96 B per point and one
  * decompression each. These calls are single-rank (like the prodc seams): spg_set_comm does not shard them. */
-typedef struct spg_points spg_points;
 /* n CompressedRistretto encodings -> n points resident in HBM as affine Niels (96 B each). Any encoding that
  * CompressedRistretto::decompress rejects: SPG_E_POINT, spg_last_error names the lowest such index, *out untouched,
  * nothing stays allocated. n >= 1, n < 2^31. */
@@ -392,8 +398,6 @@ int spg_commit_rows_buf(spg_ctx* ctx, const spg_gens* g, const spg_buf* Z, size_
  * ProofTranscript over merlin::Transcript (src/transcript.rs:5-63) and RandomTape
  * (src/random.rs:7-29). RandomTape::new draws its init scalar from OsRng in the reference; here the
  * caller supplies it (the one seam that makes proofs reproducible). Labels are NUL-terminated. */
-typedef struct spg_transcript spg_transcript;
-typedef struct spg_random_tape spg_random_tape;
 int spg_transcript_new(const char* label, spg_transcript** out);
 /* A transcript backed by the caller's own Fiat-Shamir state (SNARK::prove's `transcript: &mut Transcript`,
  * src/lib.rs:1022, appended to from :1033 on; ProofTranscript src/transcript.rs:5-63). Every operation of the
@@ -430,7 +434,6 @@ int spg_random_tape_free(spg_random_tape* tp);
  * malformed or truncated proof bytes, a wrong proof count, a commitment of the wrong row count and a commitment point
  * that does not decompress are all SPG_E_VERIFY, as in spg_snark_verify. Single-rank, like the spg_prodc_* seams:
  * spg_set_comm does not shard these. */
-typedef struct spg_poly_gens spg_poly_gens;
 /* PolyCommitmentGens::new(num_vars, label) (:31-38) = DotProductProofGens::new(n = 2^(num_vars - num_vars/2), label):
  * the first n + 2 points of label's stream; gens_n = G_0 .. G_{n-1} with h = point n + 1, gens_1 = G_n with the same h */
 int spg_poly_gens_new(spg_ctx* ctx, const uint8_t* label, size_t label_len, size_t num_vars, spg_poly_gens** out);
@@ -525,9 +528,6 @@ int spg_pe_verify_uni(spg_ctx* ctx, const spg_poly_gens* g, const uint64_t* r_mo
  * R1CSGens::new(label, _, num_vars) (src/r1csproof.rs:71-79): gens_pc = PolyCommitmentGens for
  * log2(num_vars) variables; gens_1 = gens_pc.gens_1, gens_4 = MultiCommitGens::new(4, label). All of
  * them are prefixes of the same SHAKE256 stream, held once in HBM. */
-typedef struct spg_r1cs_gens spg_r1cs_gens;
-typedef struct spg_r1cs_inst spg_r1cs_inst;
-typedef struct spg_r1cs_witness spg_r1cs_witness;
 int spg_r1cs_gens_new(spg_ctx* ctx, const uint8_t* label, size_t label_len, size_t num_vars, spg_r1cs_gens** out);
 /* *count = number of stream points held; out (optional) receives count x 32 bytes */
 int spg_r1cs_gens_download(spg_ctx* ctx, const spg_r1cs_gens* g, uint8_t* out, size_t* count);
@@ -587,7 +587,6 @@ int spg_r1cs_multi_evaluate(spg_ctx* ctx, const spg_r1cs_inst* inst, const uint6
  * The batch is the 3P matrices A_0, B_0, C_0, A_1, ... of an R1CS instance (R1CSInstance::multi_commit,
  * src/r1csinstance.rs:645-700 -> SparseMatPolynomial::multi_commit, src/sparse_mlpoly.rs:566-587).
  * The dense representation (addresses, timestamps, values, comb_ops / comb_mem) stays in HBM. */
-typedef struct spg_spark spg_spark;
 /* SparseMatPolyCommitmentGens::new(label, nvx, nvy, gens_nnz, gens_batch) (src/sparse_mlpoly.rs:289-317)
  * + multi_commit. Writes bincode(SparseMatPolyCommitment) into comm (*comm_len = its size). */
 int spg_spark_commit(spg_ctx* ctx, const spg_r1cs_instance* inst, const uint8_t* label, size_t label_len,
@@ -648,8 +647,6 @@ typedef struct {
   const uint64_t* addr_ts_bits;      /* total_num_vir_mem_accesses x mem_addr_ts_bits_size x 4 */
 } spg_snark_inputs;
 
-typedef struct spg_snark_comp spg_snark_comp; /* ComputationCommitment + ComputationDecommitment */
-typedef struct spg_snark_wit spg_snark_wit;   /* SNARK::prove run-time inputs, resident in HBM */
 
 /* SNARK::multi_encode (multi != 0: matrices grouped by next_power_of_eight(nnz), src/r1csinstance.rs:654-715)
  * or SNARK::encode (one commitment over all 3P matrices, :717-737) of one instance, with

@@ -7,17 +7,67 @@ Mirrors the reference crate's seams with the same argument meaning:
   * Gens.commit_rows(Z, L, R) ~ DensePolynomial::commit_inner           (src/dense_mlpoly.rs:184-212)
 Scalars are numpy uint64 arrays of shape (..., 4): the reference's Montgomery limbs.
 There is no CPU fallback: constructing a Context without a gfx950 device raises.
+
+The C signature of every spg_* function is read from include/spg.h when the library is loaded (_signatures, _bind):
+callers pass plain Python ints for size_t / int / long arguments, and a wrong type stops in ctypes.
 """
 import ctypes
 import os
+import re
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SPG_LIB") or os.path.join(_HERE, "lib", "libspg.so")
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "spg.h")
 
 SPG_ERRORS = {-1: "SPG_E_ARG", -2: "SPG_E_NOMEM", -3: "SPG_E_HIP", -4: "SPG_E_POINT", -5: "SPG_E_NODEVICE",
               -6: "SPG_E_VERIFY", -7: "SPG_E_CALLBACK"}
+SPG_E_VERIFY = -6
+SPG_E_ARG = -1
+
+# by-value C types of the header; every parameter with a `*` or `[` is a pointer (c_void_p: handles, byref(), ctypes
+# arrays, None, _p(numpy) and CFUNCTYPE thunks all pass), as are the callback typedefs
+_C_VALUES = {"size_t": ctypes.c_size_t, "int": ctypes.c_int, "long": ctypes.c_long, "double": ctypes.c_double,
+             "uint32_t": ctypes.c_uint32, "uint64_t": ctypes.c_uint64}
+_C_CALLBACKS = ("spg_allgather_fn", "spg_transcript_append_fn", "spg_transcript_challenge_fn")
+_PROTOTYPE = re.compile(r"^([A-Za-z_][\w \t*]*?)\s*\b(spg_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", re.M)
+
+
+def _signatures(text):
+    """{name: (restype, [argtypes])} of every `<ret> spg_name(<params>);` prototype in header text; a type outside the
+    table above raises, naming the function and the parameter"""
+    sigs = {}
+    for ret, name, params in _PROTOTYPE.findall(re.sub(r"/\*.*?\*/", "", text, flags=re.S)):
+        ret = " ".join(ret.split())
+        if ret == "const char*":
+            restype = ctypes.c_char_p
+        elif ret in _C_VALUES:
+            restype = _C_VALUES[ret]
+        else:
+            raise ValueError(f"spg.h: {name}: return type '{ret}' has no ctypes mapping")
+        argtypes = []
+        for param in ([] if params.strip() == "void" else params.split(",")):
+            words = [w for w in param.split() if w != "const"]
+            ctype = " ".join(words[:-1])  # the last word is the parameter's name
+            if "*" in param or "[" in param or ctype in _C_CALLBACKS:
+                argtypes.append(ctypes.c_void_p)
+            elif ctype in _C_VALUES:
+                argtypes.append(_C_VALUES[ctype])
+            else:
+                raise ValueError(f"spg.h: {name}: parameter '{' '.join(param.split())}' has no ctypes mapping")
+        sigs[name] = (restype, argtypes)
+    return sigs
+
+
+def _bind(cdll):
+    """restype and argtypes of every function include/spg.h declares (a symbol the library lacks raises)"""
+    with open(HEADER_PATH) as f:
+        sigs = _signatures(f.read())
+    for name, (restype, argtypes) in sigs.items():
+        fn = getattr(cdll, name)
+        fn.restype, fn.argtypes = restype, argtypes
+
 
 _lib = None
 
@@ -27,12 +77,9 @@ def lib():
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError(f"libspg.so not built at {LIB_PATH}; run __graft_entry__.build()")
-        _lib = ctypes.CDLL(LIB_PATH)
-        _lib.spg_last_error.restype = ctypes.c_char_p
-        _lib.spg_last_kernel_us.restype = ctypes.c_double
-        _lib.spg_gens_n.restype = ctypes.c_size_t
-        _lib.spg_points_n.restype = ctypes.c_size_t
-        _lib.spg_points_n.argtypes = [ctypes.c_void_p]
+        cdll = ctypes.CDLL(LIB_PATH)
+        _bind(cdll)
+        _lib = cdll
     return _lib
 
 
@@ -108,7 +155,7 @@ def torch_allgather(dist, group=None, device="cpu"):
 class Context:
     def __init__(self, device=0):
         self._h = ctypes.c_void_p()
-        rc = lib().spg_init(ctypes.c_int(device), ctypes.byref(self._h))
+        rc = lib().spg_init(device, ctypes.byref(self._h))
         if rc != 0:
             raise SpgError(f"spg_init({device}) failed: {SPG_ERRORS.get(rc, rc)} (no gfx950 device?)")
 
@@ -116,6 +163,10 @@ class Context:
         if rc != 0:
             msg = lib().spg_last_error(self._h).decode(errors="replace")
             raise SpgError(f"{what}: {SPG_ERRORS.get(rc, rc)}: {msg}")
+
+    def call(self, name, *args):
+        """lib().<name>(this context, *args), its return code checked under that name"""
+        self.check(getattr(lib(), name)(self._h, *args), name)
 
     def out_buf(self, cap):
         """the proof output buffer of this context's calls, kept between calls (a context runs one call at a time;
@@ -133,8 +184,7 @@ class Context:
     def set_comm(self, rank, nranks, allgather_fn=None):
         """spg_set_comm: shard R1CSProof::prove by instance over nranks processes (one GPU each)."""
         self._comm = allgather_fn  # keep the ctypes thunk alive
-        fn = allgather_fn if allgather_fn is not None else ctypes.cast(None, ALLGATHER_FN)
-        self.check(lib().spg_set_comm(self._h, ctypes.c_int(rank), ctypes.c_int(nranks), fn, None), "spg_set_comm")
+        self.call("spg_set_comm", rank, nranks, allgather_fn, None)
 
     def set_comm_rccl(self, rank, nranks, dist=None, unique_id=None):
         """spg_set_comm_rccl: libspg's own RCCL transport on the context stream. Rank 0's 128-byte id
@@ -154,31 +204,31 @@ class Context:
                 unique_id = bytes(buf)
         uid = (ctypes.c_uint8 * 128).from_buffer_copy(unique_id)
         self._comm = None
-        self.check(lib().spg_set_comm_rccl(self._h, uid, ctypes.c_int(rank), ctypes.c_int(nranks)), "spg_set_comm_rccl")
+        self.call("spg_set_comm_rccl", uid, rank, nranks)
 
     def comm_allgather(self, data, nranks):
         """spg_comm_allgather over the context's transport: every rank's `data` (equal lengths), rank-ordered"""
         n = len(data)
         src = (ctypes.c_uint8 * max(n, 1)).from_buffer_copy(bytes(data) or b"\0")
         dst = (ctypes.c_uint8 * max(n * nranks, 1))()
-        self.check(lib().spg_comm_allgather(self._h, src, ctypes.c_size_t(n), dst), "spg_comm_allgather")
+        self.call("spg_comm_allgather", src, n, dst)
         raw = bytes(dst)
         return [raw[k * n:(k + 1) * n] for k in range(nranks)]
 
     def set_comb(self, on=True):
         """spg_set_comb: off -> this context's MSMs skip the comb tables (bucket Pippenger pipelines only)"""
-        self.check(lib().spg_set_comb(self._h, ctypes.c_int(1 if on else 0)), "spg_set_comb")
+        self.call("spg_set_comb", 1 if on else 0)
 
     def set_vmsm_host_max(self, n=-1):
         """spg_set_vmsm_host_max: this context's variable-base MSMs of fewer than n points run on the host pool (0:
         every size through the kernels; negative: the process default)"""
-        self.check(lib().spg_set_vmsm_host_max(self._h, ctypes.c_long(n)), "spg_set_vmsm_host_max")
+        self.call("spg_set_vmsm_host_max", n)
 
     def last_kernel_us(self):
         return lib().spg_last_kernel_us(self._h)
 
     def prof_enable(self, on=True):
-        self.check(lib().spg_prof_enable(self._h, ctypes.c_int(1 if on else 0)), "spg_prof_enable")
+        self.call("spg_prof_enable", 1 if on else 0)
 
     def prof_read(self, reset=True, ops=False):
         """{kernel_name: (launches, total_us, algorithmic_bytes)} of the kernels timed since the last reset;
@@ -191,8 +241,8 @@ class Context:
         nbytes = np.zeros(mx, dtype=np.float64)
         nops = np.zeros(mx, dtype=np.float64)
         nfqm = np.zeros(mx, dtype=np.float64)
-        k = lib().spg_prof_read3(self._h, names, _p(launches), _p(tot), _p(nbytes), _p(nops), _p(nfqm),
-                                 ctypes.c_int(mx), ctypes.c_int(1 if reset else 0))
+        k = lib().spg_prof_read3(self._h, names, _p(launches), _p(tot), _p(nbytes), _p(nops), _p(nfqm), mx,
+                                 1 if reset else 0)
         if k < 0:
             self.check(k, "spg_prof_read3")
         raw = names.raw
@@ -215,6 +265,32 @@ class Context:
             pass
 
 
+class _Handle:
+    """An object that owns one native handle (self._h; self.ctx where its free function takes the context): freed
+    once, by free() or when the object is collected."""
+
+    _free = None  # the name of the spg_*_free function
+
+    @property
+    def handle(self):
+        return self._h
+
+    def free(self):
+        if self._h:
+            fn = getattr(lib(), self._free)
+            if len(fn.argtypes) == 2:
+                fn(self.ctx.handle, self._h)
+            else:
+                fn(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
 def _scalars(x):
     a = np.ascontiguousarray(x, dtype=np.uint64)
     if a.shape[-1] != 4:
@@ -222,24 +298,21 @@ def _scalars(x):
     return a
 
 
-class Buf:
+class Buf(_Handle):
     """Device-resident vector of Montgomery scalars (spg_buf)."""
+
+    _free = "spg_buf_free"
 
     def __init__(self, ctx, scalars):
         self.ctx = ctx
         a = _scalars(scalars)
         self.n = a.shape[0]
         self._h = ctypes.c_void_p()
-        ctx.check(lib().spg_buf_upload(ctx.handle, _p(a), ctypes.c_size_t(self.n), ctypes.byref(self._h)),
-                  "spg_buf_upload")
-
-    @property
-    def handle(self):
-        return self._h
+        ctx.call("spg_buf_upload", _p(a), self.n, ctypes.byref(self._h))
 
     def download(self):
         out = np.zeros((self.n, 4), dtype=np.uint64)
-        self.ctx.check(lib().spg_buf_download(self.ctx.handle, self._h, _p(out)), "spg_buf_download")
+        self.ctx.call("spg_buf_download", self._h, _p(out))
         return out
 
     @classmethod
@@ -250,34 +323,32 @@ class Buf:
         b.ctx = ctx
         b.n = 1 << a.shape[0]
         b._h = ctypes.c_void_p()
-        ctx.check(lib().spg_eq_evals(ctx.handle, _p(a), ctypes.c_size_t(a.shape[0]), ctypes.byref(b._h)),
-                  "spg_eq_evals")
+        ctx.call("spg_eq_evals", _p(a), a.shape[0], ctypes.byref(b._h))
         return b
 
     # per-operation seams (csrc/seams.hip)
     def bound_top(self, r):
         """DensePolynomial::bound_poly_var_top (src/dense_mlpoly.rs:267-275), in place; the length halves."""
-        self.ctx.check(lib().spg_buf_bound_top(self.ctx.handle, self._h, _p(_scalars(r))), "spg_buf_bound_top")
+        self.ctx.call("spg_buf_bound_top", self._h, _p(_scalars(r)))
         self.n //= 2
 
     def bound_bot(self, r):
         """DensePolynomial::bound_poly_var_bot (src/dense_mlpoly.rs:350-358), in place; the length halves."""
-        self.ctx.check(lib().spg_buf_bound_bot(self.ctx.handle, self._h, _p(_scalars(r))), "spg_buf_bound_bot")
+        self.ctx.call("spg_buf_bound_bot", self._h, _p(_scalars(r)))
         self.n //= 2
 
     def evaluate(self, r):
         """DensePolynomial::evaluate (src/dense_mlpoly.rs:361-367) at r (len(r) = log2 of the length)."""
         a = _scalars(r) if len(r) else np.zeros((1, 4), dtype=np.uint64)
         out = np.zeros(4, dtype=np.uint64)
-        self.ctx.check(lib().spg_buf_evaluate(self.ctx.handle, self._h, _p(a), ctypes.c_size_t(len(r)), _p(out)),
-                       "spg_buf_evaluate")
+        self.ctx.call("spg_buf_evaluate", self._h, _p(a), len(r), _p(out))
         return out
 
     @staticmethod
     def cubic_round_evals(A, B, C):
         """One prove_cubic round's (e0, e2, e3) with comb A B C (src/sumcheck.rs:207-236)."""
         out = np.zeros((3, 4), dtype=np.uint64)
-        A.ctx.check(lib().spg_cubic_round_evals(A.ctx.handle, A._h, B._h, C._h, _p(out)), "spg_cubic_round_evals")
+        A.ctx.call("spg_cubic_round_evals", A._h, B._h, C._h, _p(out))
         return out
 
     @staticmethod
@@ -287,22 +358,11 @@ class Buf:
         polys = np.zeros((max(num_rounds, 1), 3, 4), dtype=np.uint64)
         r = np.zeros((max(num_rounds, 1), 4), dtype=np.uint64)
         claims = np.zeros((3, 4), dtype=np.uint64)
-        A.ctx.check(lib().spg_prove_cubic(A.ctx.handle, _p(_scalars(claim)), ctypes.c_size_t(num_rounds), A._h, B._h,
-                                          C._h, transcript.handle, _p(polys), _p(r), _p(claims)), "spg_prove_cubic")
+        A.ctx.call("spg_prove_cubic", _p(_scalars(claim)), num_rounds, A._h, B._h, C._h, transcript.handle, _p(polys),
+                   _p(r), _p(claims))
         for b in (A, B, C):
             b.n >>= num_rounds
         return polys[:num_rounds], r[:num_rounds], claims
-
-    def free(self):
-        if self._h:
-            lib().spg_buf_free(self.ctx.handle, self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def _z_of_shape(z, num_proofs, num_witness_secs, num_inputs, what):
@@ -322,9 +382,11 @@ def _pqx_from_handle(ctx, h, P, n):
     return t
 
 
-class Pqx:
+class Pqx(_Handle):
     """DensePolynomialPqx (src/custom_dense_mlpoly.rs:22-359) resident in HBM (spg_pqx_*): z holds instance p's
     num_proofs[p] x num_witness_secs x num_inputs[p] scalars in (q_rev, w, x_rev) order, instances concatenated."""
+
+    _free = "spg_pqx_free"
 
     def __init__(self, ctx, z, num_proofs, max_num_proofs, num_witness_secs, num_inputs, max_num_inputs):
         self.ctx = ctx
@@ -334,9 +396,8 @@ class Pqx:
         np_ = np.asarray(num_proofs, dtype=np.uint64)
         ni_ = np.asarray(num_inputs, dtype=np.uint64)
         self._h = ctypes.c_void_p()
-        ctx.check(lib().spg_pqx_new(ctx.handle, _p(a), ctypes.c_size_t(self.P), _p(np_), ctypes.c_size_t(max_num_proofs),
-                                    ctypes.c_size_t(num_witness_secs), _p(ni_), ctypes.c_size_t(max_num_inputs),
-                                    ctypes.byref(self._h)), "spg_pqx_new")
+        ctx.call("spg_pqx_new", _p(a), self.P, _p(np_), max_num_proofs, num_witness_secs, _p(ni_), max_num_inputs,
+                 ctypes.byref(self._h))
 
     @classmethod
     def new_rev(cls, ctx, z, num_proofs, max_num_proofs, num_witness_secs, num_inputs, max_num_inputs, offset=0):
@@ -350,37 +411,33 @@ class Pqx:
         t = cls.__new__(cls)
         t.ctx, t.P, t._h = ctx, P, ctypes.c_void_p()
         t.n = sum(int(q) * int(num_witness_secs) * int(x) for q, x in zip(num_proofs, num_inputs))
-        shape = (ctypes.c_size_t(P), _p(np_), ctypes.c_size_t(max_num_proofs), ctypes.c_size_t(num_witness_secs), _p(ni_),
-                 ctypes.c_size_t(max_num_inputs), ctypes.byref(t._h))
+        shape = (P, _p(np_), max_num_proofs, num_witness_secs, _p(ni_), max_num_inputs, ctypes.byref(t._h))
         if isinstance(z, Buf):
-            ctx.check(lib().spg_pqx_new_rev_buf(ctx.handle, z.handle, ctypes.c_size_t(offset), *shape),
-                      "spg_pqx_new_rev_buf")
+            ctx.call("spg_pqx_new_rev_buf", z.handle, offset, *shape)
         else:
             assert offset == 0, "Pqx.new_rev: offset is for a Buf"
             a = _z_of_shape(z, num_proofs, num_witness_secs, num_inputs, "Pqx.new_rev")
-            ctx.check(lib().spg_pqx_new_rev(ctx.handle, _p(a), *shape), "spg_pqx_new_rev")
+            ctx.call("spg_pqx_new_rev", _p(a), *shape)
         return t
 
     def bound_rq(self, rq):
         """bound_poly_vars_rq (src/custom_dense_mlpoly.rs:300-304): bound(rq[0], 2), bound(rq[1], 2), .. in order; one
         pass over the table for two or more challenges"""
         a = _scalars(rq) if len(rq) else np.zeros((1, 4), dtype=np.uint64)
-        self.ctx.check(lib().spg_pqx_bound_rq(self.ctx.handle, self._h, _p(a), ctypes.c_size_t(len(rq))),
-                       "spg_pqx_bound_rq")
+        self.ctx.call("spg_pqx_bound_rq", self._h, _p(a), len(rq))
 
     def bound(self, r, mode):
         """bound_poly(r, mode): 1 = p, 2 = q, 3 = w, 4 = x (src/custom_dense_mlpoly.rs:180-199)"""
-        self.ctx.check(lib().spg_pqx_bound(self.ctx.handle, self._h, _p(_scalars(r)), ctypes.c_int(mode)),
-                       "spg_pqx_bound")
+        self.ctx.call("spg_pqx_bound", self._h, _p(_scalars(r)), mode)
 
     def evaluate(self, rp, rq, rw, rx):
         """evaluate(r_p, r_q, r_w, r_x) (src/custom_dense_mlpoly.rs:320-333); the table is left unchanged"""
         arrs = [_scalars(r) if len(r) else np.zeros((1, 4), dtype=np.uint64) for r in (rp, rq, rw, rx)]
         args = []
         for a, r in zip(arrs, (rp, rq, rw, rx)):
-            args += [_p(a), ctypes.c_size_t(len(r))]
+            args += [_p(a), len(r)]
         out = np.zeros(4, dtype=np.uint64)
-        self.ctx.check(lib().spg_pqx_evaluate(self.ctx.handle, self._h, *args, _p(out)), "spg_pqx_evaluate")
+        self.ctx.call("spg_pqx_evaluate", self._h, *args, _p(out))
         return out
 
     def shape(self):
@@ -392,20 +449,14 @@ class Pqx:
 
     def download(self):
         out = np.zeros((self.n, 4), dtype=np.uint64)
-        self.ctx.check(lib().spg_pqx_download(self.ctx.handle, self._h, _p(out)), "spg_pqx_download")
+        self.ctx.call("spg_pqx_download", self._h, _p(out))
         return out
 
-    def __del__(self):
-        try:
-            if self._h:
-                lib().spg_pqx_free(self.ctx.handle, self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
 
-
-class Gens:
+class Gens(_Handle):
     """Device-resident MultiCommitGens (G_0..G_{n-1}, h) with fixed-base window tables."""
+
+    _free = "spg_gens_free"
 
     def __init__(self, ctx, n, label=None, compressed=None):
         self.ctx = ctx
@@ -413,54 +464,43 @@ class Gens:
         if compressed is not None:
             comp = np.ascontiguousarray(compressed, dtype=np.uint8).reshape(-1, 32)
             assert comp.shape[0] == n + 1
-            rc = lib().spg_gens_upload(ctx.handle, _p(comp), ctypes.c_size_t(n), ctypes.byref(self._h))
-            ctx.check(rc, "spg_gens_upload")
+            ctx.call("spg_gens_upload", _p(comp), n, ctypes.byref(self._h))
         else:
             lb = np.frombuffer(bytes(label), dtype=np.uint8).copy() if label else np.zeros(1, np.uint8)
-            rc = lib().spg_gens_derive(ctx.handle, _p(lb), ctypes.c_size_t(len(label or b"")), ctypes.c_size_t(n),
-                                       ctypes.byref(self._h))
-            ctx.check(rc, "spg_gens_derive")
+            ctx.call("spg_gens_derive", _p(lb), len(label or b""), n, ctypes.byref(self._h))
         self.n = n
 
     def compressed(self):
         out = np.zeros((self.n + 1, 32), dtype=np.uint8)
-        self.ctx.check(lib().spg_gens_download(self.ctx.handle, self._h, _p(out)), "spg_gens_download")
+        self.ctx.call("spg_gens_download", self._h, _p(out))
         return out
 
     def msm(self, scalars, blind=None, gen_offset=0):
         s = _scalars(scalars)
         out = np.zeros(32, dtype=np.uint8)
         bl = None if blind is None else _scalars(blind)
-        rc = lib().spg_msm(self.ctx.handle, self._h, ctypes.c_size_t(gen_offset), _p(s), ctypes.c_size_t(s.shape[0]),
-                           None if bl is None else _p(bl), _p(out))
-        self.ctx.check(rc, "spg_msm")
+        self.ctx.call("spg_msm", self._h, gen_offset, _p(s), s.shape[0], None if bl is None else _p(bl), _p(out))
         return out.tobytes()
 
     def msm_partial(self, scalars, gen_offset=0):
         """spg_msm_partial: uncompressed (X, Y, Z, T) partial sum of one shard, 128 bytes"""
         s = _scalars(scalars)
         out = np.zeros(128, dtype=np.uint8)
-        rc = lib().spg_msm_partial(self.ctx.handle, self._h, ctypes.c_size_t(gen_offset), _p(s),
-                                   ctypes.c_size_t(s.shape[0]), _p(out))
-        self.ctx.check(rc, "spg_msm_partial")
+        self.ctx.call("spg_msm_partial", self._h, gen_offset, _p(s), s.shape[0], _p(out))
         return out.tobytes()
 
     def msm_partial_buf(self, buf, offset=0, n=None, gen_offset=0):
         """spg_msm_partial_buf: the partial sum of scalars already resident in HBM (a Buf), 128 bytes"""
         n = buf.n - offset if n is None else n
         out = np.zeros(128, dtype=np.uint8)
-        rc = lib().spg_msm_partial_buf(self.ctx.handle, self._h, ctypes.c_size_t(gen_offset), buf._h,
-                                       ctypes.c_size_t(offset), ctypes.c_size_t(n), _p(out))
-        self.ctx.check(rc, "spg_msm_partial_buf")
+        self.ctx.call("spg_msm_partial_buf", self._h, gen_offset, buf._h, offset, n, _p(out))
         return out.tobytes()
 
     def msm_buf(self, buf, offset=0, n=None, gen_offset=0):
         """spg_msm_buf: vartime_multiscalar_mul of resident scalars, 32-byte compression"""
         n = buf.n - offset if n is None else n
         out = np.zeros(32, dtype=np.uint8)
-        rc = lib().spg_msm_buf(self.ctx.handle, self._h, ctypes.c_size_t(gen_offset), buf._h, ctypes.c_size_t(offset),
-                               ctypes.c_size_t(n), _p(out))
-        self.ctx.check(rc, "spg_msm_buf")
+        self.ctx.call("spg_msm_buf", self._h, gen_offset, buf._h, offset, n, _p(out))
         return out.tobytes()
 
     def commit_rows(self, Z, L, R, blinds=None):
@@ -468,64 +508,47 @@ class Gens:
         assert z.shape[0] == L * R
         out = np.zeros((L, 32), dtype=np.uint8)
         bl = None if blinds is None else _scalars(blinds)
-        rc = lib().spg_commit_rows(self.ctx.handle, self._h, _p(z), ctypes.c_size_t(L), ctypes.c_size_t(R),
-                                   None if bl is None else _p(bl), _p(out))
-        self.ctx.check(rc, "spg_commit_rows")
+        self.ctx.call("spg_commit_rows", self._h, _p(z), L, R, None if bl is None else _p(bl), _p(out))
         return out
 
     def commit_rows_buf(self, zbuf, L, R, offset=0, blinds_buf=None):
         out = np.zeros((L, 32), dtype=np.uint8)
-        rc = lib().spg_commit_rows_buf(self.ctx.handle, self._h, zbuf.handle, ctypes.c_size_t(offset), ctypes.c_size_t(L),
-                                       ctypes.c_size_t(R), None if blinds_buf is None else blinds_buf.handle, _p(out))
-        self.ctx.check(rc, "spg_commit_rows_buf")
+        self.ctx.call("spg_commit_rows_buf", self._h, zbuf.handle, offset, L, R,
+                      None if blinds_buf is None else blinds_buf.handle, _p(out))
         return out
 
-    def free(self):
-        if self._h:
-            lib().spg_gens_free(self.ctx.handle, self._h)
-            self._h = ctypes.c_void_p()
 
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-
-class Points:
+class Points(_Handle):
     """Device-resident points a caller supplies (spg_points): n CompressedRistretto encodings kept as affine Niels, for
     GroupElement::vartime_multiscalar_mul over points that are no generator set (src/group.rs:98-116). An encoding
     that does not decompress raises SpgError (SPG_E_POINT, naming the lowest such index)."""
+
+    _free = "spg_points_free"
 
     def __init__(self, ctx, compressed):
         self.ctx = ctx
         self._h = ctypes.c_void_p()
         comp = np.ascontiguousarray(compressed, dtype=np.uint8).reshape(-1, 32)
-        rc = lib().spg_points_upload(ctx.handle, _p(comp), ctypes.c_size_t(comp.shape[0]), ctypes.byref(self._h))
-        ctx.check(rc, "spg_points_upload")
+        ctx.call("spg_points_upload", _p(comp), comp.shape[0], ctypes.byref(self._h))
         self.n = int(lib().spg_points_n(self._h))
 
     def compressed(self):
         out = np.zeros((self.n, 32), dtype=np.uint8)
-        self.ctx.check(lib().spg_points_download(self.ctx.handle, self._h, _p(out)), "spg_points_download")
+        self.ctx.call("spg_points_download", self._h, _p(out))
         return out
 
     def msm(self, scalars, offset=0):
         """spg_msm_var: sum_i scalars[i] * P[offset + i], 32-byte compression"""
         s = _scalars(scalars)
         out = np.zeros(32, dtype=np.uint8)
-        rc = lib().spg_msm_var(self.ctx.handle, self._h, ctypes.c_size_t(offset), _p(s), ctypes.c_size_t(s.shape[0]),
-                               _p(out))
-        self.ctx.check(rc, "spg_msm_var")
+        self.ctx.call("spg_msm_var", self._h, offset, _p(s), s.shape[0], _p(out))
         return out.tobytes()
 
     def msm_buf(self, buf, offset=0, s_offset=0, n=None):
         """spg_msm_var_buf: the same over scalars resident in HBM (a Buf)"""
         n = buf.n - s_offset if n is None else n
         out = np.zeros(32, dtype=np.uint8)
-        rc = lib().spg_msm_var_buf(self.ctx.handle, self._h, ctypes.c_size_t(offset), buf.handle,
-                                   ctypes.c_size_t(s_offset), ctypes.c_size_t(n), _p(out))
-        self.ctx.check(rc, "spg_msm_var_buf")
+        self.ctx.call("spg_msm_var_buf", self._h, offset, buf.handle, s_offset, n, _p(out))
         return out.tobytes()
 
     def msm_batch(self, offsets, lens, scalars):
@@ -536,21 +559,8 @@ class Points:
         s = _scalars(scalars) if int(ln.sum()) else np.zeros((1, 4), dtype=np.uint64)
         assert int(ln.sum()) == 0 or s.shape[0] == int(ln.sum())
         out = np.zeros((offs.shape[0], 32), dtype=np.uint8)
-        rc = lib().spg_msm_var_batch(self.ctx.handle, self._h, _p(offs), _p(ln), ctypes.c_size_t(offs.shape[0]), _p(s),
-                                     _p(out))
-        self.ctx.check(rc, "spg_msm_var_batch")
+        self.ctx.call("spg_msm_var_batch", self._h, _p(offs), _p(ln), offs.shape[0], _p(s), _p(out))
         return out
-
-    def free(self):
-        if self._h:
-            lib().spg_points_free(self.ctx.handle, self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def msm_points(ctx, compressed, scalars):
@@ -559,8 +569,7 @@ def msm_points(ctx, compressed, scalars):
     s = _scalars(scalars) if comp.shape[0] else np.zeros((0, 4), dtype=np.uint64)
     assert s.shape[0] == comp.shape[0]
     out = np.zeros(32, dtype=np.uint8)
-    rc = lib().spg_msm_points(ctx.handle, _p(comp), _p(s), ctypes.c_size_t(comp.shape[0]), _p(out))
-    ctx.check(rc, "spg_msm_points")
+    ctx.call("spg_msm_points", _p(comp), _p(s), comp.shape[0], _p(out))
     return out.tobytes()
 
 
@@ -572,13 +581,15 @@ TRANSCRIPT_CHALLENGE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes
                                            ctypes.c_size_t)
 
 
-class Transcript:
+class Transcript(_Handle):
     """ProofTranscript over merlin (src/transcript.rs:5-63), host object in libspg; or, with from_callbacks, a view
     of the caller's own transcript (every append_message / challenge_bytes is forwarded to it)."""
 
+    _free = "spg_transcript_free"
+
     def __init__(self, label):
         self._h = ctypes.c_void_p()
-        rc = lib().spg_transcript_new(ctypes.c_char_p(bytes(label)), ctypes.byref(self._h))
+        rc = lib().spg_transcript_new(bytes(label), ctypes.byref(self._h))
         if rc != 0:
             raise SpgError(f"spg_transcript_new: {SPG_ERRORS.get(rc, rc)}")
 
@@ -634,90 +645,69 @@ class Transcript:
 
     def caller_challenge(self, label, n):
         out = (ctypes.c_uint8 * max(n, 1))()
-        hostcheck().spgh_merlin_challenge_cb(self._merlin, ctypes.c_char_p(bytes(label)), out, ctypes.c_size_t(n))
+        hostcheck().spgh_merlin_challenge_cb(self._merlin, bytes(label), out, n)
         return bytes(out)[:n]
-
-    @property
-    def handle(self):
-        return self._h
 
     def append_message(self, label, msg):
         m = np.frombuffer(bytes(msg), dtype=np.uint8).copy() if msg else np.zeros(1, np.uint8)
-        rc = lib().spg_transcript_append_message(self._h, ctypes.c_char_p(bytes(label)), _p(m), ctypes.c_size_t(len(msg)))
+        rc = lib().spg_transcript_append_message(self._h, bytes(label), _p(m), len(msg))
         if rc != 0:
             raise SpgError(f"spg_transcript_append_message: {SPG_ERRORS.get(rc, rc)}")
 
     def append_scalar(self, label, s):
         a = _scalars(s)
-        assert lib().spg_transcript_append_scalar(self._h, ctypes.c_char_p(bytes(label)), _p(a)) == 0
+        assert lib().spg_transcript_append_scalar(self._h, bytes(label), _p(a)) == 0
 
     def challenge_scalar(self, label):
         out = np.zeros(4, dtype=np.uint64)
-        assert lib().spg_transcript_challenge_scalar(self._h, ctypes.c_char_p(bytes(label)), _p(out)) == 0
+        assert lib().spg_transcript_challenge_scalar(self._h, bytes(label), _p(out)) == 0
         return out
 
     def challenge_bytes(self, label, n):
         out = np.zeros(max(n, 1), dtype=np.uint8)
-        rc = lib().spg_transcript_challenge_bytes(self._h, ctypes.c_char_p(bytes(label)), _p(out), ctypes.c_size_t(n))
+        rc = lib().spg_transcript_challenge_bytes(self._h, bytes(label), _p(out), n)
         if rc != 0:
             raise SpgError(f"spg_transcript_challenge_bytes: {SPG_ERRORS.get(rc, rc)}")
         return out[:n].tobytes()
 
-    def __del__(self):
-        try:
-            if self._h:
-                lib().spg_transcript_free(self._h)
-                self._h = ctypes.c_void_p()
-            m = getattr(self, "_merlin", None)
-            if m:
-                self._free_merlin(m)
-                self._merlin = None
-        except Exception:
-            pass
+    def free(self):
+        """the native transcript, then the caller-side merlin of from_native_merlin"""
+        super().free()
+        m = getattr(self, "_merlin", None)
+        if m:
+            self._free_merlin(m)
+            self._merlin = None
 
 
-class RandomTape:
+class RandomTape(_Handle):
     """RandomTape (src/random.rs:7-29) with a caller-supplied init scalar (Montgomery limbs)."""
+
+    _free = "spg_random_tape_free"
 
     def __init__(self, name, init_scalar):
         self._h = ctypes.c_void_p()
         a = _scalars(init_scalar)
-        rc = lib().spg_random_tape_new(ctypes.c_char_p(bytes(name)), _p(a), ctypes.byref(self._h))
+        rc = lib().spg_random_tape_new(bytes(name), _p(a), ctypes.byref(self._h))
         if rc != 0:
             raise SpgError(f"spg_random_tape_new: {SPG_ERRORS.get(rc, rc)}")
 
-    @property
-    def handle(self):
-        return self._h
-
     def random_scalar(self, label):
         out = np.zeros(4, dtype=np.uint64)
-        assert lib().spg_random_tape_scalar(self._h, ctypes.c_char_p(bytes(label)), _p(out)) == 0
+        assert lib().spg_random_tape_scalar(self._h, bytes(label), _p(out)) == 0
         return out
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib().spg_random_tape_free(self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
 
 
 # ---------------------------------------------------------------- R1CSProof
-class R1CSGens:
+class R1CSGens(_Handle):
     """R1CSGens::new(label, _, num_vars) (src/r1csproof.rs:71-79), resident in HBM."""
+
+    _free = "spg_r1cs_gens_free"
 
     def __init__(self, ctx, label, num_vars):
         self.ctx = ctx
         self._h = ctypes.c_void_p()
         lb = np.frombuffer(bytes(label), dtype=np.uint8).copy()
-        ctx.check(lib().spg_r1cs_gens_new(ctx.handle, _p(lb), ctypes.c_size_t(len(label)), ctypes.c_size_t(num_vars),
-                                          ctypes.byref(self._h)), "spg_r1cs_gens_new")
-
-    @property
-    def handle(self):
-        return self._h
+        ctx.call("spg_r1cs_gens_new", _p(lb), len(label), num_vars, ctypes.byref(self._h))
 
     def compressed(self):
         cnt = ctypes.c_size_t(0)
@@ -726,51 +716,31 @@ class R1CSGens:
         self.ctx.check(lib().spg_r1cs_gens_download(self.ctx.handle, self._h, _p(out), ctypes.byref(cnt)), "download")
         return out
 
-    def __del__(self):
-        try:
-            if self._h:
-                lib().spg_r1cs_gens_free(self.ctx.handle, self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
 
-
-class R1CSInst:
+class R1CSInst(_Handle):
     """R1CSInstance uploaded once (CSR + merged CSC in HBM). `cinst` is a workload.CViews().inst."""
+
+    _free = "spg_r1cs_inst_free"
 
     def __init__(self, ctx, cinst):
         self.ctx = ctx
         self.num_instances = int(cinst.num_instances)  # the handle's own matrix count (1: shared by every instance)
         self._h = ctypes.c_void_p()
-        ctx.check(lib().spg_r1cs_inst_new(ctx.handle, ctypes.byref(cinst), ctypes.byref(self._h)), "spg_r1cs_inst_new")
-
-    @property
-    def handle(self):
-        return self._h
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib().spg_r1cs_inst_free(self.ctx.handle, self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
+        ctx.call("spg_r1cs_inst_new", ctypes.byref(cinst), ctypes.byref(self._h))
 
 
 def phase1_round_evals(Ap, Aq, Ax, B, C, D, mode):
     """one x (mode 4) or q (mode 2) round of the phase-1 sumcheck (src/sumcheck.rs:1173-1245): (e0, e2, e3)"""
     out = np.zeros((3, 4), dtype=np.uint64)
-    Ap.ctx.check(lib().spg_phase1_round_evals(Ap.ctx.handle, Ap.handle, Aq.handle, Ax.handle, B._h, C._h, D._h,
-                                              ctypes.c_int(mode), _p(out)), "spg_phase1_round_evals")
+    Ap.ctx.call("spg_phase1_round_evals", Ap.handle, Aq.handle, Ax.handle, B._h, C._h, D._h, mode, _p(out))
     return out
 
 
 def phase2_round_evals(A, ABC, Z, mode, single_inst, num_witness_secs):
     """one y (4), w (3) or p (1) round of the phase-2 sumcheck (src/sumcheck.rs:881-941): (e0, e2, e3)"""
     out = np.zeros((3, 4), dtype=np.uint64)
-    A.ctx.check(lib().spg_phase2_round_evals(A.ctx.handle, A.handle, ABC._h, Z._h, ctypes.c_int(mode),
-                                             ctypes.c_int(1 if single_inst else 0), ctypes.c_size_t(num_witness_secs),
-                                             _p(out)), "spg_phase2_round_evals")
+    A.ctx.call("spg_phase2_round_evals", A.handle, ABC._h, Z._h, mode, 1 if single_inst else 0, num_witness_secs,
+               _p(out))
     return out
 
 
@@ -782,10 +752,8 @@ def r1cs_multiply_vec_block(ctx, inst, num_proofs, max_num_proofs, num_inputs, m
     np_ = np.asarray(num_proofs, dtype=np.uint64)
     ni_ = np.asarray(num_inputs, dtype=np.uint64)
     hs = [ctypes.c_void_p() for _ in range(3)]
-    ctx.check(lib().spg_r1cs_multiply_vec_block(ctx.handle, inst.handle, ctypes.c_size_t(P), _p(np_),
-                                                ctypes.c_size_t(max_num_proofs), _p(ni_), ctypes.c_size_t(max_num_inputs),
-                                                ctypes.c_size_t(num_witness_secs), _p(a), *[ctypes.byref(h) for h in hs]),
-              "spg_r1cs_multiply_vec_block")
+    ctx.call("spg_r1cs_multiply_vec_block", inst.handle, P, _p(np_), max_num_proofs, _p(ni_), max_num_inputs,
+             num_witness_secs, _p(a), *[ctypes.byref(h) for h in hs])
     out = []
     for h in hs:
         t = Pqx.__new__(Pqx)
@@ -799,32 +767,31 @@ def r1cs_multiply_vec_block(ctx, inst, num_proofs, max_num_proofs, num_inputs, m
     return tuple(out)
 
 
-def _abc_args(ctx, inst, num_instances, num_witness_secs, max_num_inputs, num_inputs, evals_rx):
-    """the shared arguments of the eval-table entries, the output tables' instance count and their scalars"""
+def _abc_args(inst, num_instances, num_witness_secs, max_num_inputs, num_inputs, evals_rx):
+    """the shared arguments of the eval-table entries (after the context), the output tables' instance count and
+    their scalars"""
     Pm = inst.num_instances
     assert len(num_inputs) >= max(Pm, 1), "num_inputs: one entry per instance"
     ni_ = np.asarray(num_inputs, dtype=np.uint64)
     n = sum(int(num_witness_secs) * int(x) for x in num_inputs[:Pm])
-    return ni_, Pm, n, (ctx.handle, inst.handle, ctypes.c_size_t(num_instances), ctypes.c_size_t(num_witness_secs),
-                        ctypes.c_size_t(max_num_inputs), _p(ni_), evals_rx.handle)
+    return ni_, Pm, n, (inst.handle, num_instances, num_witness_secs, max_num_inputs, _p(ni_), evals_rx.handle)
 
 
 def r1cs_eval_tables(ctx, inst, num_instances, num_witness_secs, max_num_inputs, num_inputs, evals_rx):
     """R1CSInstance::compute_eval_table_sparse_disjoint_rounds (src/r1csinstance.rs:484-534) on evals_rx (a Buf, eq(rx)):
     (A, B, C) as resident Pqx tables of the handle's own matrix count (1 for a shared instance), one proof row, x in
     natural order"""
-    keep, Pm, n, args = _abc_args(ctx, inst, num_instances, num_witness_secs, max_num_inputs, num_inputs, evals_rx)
+    keep, Pm, n, args = _abc_args(inst, num_instances, num_witness_secs, max_num_inputs, num_inputs, evals_rx)
     hs = [ctypes.c_void_p() for _ in range(3)]
-    ctx.check(lib().spg_r1cs_eval_tables(*args, *[ctypes.byref(h) for h in hs]), "spg_r1cs_eval_tables")
+    ctx.call("spg_r1cs_eval_tables", *args, *[ctypes.byref(h) for h in hs])
     return tuple(_pqx_from_handle(ctx, h, Pm, n) for h in hs)
 
 
 def r1cs_abc_poly(ctx, inst, num_instances, num_witness_secs, max_num_inputs, num_inputs, evals_rx, rA, rB, rC):
     """prove_abc_gen (src/r1csproof.rs:430-465): r_A A + r_B B + r_C C of r1cs_eval_tables in new_rev order, one Pqx"""
-    keep, Pm, n, args = _abc_args(ctx, inst, num_instances, num_witness_secs, max_num_inputs, num_inputs, evals_rx)
+    keep, Pm, n, args = _abc_args(inst, num_instances, num_witness_secs, max_num_inputs, num_inputs, evals_rx)
     h = ctypes.c_void_p()
-    ctx.check(lib().spg_r1cs_abc_poly(*args, _p(_scalars(rA)), _p(_scalars(rB)), _p(_scalars(rC)), ctypes.byref(h)),
-              "spg_r1cs_abc_poly")
+    ctx.call("spg_r1cs_abc_poly", *args, _p(_scalars(rA)), _p(_scalars(rB)), _p(_scalars(rC)), ctypes.byref(h))
     return _pqx_from_handle(ctx, h, Pm, n)
 
 
@@ -833,14 +800,14 @@ def zk_proof_len(num_rounds):
     return 24 + 328 * num_rounds
 
 
-def _zk_prove(ctx, what, fn, head, tail, rounds, n_claims, cap):
+def _zk_prove(ctx, what, head, tail, rounds, n_claims, cap):
     n = ctypes.c_size_t(0)
     cap = zk_proof_len(rounds) if cap is None else cap
     out = np.zeros(max(cap, 1), dtype=np.uint8)
     r = np.zeros((max(rounds, 1), 4), dtype=np.uint64)
     claims = np.zeros((n_claims, 4), dtype=np.uint64)
     blind = np.zeros(4, dtype=np.uint64)
-    rc = fn(*head, *tail, _p(out), ctypes.c_size_t(cap), ctypes.byref(n), _p(r), _p(claims), _p(blind))
+    rc = getattr(lib(), what)(ctx.handle, *head, *tail, _p(out), cap, ctypes.byref(n), _p(r), _p(claims), _p(blind))
     ctx.last_len = int(n.value)
     ctx.check(rc, what)
     return out[:n.value].tobytes(), r[:rounds], claims, blind
@@ -852,9 +819,9 @@ def zk_phase1_prove(ctx, gens, nx, nq, np_, Ap, Aq, Ax, B, C, D, transcript, tap
     A (B C - D): Ap, Aq, Ax (Bufs) and B, C, D (Pqx) are bound in place. Returns (proof bytes, r [rounds, 4],
     claims [4, 4] = (Ap Aq Ax, B, C, D), blinds_evals[last]); ctx.last_len keeps *len."""
     c, b = _opt(claim), _opt(blind_claim)
-    head = (ctx.handle, gens.handle, _optp(c), _optp(b), ctypes.c_size_t(nx), ctypes.c_size_t(nq), ctypes.c_size_t(np_))
+    head = (gens.handle, _optp(c), _optp(b), nx, nq, np_)
     tail = (Ap.handle, Aq.handle, Ax.handle, B._h, C._h, D._h, transcript.handle, tape.handle)
-    res = _zk_prove(ctx, "spg_zk_phase1_prove", lib().spg_zk_phase1_prove, head, tail, nx + nq + np_, 4, cap)
+    res = _zk_prove(ctx, "spg_zk_phase1_prove", head, tail, nx + nq + np_, 4, cap)
     Ap.n, Aq.n, Ax.n = 1, 1, 1
     return res
 
@@ -865,10 +832,9 @@ def zk_phase2_prove(ctx, gens, ny, nw, np_, single_inst, num_witness_secs, eq, A
     ABC and Z (Pqx, q bound) are bound in place. Returns (proof bytes, r, claims [3, 4] = (eq, ABC, Z),
     blinds_evals[last])."""
     c, b = _opt(claim), _opt(blind_claim)
-    head = (ctx.handle, gens.handle, _optp(c), _optp(b), ctypes.c_size_t(ny), ctypes.c_size_t(nw), ctypes.c_size_t(np_),
-            ctypes.c_int(1 if single_inst else 0), ctypes.c_size_t(num_witness_secs))
+    head = (gens.handle, _optp(c), _optp(b), ny, nw, np_, 1 if single_inst else 0, num_witness_secs)
     tail = (eq.handle, ABC._h, Z._h, transcript.handle, tape.handle)
-    res = _zk_prove(ctx, "spg_zk_phase2_prove", lib().spg_zk_phase2_prove, head, tail, ny + nw + np_, 3, cap)
+    res = _zk_prove(ctx, "spg_zk_phase2_prove", head, tail, ny + nw + np_, 3, cap)
     eq.n = 1
     return res
 
@@ -881,9 +847,8 @@ def zk_sumcheck_verify(ctx, gens, comm_claim, num_rounds, transcript, proof, deg
     pb = _bytes_arr(proof)
     post = np.zeros(32, dtype=np.uint8)
     r = np.zeros((max(num_rounds, 1), 4), dtype=np.uint64)
-    rc = lib().spg_zk_sumcheck_verify(ctx.handle, gens.handle, _p(cc), ctypes.c_size_t(num_rounds),
-                                      ctypes.c_size_t(degree_bound), transcript.handle, _p(pb),
-                                      ctypes.c_size_t(len(proof)), _p(post), _p(r))
+    rc = lib().spg_zk_sumcheck_verify(ctx.handle, gens.handle, _p(cc), num_rounds, degree_bound, transcript.handle,
+                                      _p(pb), len(proof), _p(post), _p(r))
     ok, why = _verify_result(ctx, rc, "spg_zk_sumcheck_verify")
     return ok, post.tobytes(), r[:num_rounds], why
 
@@ -893,7 +858,6 @@ def _buf_from_handle(ctx, h):
     b = Buf.__new__(Buf)
     b.ctx = ctx
     b._h = h
-    lib().spg_buf_len.restype = ctypes.c_size_t
     b.n = int(lib().spg_buf_len(h))
     return b
 
@@ -904,7 +868,6 @@ def _buf_array(bufs):
 
 
 def _sync_len(bufs):
-    lib().spg_buf_len.restype = ctypes.c_size_t
     for b in bufs:
         b.n = int(lib().spg_buf_len(b.handle))
 
@@ -923,16 +886,17 @@ def hash_layer(ctx, eval_table, addrs, derefs, read_ts, audit_ts, r_hash, r_mult
     a, d, t = _buf_array(addrs), _buf_array(derefs), _buf_array(read_ts)
     init, audit = ctypes.c_void_p(), ctypes.c_void_p()
     reads, writes = (ctypes.c_void_p * n)(), (ctypes.c_void_p * n)()
-    ctx.check(lib().spg_hash_layer(ctx.handle, eval_table.handle, a, d, t, ctypes.c_size_t(n), audit_ts.handle,
-                                   _p(_scalars(r_hash)), _p(_scalars(r_multiset)), ctypes.byref(init), reads, writes,
-                                   ctypes.byref(audit)), "spg_hash_layer")
+    ctx.call("spg_hash_layer", eval_table.handle, a, d, t, n, audit_ts.handle, _p(_scalars(r_hash)),
+             _p(_scalars(r_multiset)), ctypes.byref(init), reads, writes, ctypes.byref(audit))
     mk = lambda h: _buf_from_handle(ctx, ctypes.c_void_p(h))  # noqa: E731
     return mk(init.value), [mk(h) for h in reads], [mk(h) for h in writes], mk(audit.value)
 
 
-class ProductCircuits:
+class ProductCircuits(_Handle):
     """nc ProductCircuits of M leaves each (src/product_tree.rs:18-108) built on the device from Bufs of one
     power-of-two length M >= 2 (spg_prodc_*); the inputs are left unchanged."""
+
+    _free = "spg_prodc_free"
 
     def __init__(self, ctx, polys):
         polys = list(polys)
@@ -944,12 +908,7 @@ class ProductCircuits:
         self.ctx = ctx
         self.nc, self.M = len(polys), M
         self._h = ctypes.c_void_p()
-        ctx.check(lib().spg_prodc_new(ctx.handle, _buf_array(polys), ctypes.c_size_t(self.nc), ctypes.byref(self._h)),
-                  "spg_prodc_new")
-
-    @property
-    def handle(self):
-        return self._h
+        ctx.call("spg_prodc_new", _buf_array(polys), self.nc, ctypes.byref(self._h))
 
     @property
     def shape(self):
@@ -961,7 +920,7 @@ class ProductCircuits:
     def evaluate(self):
         """ProductCircuit::evaluate of every circuit: [nc, 4]"""
         out = np.zeros((self.nc, 4), dtype=np.uint64)
-        self.ctx.check(lib().spg_prodc_evaluate(self.ctx.handle, self._h, _p(out)), "spg_prodc_evaluate")
+        self.ctx.call("spg_prodc_evaluate", self._h, _p(out))
         return out
 
     def layer(self, c, k):
@@ -970,8 +929,7 @@ class ProductCircuits:
             raise ValueError("ProductCircuits.layer: no such circuit layer")
         half = self.M >> (k + 1)
         left, right = np.zeros((half, 4), dtype=np.uint64), np.zeros((half, 4), dtype=np.uint64)
-        self.ctx.check(lib().spg_prodc_layer(self.ctx.handle, self._h, ctypes.c_size_t(c), ctypes.c_size_t(k), _p(left),
-                                             _p(right)), "spg_prodc_layer")
+        self.ctx.call("spg_prodc_layer", self._h, c, k, _p(left), _p(right))
         return left, right
 
     def proof_size(self, nd):
@@ -989,24 +947,12 @@ class ProductCircuits:
         out = np.zeros(max(cap, 1), dtype=np.uint8)
         n, rl = ctypes.c_size_t(0), ctypes.c_size_t(0)
         rand = np.zeros((self.M.bit_length(), 4), dtype=np.uint64)
-        rc = lib().spg_prodc_prove_batched(self.ctx.handle, self._h, _buf_array(flat), ctypes.c_size_t(len(dotp)),
-                                           transcript.handle, _p(out), ctypes.c_size_t(cap), ctypes.byref(n), _p(rand),
-                                           ctypes.byref(rl))
+        rc = lib().spg_prodc_prove_batched(self.ctx.handle, self._h, _buf_array(flat), len(dotp), transcript.handle,
+                                           _p(out), cap, ctypes.byref(n), _p(rand), ctypes.byref(rl))
         self.last_len = int(n.value)
         self.ctx.check(rc, "spg_prodc_prove_batched")
         _sync_len(flat)
         return out[:n.value].tobytes(), rand[:rl.value].copy()
-
-    def free(self):
-        if self._h:
-            lib().spg_prodc_free(self.ctx.handle, self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def prove_cubic_batched(ctx, claim, num_rounds, A_par, B_par, C_par, A_seq, B_seq, C_seq, coeffs, transcript):
@@ -1031,11 +977,9 @@ def prove_cubic_batched(ctx, claim, num_rounds, A_par, B_par, C_par, A_seq, B_se
     r = np.zeros((max(num_rounds, 1), 4), dtype=np.uint64)
     cpar = np.zeros((2 * n_par + 1, 4), dtype=np.uint64)
     cseq = np.zeros((3, max(n_seq, 1), 4), dtype=np.uint64)
-    ctx.check(lib().spg_prove_cubic_batched(
-        ctx.handle, _p(_scalars(claim)), ctypes.c_size_t(num_rounds), _buf_array(A_par), _buf_array(B_par),
-        ctypes.c_size_t(n_par), C_par.handle if C_par is not None else None, _buf_array(A_seq), _buf_array(B_seq),
-        _buf_array(C_seq), ctypes.c_size_t(n_seq), _p(co), transcript.handle, _p(polys), _p(r), _p(cpar), _p(cseq)),
-        "spg_prove_cubic_batched")
+    ctx.call("spg_prove_cubic_batched", _p(_scalars(claim)), num_rounds, _buf_array(A_par), _buf_array(B_par), n_par,
+             C_par.handle if C_par is not None else None, _buf_array(A_seq), _buf_array(B_seq), _buf_array(C_seq), n_seq,
+             _p(co), transcript.handle, _p(polys), _p(r), _p(cpar), _p(cseq))
     _sync_len(bufs)
     return polys[:num_rounds], r[:num_rounds], cpar if C_par is not None else cpar[:0], cseq[:, :n_seq]
 
@@ -1045,37 +989,23 @@ def r1cs_multi_evaluate(ctx, inst, num_instances, rx, ry):
     rx = _scalars(rx)
     ry = _scalars(ry)
     out = np.zeros((3 * num_instances, 4), dtype=np.uint64)
-    ctx.check(lib().spg_r1cs_multi_evaluate(ctx.handle, inst.handle, _p(rx), ctypes.c_size_t(rx.shape[0]), _p(ry),
-                                            ctypes.c_size_t(ry.shape[0]), _p(out)), "spg_r1cs_multi_evaluate")
+    ctx.call("spg_r1cs_multi_evaluate", inst.handle, _p(rx), rx.shape[0], _p(ry), ry.shape[0], _p(out))
     return out
 
 
-class R1CSWitness:
+class R1CSWitness(_Handle):
     """Witness sections (Vec<&ProverWitnessSecInfo>) resident in HBM. `secs` is workload.CViews().secs.
     shard=(p0, p1): upload only instances [p0, p1) of the per-instance sections (sharded proving)."""
+
+    _free = "spg_r1cs_witness_free"
 
     def __init__(self, ctx, secs, nws, shard=None):
         self.ctx = ctx
         self._h = ctypes.c_void_p()
         if shard is None:
-            ctx.check(lib().spg_r1cs_witness_new(ctx.handle, secs, ctypes.c_size_t(nws), ctypes.byref(self._h)),
-                      "spg_r1cs_witness_new")
+            ctx.call("spg_r1cs_witness_new", secs, nws, ctypes.byref(self._h))
         else:
-            ctx.check(lib().spg_r1cs_witness_new_shard(ctx.handle, secs, ctypes.c_size_t(nws), ctypes.c_size_t(shard[0]),
-                                                       ctypes.c_size_t(shard[1]), ctypes.byref(self._h)),
-                      "spg_r1cs_witness_new_shard")
-
-    @property
-    def handle(self):
-        return self._h
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib().spg_r1cs_witness_free(self.ctx.handle, self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
+            ctx.call("spg_r1cs_witness_new_shard", secs, nws, shard[0], shard[1], ctypes.byref(self._h))
 
 
 def r1cs_prove(ctx, gens, inst, witness, num_instances, max_num_proofs, num_proofs, max_num_inputs, num_inputs,
@@ -1087,11 +1017,8 @@ def r1cs_prove(ctx, gens, inst, witness, num_instances, max_num_proofs, num_proo
     chl = (ctypes.c_size_t * 4)()
     npf = (ctypes.c_size_t * num_instances)(*num_proofs)
     nin = (ctypes.c_size_t * num_instances)(*num_inputs)
-    rc = lib().spg_r1cs_prove(ctx.handle, gens.handle, inst.handle, ctypes.c_size_t(num_instances),
-                              ctypes.c_size_t(max_num_proofs), npf, ctypes.c_size_t(max_num_inputs), nin,
-                              witness.handle, transcript.handle, tape.handle, _p(buf), ctypes.c_size_t(cap),
-                              ctypes.byref(ln), _p(ch), chl)
-    ctx.check(rc, "spg_r1cs_prove")
+    ctx.call("spg_r1cs_prove", gens.handle, inst.handle, num_instances, max_num_proofs, npf, max_num_inputs, nin,
+             witness.handle, transcript.handle, tape.handle, _p(buf), cap, ctypes.byref(ln), _p(ch), chl)
     out, o = [], 0
     for L in list(chl):
         out.append(ch[o:o + L].copy())
@@ -1110,8 +1037,7 @@ def r1cs_gens_commit(ctx, gens, Z):
     z = _scalars(Z)
     out = np.zeros(32 * 4096, dtype=np.uint8)
     L = ctypes.c_size_t(0)
-    ctx.check(lib().spg_r1cs_gens_commit(ctx.handle, gens.handle, _p(z), ctypes.c_size_t(z.shape[0]), _p(out),
-                                         ctypes.c_size_t(out.shape[0]), ctypes.byref(L)), "spg_r1cs_gens_commit")
+    ctx.call("spg_r1cs_gens_commit", gens.handle, _p(z), z.shape[0], _p(out), out.shape[0], ctypes.byref(L))
     return [out[32 * i: 32 * i + 32].tobytes() for i in range(L.value)]
 
 
@@ -1128,17 +1054,15 @@ def r1cs_verify(ctx, gens, num_instances, max_num_proofs, num_proofs, max_num_in
         keep += [a, b, cl, blob]
         secs[i] = CWitnessComm(len(npf), a, b, cl, blob.ctypes.data)
     ev = _scalars(evals)
-    buf = np.frombuffer(bytes(proof), dtype=np.uint8).copy() if len(proof) else np.zeros(1, np.uint8)
+    buf = _bytes_arr(proof)
     ch = np.zeros((4096, 4), dtype=np.uint64)
     chl = (ctypes.c_size_t * 4)()
     npf = (ctypes.c_size_t * num_instances)(*num_proofs)
-    rc = lib().spg_r1cs_verify(ctx.handle, gens.handle, ctypes.c_size_t(num_instances), ctypes.c_size_t(max_num_proofs),
-                               npf, ctypes.c_size_t(max_num_inputs), secs, ctypes.c_size_t(len(sections)),
-                               ctypes.c_size_t(num_cons), _p(ev), transcript.handle, _p(buf), ctypes.c_size_t(len(proof)),
-                               _p(ch), chl)
-    if rc == SPG_E_VERIFY:
-        return False, lib().spg_last_error(ctx.handle).decode(errors="replace"), None
-    ctx.check(rc, "spg_r1cs_verify")
+    rc = lib().spg_r1cs_verify(ctx.handle, gens.handle, num_instances, max_num_proofs, npf, max_num_inputs, secs,
+                               len(sections), num_cons, _p(ev), transcript.handle, _p(buf), len(proof), _p(ch), chl)
+    ok, why = _verify_result(ctx, rc, "spg_r1cs_verify")
+    if not ok:
+        return False, why, None
     out, o = [], 0
     for L in list(chl):
         out.append(ch[o:o + L].copy())
@@ -1154,10 +1078,12 @@ def shard_range(num_instances, rank, nranks):
     return begin(rank), begin(rank + 1)
 
 
-class SparkCommitment:
+class SparkCommitment(_Handle):
     """SparseMatPolynomial::multi_commit over the 3P matrices of an R1CS instance (src/sparse_mlpoly.rs:566-587)
     with SparseMatPolyCommitmentGens::new(label, nvx, nvy, gens_nnz, gens_batch). The dense representation
     stays in HBM for SparkCommitment.prove. `cinst` is a workload.CViews().inst."""
+
+    _free = "spg_spark_free"
 
     def __init__(self, ctx, cinst, label, gens_nnz, gens_batch=3, cap=1 << 22):
         self.ctx = ctx
@@ -1167,14 +1093,9 @@ class SparkCommitment:
         buf = np.zeros(cap, dtype=np.uint8)
         ln = ctypes.c_size_t(0)
         lb = (ctypes.c_uint8 * len(label)).from_buffer_copy(label)
-        ctx.check(lib().spg_spark_commit(ctx.handle, ctypes.byref(cinst), lb, ctypes.c_size_t(len(label)),
-                                         ctypes.c_size_t(gens_nnz), ctypes.c_size_t(gens_batch), ctypes.byref(self._h),
-                                         _p(buf), ctypes.c_size_t(cap), ctypes.byref(ln)), "spg_spark_commit")
+        ctx.call("spg_spark_commit", ctypes.byref(cinst), lb, len(label), gens_nnz, gens_batch, ctypes.byref(self._h),
+                 _p(buf), cap, ctypes.byref(ln))
         self.bytes = buf[: ln.value].tobytes()
-
-    @property
-    def handle(self):
-        return self._h
 
     def prove(self, rx, ry, evals, transcript, tape, cap=1 << 24):
         """SparseMatPolyEvalProof::prove (src/sparse_mlpoly.rs:1497-1564) -> bincode bytes"""
@@ -1183,56 +1104,36 @@ class SparkCommitment:
         ev = _scalars(evals)
         buf = self.ctx.out_buf(cap)
         ln = ctypes.c_size_t(0)
-        self.ctx.check(lib().spg_spark_prove(self.ctx.handle, self._h, _p(rx), ctypes.c_size_t(rx.shape[0]), _p(ry),
-                                             ctypes.c_size_t(ry.shape[0]), _p(ev), ctypes.c_size_t(ev.shape[0]),
-                                             transcript.handle, tape.handle, _p(buf), ctypes.c_size_t(cap),
-                                             ctypes.byref(ln)), "spg_spark_prove")
+        self.ctx.call("spg_spark_prove", self._h, _p(rx), rx.shape[0], _p(ry), ry.shape[0], _p(ev), ev.shape[0],
+                      transcript.handle, tape.handle, _p(buf), cap, ctypes.byref(ln))
         return buf[: ln.value].tobytes()
 
     def verify(self, rx, ry, evals, transcript, proof):
         """SparseMatPolyEvalProof::verify (src/sparse_mlpoly.rs:1566-1610) -> (ok, reason)"""
         rx, ry, ev = _scalars(rx), _scalars(ry), _scalars(evals)
-        buf = np.frombuffer(bytes(proof), dtype=np.uint8).copy() if len(proof) else np.zeros(1, np.uint8)
-        rc = lib().spg_spark_verify(self.ctx.handle, self._h, _p(rx), ctypes.c_size_t(rx.shape[0]), _p(ry),
-                                    ctypes.c_size_t(ry.shape[0]), _p(ev), ctypes.c_size_t(ev.shape[0]),
-                                    transcript.handle, _p(buf), ctypes.c_size_t(len(proof)))
-        if rc == SPG_E_VERIFY:
-            return False, lib().spg_last_error(self.ctx.handle).decode(errors="replace")
-        self.ctx.check(rc, "spg_spark_verify")
-        return True, ""
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib().spg_spark_free(self.ctx.handle, self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
+        buf = _bytes_arr(proof)
+        rc = lib().spg_spark_verify(self.ctx.handle, self._h, _p(rx), rx.shape[0], _p(ry), ry.shape[0], _p(ev),
+                                    ev.shape[0], transcript.handle, _p(buf), len(proof))
+        return _verify_result(self.ctx, rc, "spg_spark_verify")
 
 
-class SnarkComp:
+class SnarkComp(_Handle):
     """SNARK::multi_encode (multi=True) / SNARK::encode of one R1CS instance (src/lib.rs:793-829); `cinst` is a
     workload.SnarkViews().block / .pairwise / .perm_root (spg_snark_instance)."""
+
+    _free = "spg_snark_comp_free"
 
     def __init__(self, ctx, cinst, multi=False):
         self.ctx = ctx
         self._h = ctypes.c_void_p()
-        ctx.check(lib().spg_snark_encode(ctx.handle, ctypes.byref(cinst), ctypes.c_int(1 if multi else 0),
-                                         ctypes.byref(self._h)), "spg_snark_encode")
-
-    @property
-    def handle(self):
-        return self._h
+        ctx.call("spg_snark_encode", ctypes.byref(cinst), 1 if multi else 0, ctypes.byref(self._h))
 
     def comm_bytes(self, as_list):
         """bincode(Vec<ComputationCommitment>) (as_list) or bincode(ComputationCommitment) (spg_snark_comm_bytes)"""
         ln = ctypes.c_size_t(0)
-        lib().spg_snark_comm_bytes(self.ctx.handle, self._h, ctypes.c_int(1 if as_list else 0), None,
-                                   ctypes.c_size_t(0), ctypes.byref(ln))
+        lib().spg_snark_comm_bytes(self.ctx.handle, self._h, 1 if as_list else 0, None, 0, ctypes.byref(ln))
         buf = np.zeros(max(ln.value, 1), dtype=np.uint8)
-        self.ctx.check(lib().spg_snark_comm_bytes(self.ctx.handle, self._h, ctypes.c_int(1 if as_list else 0),
-                                                  _p(buf), ctypes.c_size_t(ln.value), ctypes.byref(ln)),
-                       "spg_snark_comm_bytes")
+        self.ctx.call("spg_snark_comm_bytes", self._h, 1 if as_list else 0, _p(buf), ln.value, ctypes.byref(ln))
         return buf[: ln.value].tobytes()
 
     def comm_map(self):
@@ -1240,8 +1141,7 @@ class SnarkComp:
         idx = np.zeros(1 << 16, dtype=np.uintp)
         lens = np.zeros(1 << 12, dtype=np.uintp)
         n = ctypes.c_size_t(0)
-        self.ctx.check(lib().spg_snark_comm_map(self.ctx.handle, self._h, _p(idx), ctypes.c_size_t(len(idx)), _p(lens),
-                                                ctypes.c_size_t(len(lens)), ctypes.byref(n)), "spg_snark_comm_map")
+        self.ctx.call("spg_snark_comm_map", self._h, _p(idx), len(idx), _p(lens), len(lens), ctypes.byref(n))
         out, o = [], 0
         for g in range(n.value):
             out.append([int(x) for x in idx[o:o + int(lens[g])]])
@@ -1256,131 +1156,81 @@ class SnarkComp:
         c = cls.__new__(cls)
         c.ctx = ctx
         c._h = ctypes.c_void_p()
-        buf = np.frombuffer(bytes(comm), dtype=np.uint8).copy() if len(comm) else np.zeros(1, np.uint8)
+        buf = _bytes_arr(comm)
         flat = np.array([k for l in (comm_map or []) for k in l] or [0], dtype=np.uintp)
         lens = np.array([len(l) for l in (comm_map or [])] or [0], dtype=np.uintp)
-        ctx.check(lib().spg_snark_comm_load(ctx.handle, _p(buf), ctypes.c_size_t(len(comm)),
-                                            ctypes.c_int(1 if as_list else 0), _p(flat), _p(lens),
-                                            ctypes.c_size_t(len(comm_map or [])), ctypes.c_size_t(num_cons),
-                                            *[ctypes.c_size_t(x) for x in gens], ctypes.byref(c._h)),
-                  "spg_snark_comm_load")
+        ctx.call("spg_snark_comm_load", _p(buf), len(comm), 1 if as_list else 0, _p(flat), _p(lens),
+                 len(comm_map or []), num_cons, *gens, ctypes.byref(c._h))
         return c
 
-    def __del__(self):
-        try:
-            if self._h:
-                lib().spg_snark_comp_free(self.ctx.handle, self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
 
-
-class SnarkWitness:
+class SnarkWitness(_Handle):
     """SNARK::prove's run-time inputs with block_vars / exec inputs resident in HBM (workload.SnarkViews().inputs)"""
+
+    _free = "spg_snark_witness_free"
 
     def __init__(self, ctx, cinputs):
         self.ctx = ctx
         self._h = ctypes.c_void_p()
-        ctx.check(lib().spg_snark_witness_new(ctx.handle, ctypes.byref(cinputs), ctypes.byref(self._h)),
-                  "spg_snark_witness_new")
-
-    @property
-    def handle(self):
-        return self._h
-
-    def __del__(self):
-        try:
-            if self._h:
-                lib().spg_snark_witness_free(self.ctx.handle, self._h)
-                self._h = ctypes.c_void_p()
-        except Exception:
-            pass
+        ctx.call("spg_snark_witness_new", ctypes.byref(cinputs), ctypes.byref(self._h))
 
 
 def snark_prove(ctx, block, pairwise, perm_root, witness, vars_gens, transcript, tape, cap=1 << 24):
     """SNARK::prove (src/lib.rs:971-2746) -> bincode(SNARK)"""
     buf = ctx.out_buf(cap)
     ln = ctypes.c_size_t(0)
-    ctx.check(lib().spg_snark_prove(ctx.handle, block.handle, pairwise.handle, perm_root.handle, witness.handle,
-                                    vars_gens.handle, transcript.handle, tape.handle, _p(buf), ctypes.c_size_t(cap),
-                                    ctypes.byref(ln)), "spg_snark_prove")
+    ctx.call("spg_snark_prove", block.handle, pairwise.handle, perm_root.handle, witness.handle, vars_gens.handle,
+             transcript.handle, tape.handle, _p(buf), cap, ctypes.byref(ln))
     return buf[: ln.value].tobytes()
-
-
-SPG_E_VERIFY = -6
-SPG_E_ARG = -1
 
 
 def snark_verify(ctx, block, pairwise, perm_root, inputs, vars_gens, transcript, proof):
     """SNARK::verify (src/lib.rs:2750-3881) of bincode(SNARK) bytes against the encoded instances and the public
     inputs (`inputs`: workload.SnarkViews().inputs; only its sizes, input / output and init memory lists are read).
     Returns (True, "") when the proof verifies, (False, reason) when it does not; raises on bad arguments."""
-    buf = np.frombuffer(bytes(proof), dtype=np.uint8).copy() if len(proof) else np.zeros(1, np.uint8)
+    buf = _bytes_arr(proof)
     rc = lib().spg_snark_verify(ctx.handle, block.handle, pairwise.handle, perm_root.handle, ctypes.byref(inputs),
-                                vars_gens.handle, transcript.handle, _p(buf), ctypes.c_size_t(len(proof)))
-    if rc == SPG_E_VERIFY:
-        return False, lib().spg_last_error(ctx.handle).decode(errors="replace")
-    ctx.check(rc, "spg_snark_verify")
-    return True, ""
+                                vars_gens.handle, transcript.handle, _p(buf), len(proof))
+    return _verify_result(ctx, rc, "spg_snark_verify")
 
 
 def snark_verify_public(ctx, block, pairwise, perm_root, public, vars_gens, transcript, proof):
     """SNARK::verify from what the reference verifier is given (spg_snark_verify_public): SnarkComp.load'ed
     commitments and `public` (a workload.CSnarkPublic). Returns (True, "") / (False, reason); raises on bad arguments."""
-    buf = np.frombuffer(bytes(proof), dtype=np.uint8).copy() if len(proof) else np.zeros(1, np.uint8)
+    buf = _bytes_arr(proof)
     rc = lib().spg_snark_verify_public(ctx.handle, block.handle, pairwise.handle, perm_root.handle,
-                                       ctypes.byref(public), vars_gens.handle, transcript.handle, _p(buf),
-                                       ctypes.c_size_t(len(proof)))
-    if rc == SPG_E_VERIFY:
-        return False, lib().spg_last_error(ctx.handle).decode(errors="replace")
-    ctx.check(rc, "spg_snark_verify_public")
-    return True, ""
+                                       ctypes.byref(public), vars_gens.handle, transcript.handle, _p(buf), len(proof))
+    return _verify_result(ctx, rc, "spg_snark_verify_public")
 
 
 def points_sum_compress(parts):
     """spg_points_sum_compress (host only): encoding of the sum of 128-byte partial points"""
     buf = np.frombuffer(b"".join(parts), dtype=np.uint8).copy() if parts else np.zeros(1, np.uint8)
     out = np.zeros(32, dtype=np.uint8)
-    rc = lib().spg_points_sum_compress(_p(buf), ctypes.c_size_t(len(parts)), _p(out))
+    rc = lib().spg_points_sum_compress(_p(buf), len(parts), _p(out))
     assert rc == 0, rc
     return out.tobytes()
 
 
 # ---- Hyrax dense polynomial commitments and evaluation proofs on device vectors (csrc/polyeval.hip)
-class PolyGens:
+class PolyGens(_Handle):
     """PolyCommitmentGens::new(num_vars, label) (src/dense_mlpoly.rs:31-38), resident in HBM: n = 2^(num_vars -
     num_vars/2) row generators G_0 .. G_{n-1}, G_n for evaluations, and h."""
+
+    _free = "spg_poly_gens_free"
 
     def __init__(self, ctx, label, num_vars):
         self.ctx = ctx
         self._h = ctypes.c_void_p()
         lb = np.frombuffer(bytes(label), dtype=np.uint8).copy()
-        ctx.check(lib().spg_poly_gens_new(ctx.handle, _p(lb), ctypes.c_size_t(len(label)), ctypes.c_size_t(num_vars),
-                                          ctypes.byref(self._h)), "spg_poly_gens_new")
-        lib().spg_poly_gens_n.restype = ctypes.c_size_t
-        lib().spg_poly_gens_n.argtypes = [ctypes.c_void_p]
+        ctx.call("spg_poly_gens_new", _p(lb), len(label), num_vars, ctypes.byref(self._h))
         self.n = int(lib().spg_poly_gens_n(self._h))
-
-    @property
-    def handle(self):
-        return self._h
 
     def compressed(self):
         """[n + 2, 32]: G_0 .. G_n, h"""
         out = np.zeros((self.n + 2, 32), dtype=np.uint8)
-        self.ctx.check(lib().spg_poly_gens_download(self.ctx.handle, self._h, _p(out)), "spg_poly_gens_download")
+        self.ctx.call("spg_poly_gens_download", self._h, _p(out))
         return out
-
-    def free(self):
-        if self._h:
-            lib().spg_poly_gens_free(self.ctx.handle, self._h)
-            self._h = ctypes.c_void_p()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
 
 
 def _opt(x):
@@ -1401,14 +1251,14 @@ def _prove_call(ctx, what, call, cap):
     n = ctypes.c_size_t(0)
     if cap is None:
         probe = np.zeros(1, dtype=np.uint8)
-        rc = call(_p(probe), ctypes.c_size_t(0), ctypes.byref(n))
+        rc = call(_p(probe), 0, ctypes.byref(n))
         ctx.last_len = int(n.value)
         if rc != SPG_E_ARG or n.value == 0:
             ctx.check(rc, what)
             raise SpgError(f"{what}: no proof size")
         cap = int(n.value)
     out = np.zeros(max(cap, 1), dtype=np.uint8)
-    rc = call(_p(out), ctypes.c_size_t(cap), ctypes.byref(n))
+    rc = call(_p(out), cap, ctypes.byref(n))
     ctx.last_len = int(n.value)
     ctx.check(rc, what)
     return out[:n.value].tobytes()
@@ -1428,9 +1278,7 @@ def poly_commit(ctx, gens, Z, num_vars, offset=0, blinds=None):
     out = np.zeros((rows, 32), dtype=np.uint8)
     b = _opt(blinds)
     L = ctypes.c_size_t(0)
-    ctx.check(lib().spg_poly_commit(ctx.handle, gens.handle, Z.handle, ctypes.c_size_t(offset),
-                                    ctypes.c_size_t(num_vars), _optp(b), _p(out), ctypes.c_size_t(out.size),
-                                    ctypes.byref(L)), "spg_poly_commit")
+    ctx.call("spg_poly_commit", gens.handle, Z.handle, offset, num_vars, _optp(b), _p(out), out.size, ctypes.byref(L))
     return out[:L.value]
 
 
@@ -1441,9 +1289,8 @@ def poly_eval_prove(ctx, gens, Z, r, Zr, transcript, tape, offset=0, blinds=None
     czr = np.zeros(32, dtype=np.uint8)
 
     def call(out, c, n):
-        return lib().spg_poly_eval_prove(ctx.handle, gens.handle, Z.handle, ctypes.c_size_t(offset), _p(rr),
-                                         ctypes.c_size_t(rr.shape[0]), _p(zr), _optp(b), _optp(bz), transcript.handle,
-                                         tape.handle, out, c, n, _p(czr))
+        return lib().spg_poly_eval_prove(ctx.handle, gens.handle, Z.handle, offset, _p(rr), rr.shape[0], _p(zr),
+                                         _optp(b), _optp(bz), transcript.handle, tape.handle, out, c, n, _p(czr))
 
     proof = _prove_call(ctx, "spg_poly_eval_prove", call, cap)
     return proof, czr.tobytes()
@@ -1452,18 +1299,16 @@ def poly_eval_prove(ctx, gens, Z, r, Zr, transcript, tape, offset=0, blinds=None
 def poly_eval_verify(ctx, gens, r, C_Zr, comm, transcript, proof):
     """PolyEvalProof::verify (src/dense_mlpoly.rs:492-514): comm [L, 32], C_Zr 32 bytes. Returns (ok, reason)."""
     rr, cz, cm, pf = _scalars(r), _bytes_arr(C_Zr), np.ascontiguousarray(comm, dtype=np.uint8), _bytes_arr(proof)
-    rc = lib().spg_poly_eval_verify(ctx.handle, gens.handle, _p(rr), ctypes.c_size_t(rr.shape[0]), _p(cz), _p(cm),
-                                    ctypes.c_size_t(cm.size // 32), transcript.handle, _p(pf),
-                                    ctypes.c_size_t(len(proof)))
+    rc = lib().spg_poly_eval_verify(ctx.handle, gens.handle, _p(rr), rr.shape[0], _p(cz), _p(cm), cm.size // 32,
+                                    transcript.handle, _p(pf), len(proof))
     return _verify_result(ctx, rc, "spg_poly_eval_verify")
 
 
 def poly_eval_verify_plain(ctx, gens, r, Zr, comm, transcript, proof):
     """PolyEvalProof::verify_plain (src/dense_mlpoly.rs:516-528). Returns (ok, reason)."""
     rr, zr, cm, pf = _scalars(r), _scalars(Zr), np.ascontiguousarray(comm, dtype=np.uint8), _bytes_arr(proof)
-    rc = lib().spg_poly_eval_verify_plain(ctx.handle, gens.handle, _p(rr), ctypes.c_size_t(rr.shape[0]), _p(zr), _p(cm),
-                                          ctypes.c_size_t(cm.size // 32), transcript.handle, _p(pf),
-                                          ctypes.c_size_t(len(proof)))
+    rc = lib().spg_poly_eval_verify_plain(ctx.handle, gens.handle, _p(rr), rr.shape[0], _p(zr), _p(cm), cm.size // 32,
+                                          transcript.handle, _p(pf), len(proof))
     return _verify_result(ctx, rc, "spg_poly_eval_verify_plain")
 
 
@@ -1475,9 +1320,8 @@ def poly_eval_prove_batched_points(ctx, gens, Z, num_vars, r_list, Zr_list, tran
     rl = np.ascontiguousarray(r_list, dtype=np.uint64).reshape(K * num_vars, 4) if K * num_vars else np.zeros((1, 4), np.uint64)
 
     def call(out, c, n):
-        return lib().spg_poly_eval_prove_batched_points(ctx.handle, gens.handle, Z.handle, ctypes.c_size_t(offset),
-                                                        ctypes.c_size_t(num_vars), _p(rl), ctypes.c_size_t(K), _p(zr),
-                                                        transcript.handle, tape.handle, out, c, n)
+        return lib().spg_poly_eval_prove_batched_points(ctx.handle, gens.handle, Z.handle, offset, num_vars, _p(rl), K,
+                                                        _p(zr), transcript.handle, tape.handle, out, c, n)
 
     return _prove_call(ctx, "spg_poly_eval_prove_batched_points", call, cap)
 
@@ -1488,10 +1332,8 @@ def poly_eval_verify_plain_batched_points(ctx, gens, num_vars, r_list, Zr_list, 
     K = zr.shape[0]
     rl = np.ascontiguousarray(r_list, dtype=np.uint64).reshape(K * num_vars, 4) if K * num_vars else np.zeros((1, 4), np.uint64)
     cm, pf = np.ascontiguousarray(comm, dtype=np.uint8), _bytes_arr(proof)
-    rc = lib().spg_poly_eval_verify_plain_batched_points(ctx.handle, gens.handle, ctypes.c_size_t(num_vars), _p(rl),
-                                                         ctypes.c_size_t(K), _p(zr), _p(cm),
-                                                         ctypes.c_size_t(cm.size // 32), transcript.handle, _p(pf),
-                                                         ctypes.c_size_t(len(proof)))
+    rc = lib().spg_poly_eval_verify_plain_batched_points(ctx.handle, gens.handle, num_vars, _p(rl), K, _p(zr), _p(cm),
+                                                         cm.size // 32, transcript.handle, _p(pf), len(proof))
     return _verify_result(ctx, rc, "spg_poly_eval_verify_plain_batched_points")
 
 
@@ -1515,9 +1357,8 @@ def poly_eval_prove_batched_instances(ctx, gens, polys, num_vars_list, r_list, Z
     arr = _buf_array(polys)
 
     def call(out, c, ln):
-        return lib().spg_poly_eval_prove_batched_instances(ctx.handle, gens.handle, arr, offs, nvs, ctypes.c_size_t(n),
-                                                           _p(rl), lens, _p(zr), transcript.handle, tape.handle, out, c,
-                                                           ln)
+        return lib().spg_poly_eval_prove_batched_instances(ctx.handle, gens.handle, arr, offs, nvs, n, _p(rl), lens,
+                                                           _p(zr), transcript.handle, tape.handle, out, c, ln)
 
     return _prove_call(ctx, "spg_poly_eval_prove_batched_instances", call, cap)
 
@@ -1534,8 +1375,7 @@ def poly_eval_verify_plain_batched_instances(ctx, gens, r_list, Zr_list, comms, 
     blob = np.ascontiguousarray(np.concatenate(cms)) if n else np.zeros((1, 32), np.uint8)
     pf = _bytes_arr(proof)
     rc = lib().spg_poly_eval_verify_plain_batched_instances(ctx.handle, gens.handle, _p(rl), lens, _p(zr), _p(blob), cl,
-                                                            nvs, ctypes.c_size_t(n), transcript.handle, _p(pf),
-                                                            ctypes.c_size_t(len(proof)))
+                                                            nvs, n, transcript.handle, _p(pf), len(proof))
     return _verify_result(ctx, rc, "spg_poly_eval_verify_plain_batched_instances")
 
 
@@ -1572,9 +1412,8 @@ def pe_prove_disjoint(ctx, gens, polys, num_proofs_list, num_inputs_list, rq, ry
     arr = _buf_array(polys)
 
     def call(out, c, ln):
-        return lib().spg_pe_prove_disjoint(ctx.handle, gens.handle, arr, offs, nps, nis, ctypes.c_size_t(n), _p(q),
-                                           ctypes.c_size_t(len(rq)), _p(y), ctypes.c_size_t(len(ry)), _p(zr),
-                                           transcript.handle, tape.handle, out, c, ln)
+        return lib().spg_pe_prove_disjoint(ctx.handle, gens.handle, arr, offs, nps, nis, n, _p(q), len(rq), _p(y),
+                                           len(ry), _p(zr), transcript.handle, tape.handle, out, c, ln)
 
     return _prove_call(ctx, "spg_pe_prove_disjoint", call, cap)
 
@@ -1586,10 +1425,9 @@ def pe_verify_disjoint(ctx, gens, num_proofs_list, num_inputs_list, rq, ry, C_Zr
     q, y = _scalars_or_empty(rq), _scalars_or_empty(ry)
     czb, blob, cl = _cat_comms(C_Zr_list, comms)
     pf = _bytes_arr(proof)
-    rc = lib().spg_pe_verify_disjoint(ctx.handle, gens.handle, _sizes(num_proofs_list), _sizes(num_inputs_list),
-                                      ctypes.c_size_t(n), _p(q), ctypes.c_size_t(len(rq)), _p(y),
-                                      ctypes.c_size_t(len(ry)), _p(czb), _p(blob), cl, transcript.handle, _p(pf),
-                                      ctypes.c_size_t(len(proof)))
+    rc = lib().spg_pe_verify_disjoint(ctx.handle, gens.handle, _sizes(num_proofs_list), _sizes(num_inputs_list), n,
+                                      _p(q), len(rq), _p(y), len(ry), _p(czb), _p(blob), cl, transcript.handle, _p(pf),
+                                      len(proof))
     return _verify_result(ctx, rc, "spg_pe_verify_disjoint")
 
 
@@ -1600,8 +1438,7 @@ def pe_uni_evals(ctx, polys, num_vars_list, r, offsets=None):
     offs = _sizes(offsets if offsets is not None else [0] * n)
     out = np.zeros((max(n, 1), 4), dtype=np.uint64)
     rr = _scalars(r)
-    ctx.check(lib().spg_pe_uni_evals(ctx.handle, _buf_array(polys), offs, _sizes(num_vars_list), ctypes.c_size_t(n),
-                                     _p(rr), _p(out)), "spg_pe_uni_evals")
+    ctx.call("spg_pe_uni_evals", _buf_array(polys), offs, _sizes(num_vars_list), n, _p(rr), _p(out))
     return out[:n]
 
 
@@ -1617,8 +1454,8 @@ def pe_prove_uni(ctx, gens, polys, num_vars_list, r, Zr_list, transcript, tape, 
     czr = np.zeros(32, dtype=np.uint8)
 
     def call(out, c, ln):
-        return lib().spg_pe_prove_uni(ctx.handle, gens.handle, arr, offs, nvs, ctypes.c_size_t(n), _p(rr), _p(zr),
-                                      transcript.handle, tape.handle, out, c, ln, _p(czr))
+        return lib().spg_pe_prove_uni(ctx.handle, gens.handle, arr, offs, nvs, n, _p(rr), _p(zr), transcript.handle,
+                                      tape.handle, out, c, ln, _p(czr))
 
     proof = _prove_call(ctx, "spg_pe_prove_uni", call, cap)
     return proof, czr.tobytes()
@@ -1631,6 +1468,6 @@ def pe_verify_uni(ctx, gens, r, C_Zr_list, comms, poly_sizes, transcript, proof)
     rr = _scalars(r)
     czb, blob, cl = _cat_comms(C_Zr_list, comms)
     pf = _bytes_arr(proof)
-    rc = lib().spg_pe_verify_uni(ctx.handle, gens.handle, _p(rr), _p(czb), _p(blob), cl, _sizes(poly_sizes),
-                                 ctypes.c_size_t(n), transcript.handle, _p(pf), ctypes.c_size_t(len(proof)))
+    rc = lib().spg_pe_verify_uni(ctx.handle, gens.handle, _p(rr), _p(czb), _p(blob), cl, _sizes(poly_sizes), n,
+                                 transcript.handle, _p(pf), len(proof))
     return _verify_result(ctx, rc, "spg_pe_verify_uni")
