@@ -29,6 +29,7 @@
 #include "hpool.hpp"
 #include "knobs.hpp"
 #include "lds.hpp"
+#include "msm_plan.hpp"
 #include "quad.hpp"
 
 namespace spg {
@@ -373,11 +374,8 @@ int msm_comb(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const Fq* d_sca
   const size_t per = n + (d_blinds ? 1 : 0);
   const size_t want = (size_t)knob::comb_wgs();
   // window groups per scalar: few rows get up to 4 lanes per scalar (>= 2^17 lanes when there are that few)
-  const size_t gmax = (size_t)knob::comb_gmax(), gmin = (size_t)knob::comb_gmin();
-  size_t G = gmin == 2 || gmin == 4 ? gmin : 1;
-  while (G < gmax && G < 4 && B * per * G < ((size_t)1 << 17)) G *= 2;
-  const size_t spw = 256 / G;
-  const size_t S = std::max<size_t>(1, std::min((want + B - 1) / B, (per + spw - 1) / spw));
+  size_t G, S;
+  comb_rows_shape(B, per, want, (size_t)knob::comb_gmax(), (size_t)knob::comb_gmin(), &G, &S);
   Ext* part = ext;
   if (S > 1) {
     // the commit queue's second stream runs row commits while the main stream's block-witness commit is in flight:

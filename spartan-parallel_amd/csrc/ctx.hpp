@@ -11,6 +11,7 @@
 
 #include "../../include/spg.h"
 #include "curve.hpp"
+#include "msm_plan.hpp"
 
 namespace spg {
 struct Uploader;  // api.hip
@@ -233,7 +234,7 @@ static const int kBulletNB = 64;  // buckets per MSM of bullet_round_device (c =
 // the comb form of a Bullet round (bullet.hpp k_bullet_comb): partial points of the L and R MSMs, 2 x *per_msm Ext
 // into d_parts (at most kBulletPartsMax per MSM), completion posted to the mailbox with *seq_out; the host adds each
 // MSM's parts. Returns 1 when g has no comb table for these generators (the caller takes the bucket form).
-static const int kBulletPartsMax = 512;
+// (kBulletPartsMax: msm_plan.hpp)
 // B MSMs of n Montgomery scalars over generators d_idx[b n + i] (< gmax) from g's comb table, as B x *per_msm partial
 // points into d_parts (stream-ordered, no completion post); 1 when the comb does not apply
 int comb_msm_parts(spg_ctx* ctx, const spg_gens* g, const Fq* d_scalars, const uint32_t* d_idx, size_t gmax, int n,

@@ -17,6 +17,7 @@
 #include "hpool.hpp"
 #include "keccak.hpp"
 #include "knobs.hpp"
+#include "msm_plan.hpp"
 #include "pe_plan.hpp"
 #include "snark_shape.hpp"
 #include "vmsm.hpp"
@@ -500,6 +501,41 @@ long spgh_pe_plan_uni(int per_term, size_t n, const size_t* nv_list, size_t* ter
   tot[0] = p.part_len, tot[1] = p.out_len, tot[2] = p.xblocks, tot[3] = pe_proof_bytes(p.R_size), tot[4] = p.R_size;
   return (long)p.terms.size();
 }
+
+// ---- the launch shapes of msm_plan.hpp (tests/test_msm_plan_host.py; the GPU form tests choose their sizes by them).
+// Knob values are arguments: the tests pass the table's defaults or the value a form sets.
+int spgh_pick_window(size_t n_per_msm) { return pick_window(n_per_msm); }
+int spgh_pick_small_window(size_t per, int forced) { return pick_small_window(per, forced); }
+int spgh_msm_comb_rule(int has_idx, size_t B, size_t n, size_t tot) { return msm_comb_rule(has_idx != 0, B, n, tot); }
+// out[12] = (c, NB, W, rows, m, S, log2m, seg_quad, quad, regroup, final_S, final_sl)
+void spgh_msm_batch_route(size_t B, size_t per, int seg_m, int rows_cmax, int quad, long seg_quad_max, int final_sl,
+                          int* out) {
+  const MsmRoute r = msm_batch_route(B, per, seg_m, rows_cmax, quad != 0, seg_quad_max, final_sl);
+  const int row[12] = {r.c, r.NB, r.W, r.rows, r.m, r.S, r.log2m, r.seg_quad, r.quad, r.regroup, r.final_S, r.final_sl};
+  memcpy(out, row, sizeof(row));
+}
+// out[2] = (G, S)
+void spgh_comb_rows_shape(size_t B, size_t per, size_t want, size_t gmax, size_t gmin, size_t* out) {
+  comb_rows_shape(B, per, want, gmax, gmin, out, out + 1);
+}
+// out[2] = (G, spb)
+void spgh_big_digit_blocks(int per, int spt, int* out) { big_digit_blocks(per, spt, out, out + 1); }
+// out[3] = (G, BS, R) of bullet_comb_shape alone
+void spgh_bullet_comb_shape(int P, int eg, int ebs, int er, int notree, int* out) {
+  bullet_comb_shape(P, eg, ebs, er, notree, out, out + 1, out + 2);
+}
+// out[4] = (G, BS, R, wgs) of the launch over c-bit windows; returns 1 when it runs, 0 when the caller falls back
+int spgh_bullet_comb_launch(int shape_P, int P, int c, int eg, int ebs, int er, int notree, int* out) {
+  return bullet_comb_launch(shape_P, P, c, eg, ebs, er, notree, out, out + 1, out + 2, out + 3);
+}
+int spgh_bullet_parts_max() { return kBulletPartsMax; }
+// out[2] = (K, BS)
+void spgh_layer_grid(size_t W, size_t one_wg, size_t ept, unsigned* out) {
+  int bs = 0;
+  layer_grid(W, one_wg, ept, out, &bs);
+  out[1] = (unsigned)bs;
+}
+int spgh_grid_for(uint32_t total, int cap) { return grid_for(total, cap); }
 
 // The environment table (knobs.hpp) as text, one row per line: name, kind, default, lo, hi (the clamp; "-": none),
 // live (0 / 1), description, tab separated. Writes at most cap bytes and returns the length of the whole text.

@@ -29,6 +29,7 @@
 #include "keccak.hpp"
 #include "knobs.hpp"
 #include "lds.hpp"
+#include "msm_plan.hpp"
 #include "bullet.hpp"
 #include "quad.hpp"
 
@@ -622,31 +623,10 @@ int bullet_round_device(spg_ctx* ctx, const spg_gens* g, const Fq* aa_in, const 
   return 0;
 }
 
-// the comb form's launch shape by MSM size P = n / 2: G quads per scalar (window groups of ceil(22 / G)), BS threads,
-// R points per workgroup (SPG_BCOMB_G / SPG_BCOMB_BS / SPG_BCOMB_R override, for A/B runs)
-static void bullet_comb_shape(int P, int* G, int* BS, int* R) {
-  const int eg = knob::bcomb_g(), ebs = knob::bcomb_bs(), er = knob::bcomb_r();
-  // same-box A/Bs on the 2^20 SNARK (Bullet device ms per prove; profiles/r04_ab_bullet_shapes.txt): G 4 -> 8 at
-  // P = 512: 1.92 -> 1.88; G 8 -> 11 (two dependent quad additions per quad): 1.87 -> 1.81; R 4 -> 8 (one tree level
-  // fewer, twice the host-summed parts): 1.89 -> 1.74, R = 16: 1.85
-  *G = P >= 2048 ? 4 : 11;
-  *BS = P <= 64 ? 64 : (P <= 128 ? 128 : 256);
-  // R: round 4 chose 8 on device time alone; on the prover's wall clock the host's part sums weigh more (91 ns per
-  // addition on the box, K <= 4 chunks per MSM: scripts/micro/parts_finals_cpu.cpp, profiles/r05_parts_finals.txt),
-  // and R = 2 was fastest (2-rep A/B, SNARK median ms: R 8: 16.66 / 17.13, 2: 16.08 / 16.13, 1: 17.56 / 16.71); with the
-  // IFMA part sums (hvec.hpp) R = 4 was (ABBA A/B: 15.23 / 15.93 / 16.39 / 15.67 -> 15.13 / 15.04 / 15.84 / 15.02), and
-  // later in the round R = 8 (ABBA, 3 blocks: mean 16.03 -> 15.34 ms, device busy 8.65 -> 8.53 ms; R = 16 15.29 against
-  // 15.40; profiles/r05_ab_bcomb_r8.txt)
-  *R = P >= 2048 ? 1 : 8;  // the SPARK PolyEvalProofs at 2^24 nonzeros (P = 4096): 256 workgroups per MSM
-  if (eg == 4 || eg == 8 || eg == 11) *G = eg;
-  if (ebs == 64 || ebs == 128 || ebs == 256) *BS = ebs;
-  if (er >= 1 && er <= *BS / 4 && (er & (er - 1)) == 0) *R = er;
-  // the last rounds (P <= SPG_BCOMB_NOTREE): every quad its own part, no LDS tree (one level is a full quad addition,
-  // ~2.1 us on the round's latency path, scripts/micro/bullet_comb_phases) for at most 2 x 16 parts per MSM
-  if (P <= knob::bcomb_notree()) *R = *BS / 4;
-  // at most kBulletPartsMax parts per MSM (the host staging): fewer points per workgroup for the largest proofs
-  const int wgs = (P * *G + *BS / 4 - 1) / (*BS / 4);
-  while (*R > 1 && wgs * *R > kBulletPartsMax) *R /= 2;
+// the comb form's launch shape (msm_plan.hpp) under SPG_BCOMB_G / SPG_BCOMB_BS / SPG_BCOMB_R / SPG_BCOMB_NOTREE
+static bool bullet_comb_launch_env(int shape_P, int P, int c, int* G, int* BS, int* R, int* wgs) {
+  return bullet_comb_launch(shape_P, P, c, knob::bcomb_g(), knob::bcomb_bs(), knob::bcomb_r(), knob::bcomb_notree(), G,
+                            BS, R, wgs);
 }
 
 int bullet_round_comb(spg_ctx* ctx, const spg_gens* g, const Fq* aa_in, const Fq* cw_in, Fq* aa_out, Fq* cw_out,
@@ -658,11 +638,8 @@ int bullet_round_comb(spg_ctx* ctx, const spg_gens* g, const Fq* aa_in, const Fq
   const int rc = comb_get(ctx, g, gmax, &cb);
   if (rc) return rc == 1 ? 1 : rc;
   if (cb.c != 12 && cb.c != 13) return 1;  // the kernels take 12- or 13-bit windows
-  int G, BS, R;
-  bullet_comb_shape(n / 2, &G, &BS, &R);
-  if (cb.c == 13 && G != 4) G = 10;  // 20 windows: groups of 2 (11 would leave one empty)
-  const int S = BS / 4, quads = (n / 2) * G, wgs = (quads + S - 1) / S;
-  if (wgs * R > kBulletPartsMax) return 1;
+  int G, BS, R, wgs;
+  if (!bullet_comb_launch_env(n / 2, n / 2, cb.c, &G, &BS, &R, &wgs)) return 1;
   BulletCombArgs a{aa_in, cw_in, aa_out, cw_out, gidx, u, uinv, k, n, nk, cb.p, (int)cb.slots + 1, R, d_parts,
                    ctx->d_counter, ctx->d_mbox, ++ctx->mbox_seq, cb.st};
   *seq_out = a.seq;
@@ -701,6 +678,7 @@ __global__ void k_bullet_delta_scalars(const Fq* __restrict__ cw, int n, Fq cu, 
 
 int bullet_delta_scalars(spg_ctx* ctx, const Fq* cw, int n, const Fq& d, const Fq& u, const Fq& uinv, Fq* out) {
   const Fq cu = fq_to_mont(fq_mul(d, u)), cinv = fq_to_mont(fq_mul(d, uinv));
+  KScope ks(ctx, "msm_delta_scalars", 96.0 * n, 0.0, (double)n);  // (the profile's trace of SPG_DELTA_DEV)
   hipLaunchKernelGGL(k_bullet_delta_scalars, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, cw, n, cu,
                      cinv, out);
   SPG_HIP(ctx, hipGetLastError());
@@ -714,11 +692,8 @@ int comb_msm_parts(spg_ctx* ctx, const spg_gens* g, const Fq* d_scalars, const u
   const int rc = comb_get(ctx, g, gmax, &cb);
   if (rc) return rc == 1 ? 1 : rc;
   if (cb.c != 12 && cb.c != 13) return 1;
-  int G, BS, R;
-  bullet_comb_shape(std::max(2, n), &G, &BS, &R);
-  if (cb.c == 13 && G != 4) G = 10;
-  const int S = BS / 4, wgs = (n * G + S - 1) / S;
-  if (wgs * R > kBulletPartsMax) return 1;
+  int G, BS, R, wgs;
+  if (!bullet_comb_launch_env(std::max(2, n), n, cb.c, &G, &BS, &R, &wgs)) return 1;
   *per_msm = wgs * R;
   KScope ks(ctx, "msm_comb_parts", 0.0, (double)B * n * (253 / cb.c + 1) * (1.0 - 1.0 / (double)(1 << cb.c)));
   const dim3 grid((unsigned)wgs, (unsigned)B);
@@ -793,12 +768,8 @@ __global__ void __launch_bounds__(1024) k_smsm_final_q(const Ext* __restrict__ b
 }
 
 static int pick_small_window(size_t per) {
-  const int forced = knob::smsm_c();  // (re-read on every call: scripts/perf_small_msm.py sweeps it in one process)
-  if (forced >= 4 && forced <= 9) return forced;
-  // measured on MI355X (scripts/perf_small_msm.py): n = 130 -> c = 7, n = 4098 -> c = 8; the compacted
-  // Bullet MSMs (n/2 + 2 = 514 scalars) finish on the host, where 64 buckets per MSM are cheaper than 128
-  // (scripts/ab_env.sh SPG_SMSM_C "7 0": 39.7 vs 39.9-40.9 ms per SNARK::prove)
-  return per <= 1024 ? 7 : 8;
+  // (re-read on every call: scripts/perf_small_msm.py sweeps it in one process)
+  return pick_small_window(per, knob::smsm_c());
 }
 
 template <int C>
@@ -935,20 +906,6 @@ int msm_small_compressed(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, con
 }
 
 // ------------------------------------------------------------------ host orchestration
-static int pick_window(size_t n_per_msm) {
-  int best = 4;
-  double best_cost = 1e300;
-  for (int c = 4; c <= 16; c++) {
-    int W = 253 / c + 1;
-    double cost = (double)n_per_msm * W * 7.0 + (double)(1 << c) * 9.0;
-    if (cost < best_cost) {
-      best_cost = cost;
-      best = c;
-    }
-  }
-  return best;
-}
-
 template <int C>
 static void launch_digits(const MsmArgs& a, bool count, hipStream_t s) {
   size_t per = a.n + (a.blinds ? 1 : 0);
@@ -1000,21 +957,22 @@ int msm_batch_device(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const F
   // (up to 2^14 generators: the SPARK derefs / comb_ops commits at 2^24 nonzeros), whose bucket path spends as much
   // time in its digit sort and bucket reduction as in its additions
   const size_t tot = B * (n + (d_blinds ? 1 : 0));
-  if (!d_idx && B >= 64 && (n <= 1024 ? tot >= ((size_t)1 << 14) : (n <= 16384 && tot >= ((size_t)1 << 22)))) {
+  if (msm_comb_rule(d_idx != nullptr, B, n, tot)) {
     Ext* ext = d_ext ? d_ext : (Ext*)ws_get(ctx, 17, B * sizeof(Ext) + 64);
     if (!ext) return set_err(ctx, SPG_E_NOMEM, "msm comb points");
     const int hi = !d_blinds ? -1 : (h_index < 0 ? (int)g->n : (int)h_index);
     const int rc = msm_comb(ctx, g, gen_offset, d_scalars, n, B, d_blinds, d_out, hi, ext);
     if (rc != kCombSkip) return rc;
   }
-  const int c = pick_window(n + (d_blinds ? 1 : 0));
-  const int NB = 1 << (c - 1);
-  const int W = 253 / c + 1;
-  const size_t nkeys = B * (size_t)NB;
   const size_t per = n + (d_blinds ? 1 : 0);
-  const size_t max_entries = B * per * (size_t)W;
   static_assert(knob::item_k_dflt == kItemK && knob::seg_m_dflt == kSegM, "knobs.hpp defaults");
-  const int item_k = knob::item_k(), seg_m = knob::seg_m();
+  const int item_k = knob::item_k();
+  // window, digit sort, segment and final forms (msm_plan.hpp)
+  const MsmRoute rt = msm_batch_route(B, per, knob::seg_m(), knob::rows_cmax(), use_quad(), knob::seg_quad_max(),
+                                      knob::final_sl());
+  const int c = rt.c, NB = rt.NB, W = rt.W;
+  const size_t nkeys = B * (size_t)NB;
+  const size_t max_entries = B * per * (size_t)W;
   const size_t max_items = max_entries / item_k + nkeys + 1;
   SPG_CHECK(ctx, max_entries < 0x7fffffffULL, "msm batch too large");
   SPG_CHECK(ctx, (size_t)kTableRows * (g->n + 1) < 0x7fffffffULL, "generator table too large");
@@ -1027,10 +985,7 @@ int msm_batch_device(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const F
   uint32_t* entries = (uint32_t*)ws_get(ctx, 6, max_entries * 4 + 4);
   uint32_t* item_key = (uint32_t*)ws_get(ctx, 7, max_items * 4);
   Ext* partial = (Ext*)ws_get(ctx, 8, max_items * sizeof(Ext));
-  const int m = NB < seg_m ? NB : seg_m;  // buckets per segment
-  const int S = NB / m;
-  int log2m = 0;
-  while ((1 << log2m) < m) log2m++;
+  const int m = rt.m, S = rt.S, log2m = rt.log2m;  // buckets per segment, segments per MSM
   Ext* segT = (Ext*)ws_get(ctx, 9, B * (size_t)S * sizeof(Ext));
   Ext* segS = (Ext*)ws_get(ctx, 10, B * (size_t)S * sizeof(Ext));
   if (!hist || !off || !cursor || !items || !item_off || !entries || !item_key || !partial || !segT || !segS)
@@ -1038,7 +993,7 @@ int msm_batch_device(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const F
 
   // many MSMs: one workgroup per MSM sorts its digits in LDS (k_digits_rows; up to 2^15 bucket counters,
   // 128 KiB of the 160 KiB LDS, at c = 16)
-  const bool rows = B >= 64 && c <= knob::rows_cmax();
+  const bool rows = rt.rows;
   if (rows) {
     SPG_HIP(ctx, hipMemsetAsync(hist + nkeys, 0, 4, s));
   } else {
@@ -1094,7 +1049,7 @@ int msm_batch_device(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const F
   }
   {
     KScope ks(ctx, "msm_segments");
-    if (use_quad() && B * (size_t)S <= (size_t)knob::seg_quad_max())
+    if (rt.seg_quad)
       hipLaunchKernelGGL(k_segments_q, dim3((unsigned)((4 * B * S + 255) / 256)), dim3(256), 0, s, item_off, partial,
                          segT, segS, (int)B, NB, m);
     else
@@ -1111,9 +1066,9 @@ int msm_batch_device(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const F
       if (!ext && d_out) ext = (Ext*)ws_get(ctx, 17, B * sizeof(Ext) + 64);
       if (!ext) return set_err(ctx, SPG_E_NOMEM, "msm final points");
       const Ext *fT = segT, *fS = segS;
-      int fSn = S, flog2m = log2m;
-      if (B <= 16 && S > 1024) {  // few MSMs with many segments: regroup 8 segments per group first
-        const int lg = 3, G = S >> lg;
+      const int fSn = rt.final_S, flog2m = rt.final_log2m;  // what the final scan sees
+      if (rt.regroup) {  // few MSMs with many segments: regroup 8 segments per group first
+        const int lg = 3, G = rt.final_S;
         Ext* rT = (Ext*)ws_get(ctx, 18, 2 * B * (size_t)G * sizeof(Ext) + 64);
         if (!rT) return set_err(ctx, SPG_E_NOMEM, "msm regroup");
         Ext* rS = rT + B * (size_t)G;
@@ -1121,13 +1076,11 @@ int msm_batch_device(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const F
                            segS, (int)B, S, lg, log2m, rT, rS);
         fT = rT;
         fS = rS;
-        fSn = G;
-        flog2m = log2m + lg;
       }
       // many MSMs fill the chip with blocks: fewer slots per MSM do less redundant scan work (the Hillis-Steele
       // scan costs SL log SL additions), few MSMs need the shortest dependent chain
       // (B = 1024 rows: 414 -> 155 us, MI355X)
-      const int sl = knob::final_sl() ? knob::final_sl() : (B >= 256 ? 32 : 128);
+      const int sl = rt.final_sl;
       if (sl == 32)
         hipLaunchKernelGGL(k_final_q<32>, dim3((unsigned)B), dim3(128), 0, s, fT, fS, nullptr, fSn, flog2m, ext);
       else if (sl == 64)
@@ -1434,7 +1387,7 @@ int spg::msm_rows_host_enc(spg_ctx* ctx, const spg_gens* g, const Fq* d_scalars,
   const bool halve = knob::halved_enc();
   hipStream_t s = ctx->stream;
   const size_t tot = B * (n + (d_blinds ? 1 : 0));
-  const bool comb = B >= 64 && (n <= 1024 ? tot >= ((size_t)1 << 14) : (n <= 16384 && tot >= ((size_t)1 << 22)));
+  const bool comb = msm_comb_rule(false, B, n, tot);
   if (halve && comb && B >= 384) {  // (fewer rows: spark.hip kHalvedMin)
     Ext* ext = (Ext*)ws_get(ctx, 17, B * sizeof(Ext) + 64);
     if (!ext) return set_err(ctx, SPG_E_NOMEM, "msm comb points");

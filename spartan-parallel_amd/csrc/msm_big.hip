@@ -28,6 +28,7 @@
 #include "ctx.hpp"
 #include "hcurve.hpp"
 #include "knobs.hpp"
+#include "msm_plan.hpp"
 #include "quad.hpp"
 
 namespace spg {
@@ -35,7 +36,7 @@ namespace spg {
 namespace {
 
 // workspace slots 100..108 (msm.hip 0..18, proto.hip 20..24, r1cs.hip 30.., spark.hip 60.., snark / verify 91..96)
-constexpr int kBigBS = 256;      // threads per workgroup (64 quads)
+// (kBigBS, threads per workgroup: msm_plan.hpp)
 constexpr int kBigQuads = kBigBS / 4;
 constexpr int kBigGroup = 64;    // buckets per group reduction (big_group)
 
@@ -415,8 +416,7 @@ int msm_single_big(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const Fq*
   a.n1 = (int)(g->n + 1);
   // digit blocks: SPG_BIG_SPT scalars per thread (default 1), at most 512 blocks (the histogram matrix is NB x G)
   const int spt = knob::big_spt();
-  a.G = std::max(1, std::min(512, (per + spt * kBigBS - 1) / (spt * kBigBS)));
-  a.spb = (per + a.G - 1) / a.G;
+  big_digit_blocks(per, spt, &a.G, &a.spb);
   int ng = 0, rc = 0;
   Ext* res = (Ext*)ctx->d_res;  // the coherent result page: 2 NB / 64 points (<= 256 at c = 14)
   static_assert(kResScalars * sizeof(Fq) >= 2 * (1 << 13) / kBigGroup * sizeof(Ext), "result page too small");

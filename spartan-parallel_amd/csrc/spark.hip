@@ -28,6 +28,7 @@
 #include "proto.hpp"
 #include "layer.hpp"
 #include "lds.hpp"
+#include "msm_plan.hpp"
 #include "sumcheck.hpp"
 
 namespace spg {
@@ -608,17 +609,7 @@ int dotp_evaluate(spg_ctx* ctx, const std::vector<Triple>& dotp, size_t n, Fq* o
 // workgroups and block size of a fused layer round over W = nt * len elements: one workgroup up to kOneWgMax
 // elements (no ticket), else about kEltPerThread elements per thread over 256-thread workgroups
 static void layer_grid(size_t W, unsigned* K, int* BS) {
-  const size_t one_wg = (size_t)knob::layer_onewg(), ept = (size_t)knob::layer_ept();
-  if (W <= 64) {
-    *K = 1;
-    *BS = 64;
-  } else if (W <= one_wg) {
-    *K = 1;
-    *BS = 256;
-  } else {
-    *BS = 256;
-    *K = (unsigned)std::min<size_t>((W + 256 * ept - 1) / (256 * ept), 2048);
-  }
+  layer_grid(W, (size_t)knob::layer_onewg(), (size_t)knob::layer_ept(), K, BS);  // msm_plan.hpp
 }
 
 // ------------------------------------------------------------------------------------ the layer prover

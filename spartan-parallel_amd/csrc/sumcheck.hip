@@ -15,6 +15,7 @@
 #include "cube.hpp"
 #include "knobs.hpp"
 #include "lds.hpp"
+#include "msm_plan.hpp"
 #include "qsum.hpp"
 #include "sumcheck.hpp"
 
@@ -1116,10 +1117,7 @@ static size_t sc_quad_max() { return (size_t)knob::sc_quad_max(); }
 // the partials buffer)
 static int grid_for(uint32_t total) {
   static_assert(kScGridMax == 4096, "the SPG_SC_GRID row of knobs.hpp clamps to kScGridMax");
-  const int cap = knob::sc_grid();
-  int nb = (int)((total + 255) / 256);
-  if (nb > cap) nb = cap;
-  return nb < 1 ? 1 : nb;
+  return grid_for(total, knob::sc_grid());  // msm_plan.hpp
 }
 
 // the round's three scalars arrive in the host mailbox (posted by the last block of the eval kernel);

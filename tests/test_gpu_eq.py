@@ -20,17 +20,68 @@ def eq_ref(oracle, r):
     return t
 
 
+ELLS = [0, 1, 2, 3, 4, 7, 8, 9, 11, 12, 13, 16, 17, 20]
+
+
+def challenges(oracle, ell):
+    rng = np.random.default_rng(100 + ell)
+    return oracle.fq_from_bytes_wide(rng.integers(0, 256, 64 * ell, dtype=np.uint8).tobytes()) if ell else \
+        np.zeros((0, 4), dtype=np.uint64)
+
+
 @pytest.mark.gpu
-@pytest.mark.parametrize("ell", [0, 1, 2, 3, 4, 7, 8, 9, 11, 12, 13, 16, 17, 20])
+@pytest.mark.parametrize("ell", ELLS)
 def test_eq_evals_match_oracle(ctx, oracle, ell):
     import spg
 
-    rng = np.random.default_rng(100 + ell)
-    r = oracle.fq_from_bytes_wide(rng.integers(0, 256, 64 * ell, dtype=np.uint8).tobytes()) if ell else \
-        np.zeros((0, 4), dtype=np.uint64)
+    r = challenges(oracle, ell)
     got = spg.Buf.eq_evals(ctx, r).download()
     assert got.shape == (1 << ell, 4)
     assert np.array_equal(got, eq_ref(oracle, r))
+
+
+def eq_child_main():
+    """prints `ell sha256(table)` per size, then the eq_table launch count of the profile (a fresh process that reads
+    SPG_EQ_LDS)"""
+    import hashlib
+
+    import pyoracle
+    import spg
+
+    ctx = spg.Context(0)
+    ctx.prof_enable(True)
+    ctx.prof_read(reset=True)
+    for ell in ELLS:
+        got = spg.Buf.eq_evals(ctx, challenges(pyoracle, ell)).download()
+        print(ell, got.shape[0], hashlib.sha256(np.ascontiguousarray(got).tobytes()).hexdigest())
+    print("eq_table", ctx.prof_read().get("eq_table", (0,))[0])
+    print("ok")
+
+
+@pytest.mark.gpu
+def test_eq_evals_one_lane_per_entry(oracle):
+    """SPG_EQ_LDS=0: every size again through k_eq_table<false>, one lane per entry up to ell = 12 and the factored
+    form (two of them, then k_eq_combine) above, where the LDS kernel factors only past 16. spg_eq_evals reads the
+    switch unconditionally on its way to the launch, so every table here is built by the switched kernels; the
+    profile's eq_table count (one scope per table in either form) only confirms that each table was a device launch."""
+    import hashlib
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = ("import sys; sys.path[:0] = [%r, %r, %r]\nimport test_gpu_eq\ntest_gpu_eq.eq_child_main()\n"
+            % (os.path.join(root, "spartan-parallel_amd"), os.path.join(root, "oracle"), os.path.join(root, "tests")))
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, SPG_EQ_LDS="0"), capture_output=True,
+                         text=True, timeout=240)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [line.split() for line in out.stdout.split("\n")[:-1]]
+    assert lines[-1] == ["ok"] and lines[-2] == ["eq_table", str(len(ELLS))], lines[-2:]
+    assert [int(w[0]) for w in lines[:-2]] == ELLS
+    for ell, n, h in lines[:-2]:
+        want = eq_ref(oracle, challenges(oracle, int(ell)))
+        assert int(n) == 1 << int(ell)
+        assert h == hashlib.sha256(np.ascontiguousarray(want).tobytes()).hexdigest(), "ell = %s" % ell
 
 
 @pytest.mark.gpu

@@ -109,7 +109,9 @@ def test_msm_blind_and_offset(ctx, oracle, gens64):
     assert gens64.msm(s, gen_offset=10) == oracle.msm(pts[10:60], s)
 
 
-# (128, 512) and (64, 1024): >= 64 rows wider than the latency path take the LDS row sort (k_digits_rows)
+# (64, 128): >= 64 rows below the comb's size rule (2^14 scalars in all) take the bucket pipeline's LDS row sort
+# (k_digits_rows, c = 9); (128, 512) and (64, 1024) meet the rule and come from the comb table since it arrived
+# (tests/test_gpu_msm_forms.py runs them through the buckets with the comb off)
 @pytest.mark.parametrize("L,R", [(1, 1), (4, 2), (8, 32), (64, 128), (16, 1024), (128, 512), (64, 1024)])
 def test_commit_rows(ctx, oracle, gens64, L, R):
     rng = np.random.default_rng(L * 1000 + R)
@@ -186,8 +188,9 @@ def test_commit_rows_comb(ctx, oracle, gens64, L, R):
 
 
 def test_commit_rows_wide(ctx, oracle):
-    """Hyrax rows of 2^14 scalars (window c = 14, 2^13 bucket counters) in batches of >= 64 rows take the LDS row
-    sort too (the SPARK derefs / comb_ops commitments at 2^24 nonzeros have such rows)"""
+    """Hyrax rows of 2^14 scalars (window c = 15: pick_window never picks 14; 2^14 bucket counters) in batches of
+    >= 64 rows, fewer than the comb's 2^22 scalars, take the LDS row sort too (the SPARK derefs / comb_ops commitments
+    at 2^24 nonzeros have such rows)"""
     import spg
 
     L, R = 64, 1 << 14

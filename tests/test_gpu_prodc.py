@@ -287,6 +287,57 @@ def test_prodc_prove_batched_launch_forms(ctx, oracle):
         assert res.stdout.strip().splitlines()[-1] == want, env
 
 
+# the lane form's grid (spark.hip layer_grid; only rounds that are neither wide nor in the quad form take it, and only
+# single rounds): every round ticketed over several workgroups, one workgroup looping over everything, and 1 or 8
+# elements per thread of the wider grids
+LANE = {"SPG_LAYER_QUAD": "0", "SPG_WIDE_MIN": "1000000000000", "SPG_LAYER_PAIR": "0", "SPG_LAYER_TRIPLE": "0"}
+GRID_FORMS = [dict(LANE, SPG_LAYER_ONEWG="0"), dict(LANE, SPG_LAYER_ONEWG=str(1 << 20)),
+              dict(LANE, SPG_LAYER_ONEWG="0", SPG_LAYER_EPT="1"), dict(LANE, SPG_LAYER_ONEWG="0", SPG_LAYER_EPT="8")]
+
+
+def test_prodc_layer_grid_forms(oracle):
+    """the (4, 2), M = 4096 proof with every round a single lane-form round on layer_grid's shapes, against the
+    oracle's bytes. The top layer's first round runs over 6 x 1024 elements: 12 workgroups by default, 24 and 3 with
+    1 and 8 elements per thread, one with SPG_LAYER_ONEWG past that size; with SPG_LAYER_ONEWG=0 every round of more
+    than 64 elements takes the ticketed form. The profile's spark_layer_round count shows that every round of every
+    layer was such a launch (no pair, triple or wide launch took one)."""
+    import hashlib
+
+    import msm_form_cases as fc
+
+    M, nc, nd = 4096, 4, 2
+    leaves, dotp = batched_inputs(oracle, M, nc, nd, 7 * M + 10 * nc + nd)
+    e_proof, e_rand, e_check, ok = prodc_ref.prove_batched(b"prodc_batched", leaves, dotp)
+    assert ok
+    want = hashlib.sha256(e_proof + e_rand.tobytes() + e_check).hexdigest()
+    W = (nc + nd) * (M // 4)
+    assert [fc.layer_grid(W, env)[0] for env in GRID_FORMS] == [12, 1, 24, 3] and fc.layer_grid(W)[0] == 12
+    assert fc.layer_grid(65, GRID_FORMS[0]) == (1, 256) and fc.layer_grid(1025, GRID_FORMS[0])[0] == 3
+    rounds = sum(range(1, M.bit_length() - 1))  # layers of 2, 4, .., M / 2 entries per half: 1 + 2 + .. + 11 rounds
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = (
+        "import sys, hashlib; sys.path[:0] = [%r, %r, %r]\n"
+        "import pyoracle, spg\n"
+        "from test_gpu_prodc import batched_inputs, gpu_prove_batched\n"
+        "leaves, dotp = batched_inputs(pyoracle, %d, %d, %d, %d)\n"
+        "ctx = spg.Context(0)\n"
+        "ctx.prof_enable(True)\n"
+        "ctx.prof_read(reset=True)\n"
+        "proof, rand, check, _ = gpu_prove_batched(ctx, leaves, dotp)\n"
+        "prof = ctx.prof_read()\n"
+        "print(*(prof.get(k, (0,))[0] for k in ('spark_layer_round', 'spark_layer_pair', 'spark_layer_triple')))\n"
+        "print(hashlib.sha256(proof + rand.tobytes() + check).hexdigest())\n"
+    ) % (os.path.join(root, "tests"), os.path.join(root, "oracle"), os.path.join(root, "spartan-parallel_amd"), M, nc, nd,
+         7 * M + 10 * nc + nd)
+    for env in GRID_FORMS:
+        res = subprocess.run([sys.executable, "-c", code], env={**os.environ, **env}, capture_output=True, text=True,
+                             timeout=240)
+        assert res.returncode == 0, (env, res.stderr[-2000:])
+        lines = res.stdout.strip().splitlines()
+        assert lines[-1] == want, env
+        assert lines[-2].split() == [str(rounds), "0", "0"], (env, lines[-2])
+
+
 # ------------------------------------------------------------------------------------------------ argument errors
 def test_argument_errors(ctx, oracle):
     import spg

@@ -126,6 +126,29 @@ ROUND_FORMS = {
     "pairs_up_to_32768_elements": {"SPG_P1_PAIR_MAX": "32768", "SPG_P2_PAIR_MAX": "32768"},
     "phase1_pairs_small_only": {"SPG_P1_PAIR_MAX": "16"},
     "witness_upload_workers": {"SPG_H2D": "1"},
+    # host-side forms (no kernel family switches, so the profile cannot show them: these entries compare bytes only.
+    # Whether this small case reaches every switched site -- bucket finals of 64 chunks, host sums past SPG_VEC_MIN --
+    # has not been shown)
+    "witness_upload_three_workers_1k_chunks": {"SPG_H2D": "1", "SPG_H2D_THREADS": "3", "SPG_H2D_CHUNK_KB": "1"},
+    "bucket_finals_one_chunk": {"SPG_FINALS_K": "1"},
+    "bucket_finals_64_chunks": {"SPG_FINALS_K": "64"},
+    "no_pool_workers": {"SPG_POOL_THREADS": "0"},
+    "one_pool_worker": {"SPG_POOL_THREADS": "1"},
+    "pool_slices_of_one_unit": {"SPG_SLICE_MIN": "1"},
+    "host_sums_never_vectorised": {"SPG_VEC_MIN": "0"},
+    "host_sums_vectorised_from_one": {"SPG_VEC_MIN": "1"},
+    "host_sums_scalar": {"SPG_HOST_IFMA": "0"},
+    "host_bursts_no_prefetch": {"SPG_HOST_PREFETCH": "0"},
+}
+# forms that switch a kernel family or a launch shape: (environment, scopes whose launch counts must rise above the
+# default run's, scope prefixes of which something must run). test_round_forms_that_show_they_ran reads the profile.
+SHOWN_FORMS = {
+    # the <true> blob kernels; without the LDS kernel every table is a launch of its own, so the count rises
+    "eq_tables_one_lane_per_entry": ({"SPG_EQ_LDS": "0"}, ["eq_table"], ["eq_table"]),
+    "eval_grid_of_one": ({"SPG_SC_GRID": "1"}, [], ["sc_phase1"]),
+    "eval_grid_of_two": ({"SPG_SC_GRID": "2"}, [], ["sc_phase1"]),
+    # row-commit batches of at most 384 points are encoded by k_compress_ext instead of on the host pool
+    "row_encodings_never_on_host": ({"SPG_HOST_ENC_MAX": "0"}, ["msm_compress"], ["msm_compress"]),
 }
 
 
@@ -170,6 +193,66 @@ def test_round_forms(form):
     assert out.returncode == 0, out.stderr[-2000:]
     golden = json.load(open(os.path.join(G, "snark_proofs.json")))[case]
     assert out.stdout.split()[-1] == golden["proof_sha256"]
+
+
+def profiled_prove(env):
+    """(proof sha256, {scope: launches}) of mem_both_b3_x64_q2 proved in a fresh process under env"""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    code = (
+        "import sys, hashlib; sys.path[:0] = [%r, %r]\n"
+        "import spg, workload\n"
+        "from r1cs_cases import SNARK_CASES\n"
+        "from test_gpu_snark import gpu_snark, GENS_LABEL, GENS_NV\n"
+        "ctx = spg.Context(0)\n"
+        "g = spg.R1CSGens(ctx, GENS_LABEL, GENS_NV)\n"
+        "ctx.prof_enable(True)\n"
+        "ctx.prof_read(reset=True)\n"
+        "(p,) = gpu_snark(ctx, g, workload.SnarkWorkload(**SNARK_CASES['mem_both_b3_x64_q2']), workload.tape_seed())\n"
+        "print(*('%%s=%%d' %% (k, v[0]) for k, v in sorted(ctx.prof_read().items())))\n"
+        "print(hashlib.sha256(p).hexdigest())\n"
+    ) % (os.path.join(root, "spartan-parallel_amd"), os.path.join(root, "tests"))
+    out = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, **env), capture_output=True, text=True,
+                         timeout=240)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = out.stdout.strip().splitlines()
+    return lines[-1], {k: int(v) for k, v in (w.split("=") for w in lines[-2].split())}
+
+
+@pytest.fixture(scope="module")
+def default_profile():
+    return profiled_prove({})
+
+
+@pytest.mark.parametrize("form", sorted(SHOWN_FORMS))
+def test_round_forms_that_show_they_ran(default_profile, form):
+    """forms whose switched site leaves a trace in the kernel profile, against the golden proof's bytes and against
+    the default run's launch counts: eq tables one lane per entry (SPG_EQ_LDS=0: k_eq_table<true> with the blob, and
+    a launch per table where the LDS kernel shares one among three); round evaluations on a grid of one or two
+    workgroups (SPG_SC_GRID: the case's phase-1 domain, computed from its executions and constraints, is more threads
+    of work than one or two workgroups hold, so the grid-stride loops iterate); row-commit encodings
+    on the device at every count (SPG_HOST_ENC_MAX=0)"""
+    import msm_form_cases as fc
+
+    env, rises, runs = SHOWN_FORMS[form]
+    if "SPG_SC_GRID" in env:
+        import workload
+
+        # the block proof's phase-1 domain is the case's sum of executions x constraints; already the half of it that
+        # every round covers at least once must be more threads (a quad per point) than the capped grid holds
+        dom = workload.SnarkWorkload(**SNARK_CASES["mem_both_b3_x64_q2"]).total_constraints // 2
+        cap = int(env["SPG_SC_GRID"])
+        assert 4 * dom > 256 * cap and fc.grid_for(4 * dom, env) == cap < fc.grid_for(4 * dom)
+    sha0, prof0 = default_profile
+    sha, prof = profiled_prove(env)
+    golden = json.load(open(os.path.join(G, "snark_proofs.json")))["mem_both_b3_x64_q2"]
+    assert sha0 == golden["proof_sha256"] and sha == golden["proof_sha256"]
+    for s in rises:
+        assert prof.get(s, 0) > prof0.get(s, 0), (s, prof.get(s, 0), prof0.get(s, 0))
+    for pre in runs:
+        assert sum(v for k, v in prof.items() if k.startswith(pre)) > 0, (pre, prof)
 
 
 # the smallest straight-line program whose block witnesses take the commit queue's early path: two block-vars

@@ -261,6 +261,41 @@ def test_no_drift(table):
     assert not unknown, unknown
 
 
+# knobs that select no launch form and that no GPU test's environment names, each with its reason. Everything else in
+# the table must be named in an environment of tests/test_gpu_*.py or tests/*_cases.py (knobs.hpp: "a new launch form
+# adds its row plus an entry in the form list of the matching GPU test").
+NOT_A_FORM = {
+    "SPG_BIG_PROBE": "debug: per-workgroup timestamps of msm_big on stderr; the results do not depend on it",
+    "SPG_COMB_PAD_GB": "cap: its other side (tables that stay packed) runs under SPG_COMB_PAD=0 and the 70 GB table of "
+                       "test_comb_big_rule_other_branch",
+    "SPG_COPY_TRACE": "trace: counts hipMemcpyAsync calls per source line",
+    "SPG_DEBUG_SNARK": "debug: transcript checkpoints on stderr",
+    "SPG_DEBUG_TR": "debug: first challenges on stderr",
+    "SPG_H2D_TRACE": "trace: one stderr line per streamed upload",
+    "SPG_POOL_SPIN_US": "deployment: how long an idle pool worker spins before it parks; no result depends on it",
+    "SPG_RCCL_TIMEOUT_S": "deployment: bounded wait of an RCCL exchange (tests/test_gpu_dist.py aborts by failpoint)",
+    "SPG_TRACE_EVENTS": "trace: lap ends with their clock times on stderr",
+}
+
+
+def test_every_form_has_a_gpu_test(table):
+    """every knob is named in an environment of some GPU test (a quoted name or a NAME= keyword in
+    tests/test_gpu_*.py or tests/*_cases.py), or pinned in NOT_A_FORM with its reason"""
+    files = glob.glob(os.path.join(ROOT, "tests", "test_gpu_*.py")) + glob.glob(os.path.join(ROOT, "tests", "*_cases.py"))
+    assert len(files) > 20
+    text = ""
+    for f in files:
+        with open(f, errors="replace") as fh:
+            text += fh.read()
+    names = [r[0] for r in table if r[0].startswith("SPG_")]
+    named = {n for n in names if re.search(r"[\"']%s[\"']|\b%s=" % (n, n), text)}
+    assert set(NOT_A_FORM) <= set(names), sorted(set(NOT_A_FORM) - set(names))
+    assert not (named & set(NOT_A_FORM)), "has a test now; take it out of NOT_A_FORM: %s" % sorted(named & set(NOT_A_FORM))
+    missing = sorted(set(names) - named - set(NOT_A_FORM))
+    assert not missing, "no GPU test's environment names %s" % missing
+    assert all(reason.strip() for reason in NOT_A_FORM.values())
+
+
 def test_read_sites():
     """knobs.hpp is the only file in csrc/ that reads the environment"""
     hits = []
