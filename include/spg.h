@@ -365,6 +365,44 @@ int spg_msm_points(spg_ctx* ctx, const uint8_t* compressed, const uint64_t* scal
  * default (SPG_VMSM_HOST_MAX, else 64, the measured crossover). Results are identical either way. */
 int spg_set_vmsm_host_max(spg_ctx* ctx, long n);
 
+/* ---- many short sums in one launch (csrc/eqcheck.hip) -----------------------------------------
+ * E independent equations sum_i s_i * P_i = identity over one-off points: the shape of a verifier's sigma-protocol
+ * checks (KnowledgeProof, EqualityProof, ProductProof, DotProductProof, the tail of DotProductProofLog,
+ * src/nizk/mod.rs:50-570), a few hundred sums of 2-25 terms. The call is one flat list of T = first[E] terms cut into
+ * consecutive equations: equation e is terms first[e] .. first[e+1] (first[0] = 0, E + 1 entries, non-decreasing).
+ * Term i has the scalar scalars_mont[4 i ..] (Montgomery limbs) and a point named by forms[i] and operands[i]:
+ *   SPG_EQS_COMPRESSED  compressed[32 * operands[i] ..], a CompressedRistretto decoded on the device
+ *   SPG_EQS_EXTENDED    extended[128 * operands[i] ..], X, Y, Z, T in the spg_msm_partial layout (a point the caller
+ *                       already holds uncompressed; taken as given, not checked to be on the curve)
+ *   SPG_EQS_INDEX       point operands[i] of `base` (resident affine Niels: no decompression; a few generators)
+ * base may be NULL when no term uses SPG_EQS_INDEX, a pool may be NULL when its count is 0.
+ * status[e]: 0 the sum is the ristretto255 identity (RFC 9496 4.3.3 equality with the identity: X = 0 or Y = 0 of the
+ *              extended sum); an equation without terms is the identity, as the reference's empty sum
+ *            1 the sum is not the identity
+ *            2 a term's encoding was rejected by CompressedRistretto::decompress
+ * *bad_term (optional): the lowest term with a rejected encoding over the whole call, -1 when there is none.
+ * sums (optional): E x 32, the encoding of each sum (32 zero bytes for status 2).
+ * Returns 0 when it ran, whatever the statuses. Malformed arguments (first not non-decreasing or not starting at 0,
+ * an unknown form, an operand index past its pool or past the handle): SPG_E_ARG before anything is launched.
+ * T and E below 2^31. Single-rank, like the variable-base calls above. */
+#define SPG_EQS_COMPRESSED 0
+#define SPG_EQS_EXTENDED 1
+#define SPG_EQS_INDEX 2
+int spg_eqs_check(spg_ctx* ctx, const spg_points* base, const uint8_t* compressed, size_t n_compressed,
+                  const uint8_t* extended, size_t n_extended, const uint8_t* forms, const uint32_t* operands,
+                  const uint64_t* scalars_mont, const size_t* first, size_t E, uint8_t* sums, uint8_t* status,
+                  long* bad_term);
+/* The equations and terms of this context's most recent spg_eqs_check (a deferred verifier's launch included; 0, 0
+ * before the first). */
+int spg_eqs_last_counts(const spg_ctx* ctx, size_t* equations, size_t* terms);
+/* on != 0: this context's verifiers (spg_snark_verify*, spg_r1cs_verify, spg_spark_verify, spg_zk_sumcheck_verify,
+ * spg_poly_eval_verify* / spg_pe_verify_*) do not evaluate their sigma-protocol group equations one by one on the host
+ * but collect them as terms and check them in one spg_eqs_check launch at the end of the call. Verdicts and
+ * spg_last_error texts are those of the default (off) for every input: the lowest-numbered failing equation names the
+ * failure, and any other failure met while equations are pending checks those first. Group values that feed the
+ * transcript stay on the host either way. */
+int spg_set_verify_device(spg_ctx* ctx, int on);
+
 /* ---- R1CS data-parallel satisfiability proof --------------------------------------------------
  * Flat C views of the reference's R1CSInstance (src/r1csinstance.rs:19-31) and
  * ProverWitnessSecInfo (src/lib.rs:508-527). Entries are the reference's SparseMatEntry

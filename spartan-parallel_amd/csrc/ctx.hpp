@@ -25,6 +25,10 @@ struct spg_ctx {
   // spg_set_vmsm_host_max: this context's variable-base MSMs below that many points run on the host pool
   // (msm_var.hip); -1: the process default (SPG_VMSM_HOST_MAX, read once, else the measured crossover)
   long vmsm_host_max = -1;
+  // spg_set_verify_device: this context's verifiers collect their sigma-protocol group equations and check them in
+  // one spg_eqs_check launch at the end of the entry point (verify.hip, eqcheck.hip) instead of one by one on the host
+  bool verify_device = false;
+  size_t eqs_equations = 0, eqs_terms = 0;  // of the most recent spg_eqs_check launch (spg_eqs_last_counts)
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   hipEvent_t ev_cx = nullptr;  // DotProductProofLog: the Cx MSM's completion, ahead of Bullet round 0 on the stream
@@ -127,6 +131,12 @@ struct spg_gens {
   mutable std::mutex comb_mu;
   mutable Comb comb;
   mutable std::vector<Comb> comb_retired;
+};
+
+struct spg_points {  // caller-supplied points (msm_var.hip; base operands of eqcheck.hip)
+  size_t n = 0;
+  spg::Niels* niels = nullptr;      // n affine Niels points (device)
+  uint8_t* compressed = nullptr;    // n x 32 host copy
 };
 
 namespace spg {

@@ -11,6 +11,7 @@
 
 #include "comm.hpp"
 #include "curve.hpp"
+#include "eqcheck.hpp"
 #include "hcurve.hpp"
 #include "hvec.hpp"
 #include "hostmath.hpp"
@@ -357,6 +358,35 @@ int spgh_vmsm_digits(const uint64_t* scalar_mont, int c, int* out) {
   const int W = vmsm_windows(c);
   for (int w = 0; w < W; w++) out[w] = vmsm_digit(k.l, c, w, carry);
   return W;
+}
+
+// spg_eqs_check's semantics on the host (eqcheck.hpp): the argument check the device entry makes before it launches
+// anything (-1: malformed, as SPG_E_ARG), then every equation evaluated with hcurve.hpp. base: the nb base points as
+// encodings (the device entry holds them resident). plan (optional): the term and sum kernels' grids for this call.
+int spgh_eqs_check(const uint8_t* base, size_t nb, const uint8_t* compressed, size_t nc, const uint8_t* extended,
+                   size_t ne, const uint8_t* forms, const uint32_t* operands, const uint64_t* scalars_mont,
+                   const size_t* first, size_t E, uint8_t* sums, uint8_t* status, long* bad_term, unsigned* plan) {
+  if (E && (!first || !status)) return -1;
+  if (nb && !base) return -1;
+  EqsView v;
+  v.kinds = forms;
+  v.refs = operands;
+  v.scalars = (const Fq*)scalars_mont;
+  v.first = first;
+  v.E = E;
+  v.compressed = compressed;
+  v.nc = nc;
+  v.extended = extended;
+  v.ne = ne;
+  v.nb = nb;
+  if (eqs_validate(v)) return -1;
+  if (plan) {
+    const EqsPlan p = eqs_plan(v.T(), E);
+    plan[0] = p.term_grid;
+    plan[1] = p.sum_grid;
+  }
+  eqs_host_eval(v, base, sums, status, bad_term);
+  return 0;
 }
 
 // merge_order (snark_shape.hpp), the section merge of SNARK::prove and SNARK::verify: sizes = the components'

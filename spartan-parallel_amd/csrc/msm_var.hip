@@ -32,12 +32,6 @@
 #include "quad.hpp"
 #include "vmsm.hpp"
 
-struct spg_points {
-  size_t n = 0;
-  spg::Niels* niels = nullptr;      // n affine Niels points (device)
-  uint8_t* compressed = nullptr;    // n x 32 host copy
-};
-
 namespace spg {
 
 namespace {

@@ -4,6 +4,13 @@
 // points, hcurve.hpp), variable-base MSMs over proof points (Hyrax row commitments, Bullet L/R) by a host
 // Pippenger on the pool, and the Bullet generator folds sum_i s_i G_i as fixed-base MSMs on the GPU against the
 // resident generator tables (device_msm_idx).
+// Deferred mode (spg_set_verify_device, off by default): the sigma-protocol checks below are independent equations
+// sum_i s_i P_i = identity whose scalars come from the transcript, so V does not evaluate them but appends their
+// terms to one list (each equation keeps its check's label) and every entry point checks the list in one
+// spg_eqs_check launch when its walk is over (eqcheck.hip). Any other failure met on the way checks the pending
+// equations first, so the failure reported is the one the eager order meets first. Group values that feed the
+// transcript (the ZK sumcheck's target, R1CSProof's expected1 / claim2 / expected2, PolyEvalProof's LZ and Zc) are a
+// transcript-ordered chain and stay on the host in both modes.
 //
 //   KnowledgeProof / EqualityProof / ProductProof / DotProductProof::verify   src/nizk/mod.rs:50-404
 //   BulletReductionProof::verify, DotProductProofLog::verify                  src/nizk/bullet.rs:138-232, mod.rs:525-570
@@ -19,6 +26,7 @@
 #include <algorithm>
 #include <string>
 
+#include "eqcheck.hpp"
 #include "hostpoly.hpp"
 #include "knobs.hpp"
 #include "pe_plan.hpp"
@@ -307,10 +315,93 @@ struct V {
   spg_ctx* ctx;
   Tr& t;
   const char* failed = nullptr;
-  V(spg_ctx* c, Tr& tt) : ctx(c), t(tt) {}
+  const bool deferred;
+  V(spg_ctx* c, Tr& tt) : ctx(c), t(tt), deferred(c->verify_device) {}
+  // the first failure names the verdict; in deferred mode an equation still pending is an earlier check than
+  // whatever fails now, so the pending equations are checked first and a failing one wins
   bool fail(const char* what) {
-    if (!failed) failed = what;
+    if (!failed) {
+      const char* w = flush();
+      failed = w ? w : what;
+    }
     return false;
+  }
+  // the end of an entry point's walk: an accepting walk still has to pass its pending equations, a rejecting one
+  // that named no failure reports "rejected" unless a pending equation fails
+  bool conclude(bool ok) {
+    if (!ok) return fail("rejected");
+    const char* w = flush();
+    return w ? fail(w) : true;
+  }
+
+  // ---- deferred mode: the term list of one spg_eqs_check call. Proof points go in as their 32 bytes (the device
+  // decodes them: a rejected encoding is status 2, the eager path's "point decompression"), points the verifier holds
+  // as HExt in the extended form, generators as indices into the first generator set met (resident affine Niels;
+  // generators of another set as their encodings)
+  struct Pending {
+    std::vector<uint8_t> forms, ext;
+    std::vector<uint32_t> refs;
+    FqV scalars;
+    std::vector<Pt> comp;
+    std::vector<size_t> first{0};
+    std::vector<const char*> labels;
+  } pend;
+  const spg_gens* base = nullptr;
+  void term(uint8_t form, size_t ref, const Fq& s) {
+    pend.forms.push_back(form);
+    pend.refs.push_back((uint32_t)ref);
+    pend.scalars.push_back(s);
+  }
+  void tP(const Fq& s, const Pt& p) {
+    term(kEqsCompressed, pend.comp.size(), s);
+    pend.comp.push_back(p);
+  }
+  void tX(const Fq& s, const HExt& P) {
+    term(kEqsExtended, pend.ext.size() / 128, s);
+    pend.ext.resize(pend.ext.size() + 128);
+    eqs_ext_bytes(P, pend.ext.data() + pend.ext.size() - 128);
+  }
+  void tG(ProverGens& g, size_t idx, const Fq& s) {
+    if (!base) base = g.dev;
+    if (g.dev && base == g.dev && idx <= g.dev->n) return term(kEqsIndex, idx, s);
+    Pt p;
+    memcpy(p.b, g.host.comp.data() + 32 * idx, 32);
+    tP(s, p);
+  }
+  // -(x.commit(blind, k)) as terms
+  void tCommitNeg(ProverGens& g, const KeyView& k, const FqV& x, const Fq& blind) {
+    for (size_t i = 0; i < std::min(x.size(), k.G.size()); i++) tG(g, k.G[i], fq_neg(x[i]));
+    tG(g, k.h, fq_neg(blind));
+  }
+  bool eq_done(const char* label) {  // closes the open equation
+    pend.first.push_back(pend.forms.size());
+    pend.labels.push_back(label);
+    return true;
+  }
+  // checks the pending equations in one launch: nullptr when all hold (or none is pending), else the failure of the
+  // lowest-numbered one that does not
+  const char* flush() {
+    const size_t E = pend.labels.size();
+    if (!E) return nullptr;
+    EqsView v;
+    v.kinds = pend.forms.data();
+    v.refs = pend.refs.data();
+    v.scalars = pend.scalars.data();
+    v.first = pend.first.data();
+    v.E = E;
+    v.compressed = pend.comp.empty() ? nullptr : pend.comp[0].b;
+    v.nc = pend.comp.size();
+    v.extended = pend.ext.data();
+    v.ne = pend.ext.size() / 128;
+    v.nb = base ? base->n + 1 : 0;
+    std::vector<uint8_t> status(E);
+    const int rc = eqs_check_run(ctx, v, base ? base->niels : nullptr, nullptr, status.data(), nullptr);
+    const std::vector<const char*> labels = std::move(pend.labels);
+    pend = Pending();
+    if (rc) return "device equation check";
+    for (size_t e = 0; e < E; e++)
+      if (status[e]) return status[e] == kEqsBadPoint ? "point decompression" : labels[e];
+    return nullptr;
   }
   // x.commit(blind, key) for keys of a few generators (host fixed-base tables)
   HExt commit(ProverGens& g, const KeyView& k, const FqV& x, const Fq& blind) {
@@ -365,6 +456,12 @@ struct V {
     t.point("C", C);
     t.point("alpha", p.alpha);
     const Fq c = t.challenge("c");
+    if (deferred) {  // c C + alpha - (z1 G + z2 h) = 0
+      tP(c, C);
+      tP(fq_one(), p.alpha);
+      tCommitNeg(g, k, {p.z1}, p.z2);
+      return eq_done("KnowledgeProof");
+    }
     return eqP(commit1(g, k, p.z1, p.z2), addP(mulP(dec(C), c), dec(p.alpha))) || fail("KnowledgeProof");
   }
   bool equality(ProverGens& g, const KeyView& k, const EqualityProofP& p, const Pt& C1, const Pt& C2) {
@@ -373,6 +470,13 @@ struct V {
     t.point("C2", C2);
     t.point("alpha", p.alpha);
     const Fq c = t.challenge("c");
+    if (deferred) {  // c (C1 - C2) + alpha - z h = 0
+      tP(c, C1);
+      tP(fq_neg(c), C2);
+      tP(fq_one(), p.alpha);
+      tG(g, k.h, fq_neg(p.z));
+      return eq_done("EqualityProof");
+    }
     const HExt C = subP(dec(C1), dec(C2));
     return eqP(g.host.msm({k.h}, {p.z}), addP(mulP(C, c), dec(p.alpha))) || fail("EqualityProof");
   }
@@ -385,6 +489,21 @@ struct V {
     t.point("beta", p.beta);
     t.point("delta", p.delta);
     const Fq c = t.challenge("c");
+    if (deferred) {  // alpha + c X = com(z0, z1); beta + c Y = com(z2, z3); delta + c Z = z2 X + z4 h
+      tP(fq_one(), p.alpha);
+      tP(c, X);
+      tCommitNeg(g, k, {p.z[0]}, p.z[1]);
+      eq_done("ProductProof");
+      tP(fq_one(), p.beta);
+      tP(c, Y);
+      tCommitNeg(g, k, {p.z[2]}, p.z[3]);
+      eq_done("ProductProof");
+      tP(fq_one(), p.delta);
+      tP(c, Z);
+      tP(fq_neg(p.z[2]), X);
+      tG(g, k.h, fq_neg(p.z[4]));
+      return eq_done("ProductProof");
+    }
     const HExt Xp = dec(X);
     auto check = [&](const Pt& P, const HExt& Q, const HExt& rhs) { return eqP(addP(dec(P), mulP(Q, c)), rhs); };
     const bool ok = check(p.alpha, Xp, commit1(g, k, p.z[0], p.z[1])) && check(p.beta, dec(Y), commit1(g, k, p.z[2], p.z[3])) &&
@@ -403,6 +522,16 @@ struct V {
     if (p.z.size() != a.size() || a.size() > kn.G.size()) return fail("DotProductProof size");
     Fq dz = fq_zero();
     for (size_t i = 0; i < a.size(); i++) dz = fq_add(dz, fq_mul(p.z[i], a[i]));
+    if (deferred) {  // c Cx + delta = com(z, z_delta); c Cy + beta = com(<z, a>, z_beta)
+      tP(c, Cx);
+      tP(fq_one(), p.delta);
+      tCommitNeg(g, kn, p.z, p.z_delta);
+      eq_done("DotProductProof");
+      tP(c, Cy);
+      tP(fq_one(), p.beta);
+      tCommitNeg(g, k1, {dz}, p.z_beta);
+      return eq_done("DotProductProof");
+    }
     const bool ok = eqP(addP(mulP(dec(Cx), c), dec(p.delta)), commit(g, kn, p.z, p.z_delta)) &&
                     eqP(addP(mulP(dec(Cy), c), dec(p.beta)), commit1(g, k1, dz, p.z_beta));
     return ok || fail("DotProductProof");
@@ -441,6 +570,24 @@ struct V {
     const HExt g_hat = gens_msm(g, g.gens_n, s);
     Fq a_hat = fq_zero();
     for (size_t i = 0; i < n; i++) a_hat = fq_add(a_hat, fq_mul(a[i], s[i]));
+    if (deferred) {
+      // a_hat (c Gamma_hat + beta) + delta - z1 (g_hat + a_hat r G_1) - z2 h = 0 with
+      // Gamma_hat = sum_i u_i^2 L_i + sum_i u_i^-2 R_i + Cx + r Cy
+      t.point("delta", p.delta);
+      t.point("beta", p.beta);
+      const Fq c = t.challenge("c");
+      const Fq ac = fq_mul(a_hat, c);
+      for (size_t i = 0; i < lg_n; i++) tP(fq_mul(ac, fq_sqr(ch[i])), p.L[i]);
+      for (size_t i = 0; i < lg_n; i++) tP(fq_mul(ac, fq_sqr(chinv[i])), p.R[i]);
+      tX(ac, Cx);
+      tX(fq_mul(ac, r), Cy);
+      tP(a_hat, p.beta);
+      tP(fq_one(), p.delta);
+      tX(fq_neg(p.z1), g_hat);
+      tG(g, g.gens_1.G[0], fq_neg(fq_mul(p.z1, fq_mul(a_hat, r))));
+      tG(g, g.gens_1.h, fq_neg(p.z2));
+      return eq_done("DotProductProofLog");
+    }
     FqV sc;
     std::vector<HExt> P;
     for (size_t i = 0; i < lg_n; i++) {
@@ -777,8 +924,29 @@ struct SnarkVerifier : V {
     }
     if (!pe_batched_disjoint(g, pf.evals, np_list, ni_list, rq, ry, comm_Zr, comm_list)) return false;
     const FqV prefix = prefix_list(nws, rw);
+    if (deferred) {
+      // sum_p EQ_p m_p sum_i prefix_i f_{i,p} C_{i,p} - comm_vars_at_ry = 0, the C_{i,p} as decoded above (comm_Zr)
+      FqV EQ = eq_evals_host(rp);
+      EQ.resize(n);
+      std::vector<size_t> sec0(nws, 0);
+      for (size_t i = 1; i < nws; i++) sec0[i] = sec0[i - 1] + ws[i - 1]->num_proofs.size();
+      for (size_t p = 0; p < n; p++) {
+        Fq m = fq_one();
+        for (size_t q = 0; q < nq - lg2(num_proofs[p]); q++) m = fq_mul(m, fq_sub(fq_one(), rq[q]));
+        m = fq_mul(m, EQ[p]);
+        for (size_t i = 0; i < nws; i++) {
+          const size_t pw = ws[i]->num_proofs.size() == 1 ? 0 : p;
+          if (pw >= ws[i]->num_proofs.size()) return fail("witness section instances");
+          const size_t lni = lg2(ws[i]->num_inputs[pw]);
+          const Fq f = ws[i]->num_inputs[pw] >= max_ni ? fq_one() : ry_factors[ny - lni];
+          tX(fq_mul(m, fq_mul(prefix[i], f)), comm_Zr[sec0[i] + pw]);
+        }
+      }
+      tP(fq_neg(fq_one()), pf.comm_vars_at_ry);
+      eq_done("comm_vars_at_ry");
+    }
     std::vector<HExt> expected_list;
-    for (size_t p = 0; p < n; p++) {
+    for (size_t p = 0; !deferred && p < n; p++) {
       HExt comb = h::hext_identity();
       for (size_t i = 0; i < nws; i++) {
         const size_t pw = ws[i]->num_proofs.size() == 1 ? 0 : p;
@@ -794,7 +962,7 @@ struct SnarkVerifier : V {
     }
     FqV EQ = eq_evals_host(rp);
     EQ.resize(n);
-    if (!eqP(msm_var(EQ, expected_list), pf.comm_vars_at_ry)) return fail("comm_vars_at_ry");
+    if (!deferred && !eqP(msm_var(EQ, expected_list), pf.comm_vars_at_ry)) return fail("comm_vars_at_ry");
     const Fq k = fq_mul(fq_add(fq_add(fq_mul(r_A, ev[0]), fq_mul(r_B, ev[1])), fq_mul(r_C, ev[2])), p_rp);
     const Pt expected2 = compress(mulP(dec(pf.comm_vars_at_ry), k));
     if (!equality(g, g.gens_1, pf.eq2, expected2, post2)) return false;
@@ -1347,7 +1515,7 @@ static int spg_snark_verify_impl(spg_ctx* ctx, const spg_snark_comp* block, cons
   SnarkVerifier v(ctx, transcript->t);
   bool ok = false;
   try {
-    ok = snark_verify(v, pf, in, pub, vb, vp, vr, vars_gens->g);
+    ok = v.conclude(snark_verify(v, pf, in, pub, vb, vp, vr, vars_gens->g));
   } catch (const Fail& f) {
     v.fail(f.what);
   }
@@ -1383,7 +1551,7 @@ static int spg_spark_verify_impl(spg_ctx* ctx, spg_spark* S, const uint64_t* rx,
   SnarkVerifier v(ctx, transcript->t);
   bool ok = false;
   try {
-    ok = v.spark(S, pf, ex, ey, evals);
+    ok = v.conclude(v.spark(S, pf, ex, ey, evals));
   } catch (const Fail& f) {
     v.fail(f.what);
   }
@@ -1465,8 +1633,8 @@ static int spg_r1cs_verify_impl(spg_ctx* ctx, const spg_r1cs_gens* gens, size_t 
   std::vector<FqV> ch;
   bool ok = false;
   try {
-    ok = v.r1cs(const_cast<ProverGens&>(gens->g), pf, num_instances, max_num_proofs, np, max_num_inputs, ws, num_cons,
-                ev, &ch);
+    ok = v.conclude(v.r1cs(const_cast<ProverGens&>(gens->g), pf, num_instances, max_num_proofs, np, max_num_inputs, ws,
+                           num_cons, ev, &ch));
   } catch (const Fail& f) {
     v.fail(f.what);
   }
@@ -1659,7 +1827,7 @@ static int spg_snark_verify_public_impl(spg_ctx* ctx, const spg_snark_comp* bloc
   SnarkVerifier v(ctx, transcript->t);
   bool ok = false;
   try {
-    ok = snark_verify(v, pf, in, pub, vb, vp, vr, vars_gens->g);
+    ok = v.conclude(snark_verify(v, pf, in, pub, vb, vp, vr, vars_gens->g));
   } catch (const Fail& f) {
     v.fail(f.what);
   }
@@ -1688,7 +1856,7 @@ static int pe_verify_run(spg_ctx* ctx, Tr& t, const char* what, bool parsed, con
   V v(ctx, t);
   bool ok = false;
   try {
-    ok = run(v);
+    ok = v.conclude(run(v));
   } catch (const Fail& f) {
     v.fail(f.what);
   }

@@ -224,6 +224,18 @@ class Context:
         every size through the kernels; negative: the process default)"""
         self.call("spg_set_vmsm_host_max", n)
 
+    def set_verify_device(self, on=True):
+        """spg_set_verify_device: this context's verifiers collect their sigma-protocol group equations and check them
+        in one spg_eqs_check launch at the end of the call (same verdicts and error texts; off by default)"""
+        self.call("spg_set_verify_device", 1 if on else 0)
+
+    def eqs_last_counts(self):
+        """spg_eqs_last_counts: (equations, terms) of this context's most recent spg_eqs_check launch, a deferred
+        verifier's included"""
+        e, t = ctypes.c_size_t(), ctypes.c_size_t()
+        self.call("spg_eqs_last_counts", ctypes.byref(e), ctypes.byref(t))
+        return int(e.value), int(t.value)
+
     def last_kernel_us(self):
         return lib().spg_last_kernel_us(self._h)
 
@@ -571,6 +583,42 @@ def msm_points(ctx, compressed, scalars):
     out = np.zeros(32, dtype=np.uint8)
     ctx.call("spg_msm_points", _p(comp), _p(s), comp.shape[0], _p(out))
     return out.tobytes()
+
+
+# operand forms of spg_eqs_check (the header's SPG_EQS_* values)
+EQS_COMPRESSED, EQS_EXTENDED, EQS_INDEX = 0, 1, 2
+
+
+def eqs_pack(forms, operands, scalars, first, compressed=None, extended=None):
+    """the flat arrays of one spg_eqs_check call: (compressed (nc, 32) u8, extended (ne, 128) u8, forms u8, operands
+    u32, scalars (T, 4) u64, first u64 of E + 1 entries)"""
+    comp = np.ascontiguousarray(np.zeros((0, 32), np.uint8) if compressed is None else compressed,
+                                dtype=np.uint8).reshape(-1, 32)
+    ext = np.ascontiguousarray(np.zeros((0, 128), np.uint8) if extended is None else extended,
+                               dtype=np.uint8).reshape(-1, 128)
+    f = np.ascontiguousarray(forms, dtype=np.uint8).reshape(-1)
+    o = np.ascontiguousarray(operands, dtype=np.uint32).reshape(-1)
+    s = _scalars(scalars) if f.shape[0] else np.zeros((0, 4), dtype=np.uint64)
+    fi = np.ascontiguousarray(first, dtype=np.uint64).reshape(-1)
+    assert f.shape == o.shape and s.shape[0] == f.shape[0] and fi.shape[0] >= 1
+    return comp, ext, f, o, s, fi
+
+
+def eqs_check(ctx, forms, operands, scalars, first, compressed=None, extended=None, base=None, sums=True):
+    """spg_eqs_check: E = len(first) - 1 sums of terms first[e] .. first[e + 1], term i = scalars[i] times the point
+    operands[i] of the pool forms[i] names (EQS_COMPRESSED: compressed, EQS_EXTENDED: extended (128 bytes each),
+    EQS_INDEX: the Points `base`). Returns (status u8[E]: 0 identity / 1 not / 2 rejected encoding, the (E, 32)
+    encodings of the sums or None, the lowest rejected term or -1). Malformed arguments raise SpgError (SPG_E_ARG)."""
+    comp, ext, f, o, s, fi = eqs_pack(forms, operands, scalars, first, compressed, extended)
+    E = fi.shape[0] - 1
+    status = np.full(max(E, 1), 255, dtype=np.uint8)
+    out = np.zeros((max(E, 1), 32), dtype=np.uint8) if sums else None
+    bad = ctypes.c_long(-2)
+    ctx.call("spg_eqs_check", base.handle if base is not None else None, _p(comp) if comp.shape[0] else None,
+             comp.shape[0], _p(ext) if ext.shape[0] else None, ext.shape[0], _p(f) if f.shape[0] else None,
+             _p(o) if o.shape[0] else None, _p(s) if s.shape[0] else None, _p(fi), E,
+             _p(out) if sums else None, _p(status), ctypes.byref(bad))
+    return status[:E], (out[:E] if sums else None), int(bad.value)
 
 
 # ---------------------------------------------------------------- Fiat-Shamir objects
