@@ -32,6 +32,7 @@ extern "C" {
 #define SPG_E_NODEVICE -5  /* no usable gfx950 device */
 #define SPG_E_VERIFY -6    /* a proof did not verify (spg_last_error names the failed check) */
 #define SPG_E_CALLBACK -7  /* a caller-provided transcript callback returned non-zero */
+#define SPG_E_UNSAT -8  /* check mode: the witness does not satisfy the instance (spg_last_error names the row) */
 
 /* Opaque handles: every one is created, used and freed through the functions below. */
 typedef struct spg_ctx spg_ctx;
@@ -589,6 +590,34 @@ int spg_r1cs_prove(spg_ctx* ctx, const spg_r1cs_gens* gens, const spg_r1cs_inst*
                    const spg_r1cs_witness* witness, spg_transcript* transcript, spg_random_tape* tape,
                    uint8_t* proof, size_t proof_cap, size_t* proof_len, uint64_t* challenges_out, size_t* ch_lens);
 
+/* ---- witness satisfiability: Az[i] Bz[i] == Cz[i] for every row (the reference's R1CSInstance::is_sat,
+ * src/r1csinstance.rs:322-357), one streaming launch over the tables multiply_vec_block leaves in HBM. */
+typedef struct {
+  uint64_t rows;        /* rows examined: sum_p num_proofs[p] * num_cons[p] */
+  uint64_t violations;  /* rows with Az * Bz != Cz */
+  uint64_t p, q, row;   /* the lowest violating (p, q, row), lexicographic, in natural (not reversed) indices */
+  uint64_t az[4], bz[4], cz[4]; /* the three values there (Montgomery); all of p..cz zero when violations == 0 */
+} spg_sat_report;
+/* On three tables as spg_r1cs_multiply_vec_block returns them: one shape, one witness section, unbound (current
+ * sizes equal to the allocation sizes); anything else is SPG_E_ARG before a launch. Returns 0 when it ran, whatever
+ * it found, as spg_eqs_check does. Single-rank. */
+int spg_pqx_sat_check(spg_ctx* ctx, const spg_pqx* Az, const spg_pqx* Bz, const spg_pqx* Cz, spg_sat_report* out);
+/* The same on an instance and a witness: the shape and witness arguments of spg_r1cs_prove with the same checks, the
+ * prover's own multiply_vec_block, then the check; no generators, transcript or tape. p is the caller's instance
+ * index, also when every instance shares one matrix triple. Under spg_set_comm with nranks > 1 a collective: every
+ * rank checks its shard and every rank returns the same merged report (counts summed, the lowest row's values). */
+int spg_r1cs_sat_check(spg_ctx* ctx, const spg_r1cs_inst* inst, size_t num_instances, size_t max_num_proofs,
+                       const size_t* num_proofs, size_t max_num_inputs, const size_t* num_inputs,
+                       const spg_r1cs_witness* witness, spg_sat_report* out);
+/* on != 0 (off by default; no environment switch): spg_r1cs_prove runs the check right after its
+ * multiply_vec_block, and through it spg_snark_prove checks its three R1CSProofs. A violation returns SPG_E_UNSAT with
+ * *proof_len = 0 and spg_last_error "R1CS unsatisfied: instance P execution Q constraint R (V of N rows)", in
+ * spg_snark_prove prefixed with the stage ("block: ", "pairwise: ", "perm_root: "; the block stage also names the
+ * caller's block number). Transcript and tape are left in an unspecified state then. With nranks > 1 every rank
+ * learns the verdict in one exchange before any returns, so all return SPG_E_UNSAT together. With the mode off
+ * the provers launch exactly what they did before. */
+int spg_set_check_sat(spg_ctx* ctx, int on);
+
 /* DensePolynomial::commit without blinds (src/dense_mlpoly.rs:184-256) of n scalars (zero-padded to a power of
  * two 2^k) with gens.gens_pc: L = 2^(k/2) Hyrax row commitments of 2^(k - k/2) scalars into out (32 bytes each,
  * out_cap bytes; *L_out = L). The commitments spg_r1cs_verify takes for every witness section instance. */
@@ -701,6 +730,24 @@ int spg_snark_witness_free(spg_ctx* ctx, spg_snark_wit* wit);
 int spg_snark_prove(spg_ctx* ctx, spg_snark_comp* block, spg_snark_comp* pairwise, spg_snark_comp* perm_root,
                     const spg_snark_wit* wit, spg_r1cs_gens* vars_gens, spg_transcript* transcript,
                     spg_random_tape* tape, uint8_t* proof, size_t proof_cap, size_t* proof_len);
+/* What a verifier would reject a bad witness for, found without proving (debug builds call it before
+ * spg_snark_prove; the reference's assert!(inst.is_sat(..)) over the whole program). */
+typedef struct {
+  spg_sat_report sat[3];  /* block, pairwise, perm_root; p is the prover's (sorted / merged) instance position */
+  uint64_t component[3];  /* where sat[k].p came from: block: the caller's block number; pairwise: 0 execution consistency,
+                             1 physical, 2 virtual memory coherence; perm_root: 0 exec, 1 init phys, 2 init virt, 3 phys, 4 virt */
+  uint64_t perm_products[3]; /* 1 = the two sides differ: execution / blocks, physical memory, virtual memory */
+  int64_t io_point;       /* -1, or the first of the IO proof's opened points whose exec-inputs entry differs from its public value */
+  int64_t first;          /* -1 all pass; else the first failure in the verifier's order: 0-2 sat, 3-5 perm products, 6 io */
+} spg_snark_report;
+/* Runs SNARK::prove's witness generation through the input commitments (tau and r are drawn from `transcript` as a
+ * prove would draw them; the commitments are computed and discarded), then runs every check and fills *out: the
+ * three R1CS instances' satisfiability on the device, the permutation products spg_snark_verify multiplies, and the
+ * IO proof's opened points against the exec inputs. Returns 0 when it ran, whatever it found; spg_last_error
+ * describes the first failure. `transcript` is left in an unspecified state: pass a throwaway. Single-rank. */
+int spg_snark_check(spg_ctx* ctx, spg_snark_comp* block, spg_snark_comp* pairwise, spg_snark_comp* perm_root,
+                    const spg_snark_wit* wit, spg_r1cs_gens* vars_gens, spg_transcript* transcript,
+                    spg_snark_report* out);
 
 /* SNARK::verify (src/lib.rs:2750-3881) on the prover's own argument block: replays the transcript from the public
  * inputs (the spg_snark_inputs sizes, input / output / liveness and the init memory lists; block_vars, exec_inputs

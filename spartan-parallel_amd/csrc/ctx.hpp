@@ -28,6 +28,12 @@ struct spg_ctx {
   // spg_set_verify_device: this context's verifiers collect their sigma-protocol group equations and check them in
   // one spg_eqs_check launch at the end of the entry point (verify.hip, eqcheck.hip) instead of one by one on the host
   bool verify_device = false;
+  // spg_set_check_sat: spg_r1cs_prove checks Az * Bz == Cz right after its multiply_vec_block (satcheck.hip) and
+  // refuses an unsatisfying witness with SPG_E_UNSAT; sat_stage / sat_order: the SNARK stage whose R1CSProof is
+  // running and its instances' caller-side numbers (snark.hip), for the message
+  bool check_sat = false;
+  const char* sat_stage = nullptr;
+  const size_t* sat_order = nullptr;
   size_t eqs_equations = 0, eqs_terms = 0;  // of the most recent spg_eqs_check launch (spg_eqs_last_counts)
   hipStream_t stream = nullptr;
   hipEvent_t ev0 = nullptr, ev1 = nullptr;

@@ -20,6 +20,7 @@
 #include "knobs.hpp"
 #include "msm_plan.hpp"
 #include "pe_plan.hpp"
+#include "satcheck.hpp"
 #include "snark_shape.hpp"
 #include "vmsm.hpp"
 
@@ -386,6 +387,23 @@ int spgh_eqs_check(const uint8_t* base, size_t nb, const uint8_t* compressed, si
     plan[1] = p.sum_grid;
   }
   eqs_host_eval(v, base, sums, status, bad_term);
+  return 0;
+}
+
+// the merge of the ranks' satisfiability reports behind spg_r1cs_sat_check and the check mode of a sharded
+// spg_r1cs_prove (satcheck.hpp): reports = nranks spg_sat_report records, as the allgather delivers them
+int spgh_sat_merge(const spg_sat_report* reports, int nranks, spg_sat_report* out) {
+  if (!reports || !out || nranks < 1) return -1;
+  sat_merge(reports, nranks, out);
+  return 0;
+}
+// sat_descs / sat_decode (satcheck.hpp): the natural key of a packed table -> (p, q, row) and the stored (bit-reversed)
+// position, out[0..4); -1 for a shape the entries refuse or a key past the domain
+int spgh_sat_decode(const size_t* num_proofs, const size_t* num_cons, size_t P, uint64_t key, uint64_t* out) {
+  std::vector<SatDesc> d;
+  uint64_t total = 0;
+  if (!P || sat_descs(num_proofs, num_cons, P, &d, &total) || key >= total) return -1;
+  sat_decode(d, key, out, out + 1, out + 2, out + 3);
   return 0;
 }
 

@@ -20,6 +20,7 @@
 #include "pe_plan.hpp"
 #include "proto.hpp"
 #include "lds.hpp"
+#include "satcheck.hpp"
 #include "sumcheck.hpp"
 #include "zk_rounds.hpp"
 
@@ -630,7 +631,21 @@ struct Prover {
 
   int run();
   int run_stages();
+  void init_shape();
   int setup_tables(ZFill& zf);
+  // setup_tables in three parts, so that spg_r1cs_sat_check runs the first and the last without a transcript:
+  // shapes, workspace and descriptors (want_z: the Z table too); the tau eq tables; the k_spmv launch
+  int setup_desc(ZFill& zf, bool want_z);
+  int setup_tau();
+  int launch_spmv();
+  SpDesc* dsd_ = nullptr;
+  SecDesc* dsec_ = nullptr;
+  bool spmv_tiled_ = false;
+  double visits_ = 0;
+  // Az * Bz == Cz over this rank's tables (satcheck.hip), merged over the ranks: every rank gets the same report,
+  // with p the caller's instance index
+  // (rc: this rank's status so far; non-zero skips its launch and fails every rank)
+  int sat_check_tables(int rc, spg_sat_report* out);
   // phase 1
   int p1_mode(size_t j) const { return j < sh.nx ? MODE_X : (j < sh.nx + sh.nq ? MODE_Q : MODE_P); }
   int p1_advance(Phase1& s, size_t j);
@@ -795,19 +810,24 @@ static PqxDev compact_table(Fq* d, size_t n, size_t P) {
   return T;
 }
 
-int Prover::run_stages() {
-  t.protocol("R1CS proof");
+// the sizes of the prove and this rank's instances, from the arguments
+void Prover::init_shape() {
   sh.num_cons = inst.max_num_cons;
   sh.single = inst.num_instances == 1;
   std::vector<size_t> block_num_cons(P);
   for (size_t p = 0; p < P; p++) block_num_cons[p] = inst.num_cons[sh.single ? 0 : p];
   sh.np = lg2(npow2(P)), sh.nq = lg2(max_np), sh.nx = lg2(sh.num_cons), sh.nw = lg2(nws), sh.ny = lg2(Y);
-  plan_exchanges(sh.np, sh.nq, sh.nx, sh.nw, sh.ny);
   // this rank's instances [p0, p1): everything O(N) lives only here; nranks == 1 -> all of them
   sh.PLn = p1 - p0;
   sh.l_proofs.assign(num_proofs.begin() + p0, num_proofs.begin() + p1);
   sh.l_inputs.assign(num_inputs.begin() + p0, num_inputs.begin() + p1);
   sh.l_cons.assign(block_num_cons.begin() + p0, block_num_cons.begin() + p1);
+}
+
+int Prover::run_stages() {
+  t.protocol("R1CS proof");
+  init_shape();
+  plan_exchanges(sh.np, sh.nq, sh.nx, sh.nw, sh.ny);
 
   ZFill zf;
   int rc = setup_tables(zf);
@@ -847,11 +867,62 @@ int Prover::run_stages() {
 // Z (p, q_rev, w, x_rev) and Az, Bz, Cz = multiply_vec_block (p, q_rev, 0, x_rev) for the local instances: shapes,
 // workspace, every setup descriptor in one host-to-device copy, the tau eq tables, k_spmv; zf: the Z fill, made ready
 int Prover::setup_tables(ZFill& zf) {
-  const size_t PLn = sh.PLn, np = sh.np, nq = sh.nq, nx = sh.nx;
+  int rc = setup_desc(zf, true);
+  if (!rc) rc = setup_tau();
+  if (!rc) rc = launch_spmv();
+  if (!ctx->check_sat) return rc;
+  // check mode (spg_set_check_sat): refuse a witness that does not satisfy the instance, naming the row. Every rank
+  // holds the merged report, so all of them return here together and none waits in a later exchange; a rank whose
+  // setup failed still takes part, with its failure as status.
+  spg_sat_report rep;
+  if ((rc = sat_check_tables(rc, &rep))) return rc;
+  if (!rep.violations) return 0;
+  xshared = true;
+  std::string msg = sat_message(rep);
+  if (ctx->sat_stage) {
+    if (ctx->sat_order) msg += "; block " + std::to_string(ctx->sat_order[rep.p]);
+    msg = std::string(ctx->sat_stage) + ": " + msg;
+  }
+  return set_err(ctx, SPG_E_UNSAT, msg);
+}
+
+int Prover::sat_check_tables(int rc, spg_sat_report* out) {
+  std::vector<SatDesc> d;
+  uint64_t total = 0;
+  spg_sat_report mine;
+  memset(&mine, 0, sizeof(mine));
+  memset(out, 0, sizeof(*out));
+  if (rc) {
+  } else if (const char* why = sat_descs(sh.l_proofs.data(), sh.l_cons.data(), sh.PLn, &d, &total))
+    rc = set_err(ctx, SPG_E_ARG, std::string("sat_check: ") + why);
+  else if (total != cy.Az.total)
+    rc = set_err(ctx, SPG_E_ARG, "sat_check: descriptors do not cover the tables");
+  else
+    rc = sat_check_run(ctx, d, total, cy.Az.d, cy.Bz, cy.Cz, &mine);
+  if (mine.violations) mine.p += p0;
+  if (nranks == 1) {
+    *out = mine;
+    return rc;
+  }
+  // one framed allgather, outside the round plan: a rank whose check failed to run fails every rank with it
+  std::vector<uint8_t> all;
+  rc = comm_allgather(ctx, Shard{(int)rank, (int)nranks}, rc, &mine, sizeof(mine), all);
+  if (rc) {
+    xshared = true;
+    return rc;
+  }
+  sat_merge((const spg_sat_report*)all.data(), (int)nranks, out);
+  return 0;
+}
+
+int Prover::setup_desc(ZFill& zf, bool want_z) {
+  const size_t PLn = sh.PLn;
   cy.Zp = pqx_shape(sh.l_proofs, nws, sh.l_inputs, npow2(P), max_np, npow2(nws), Y);
   const size_t ztot = cy.Zp.total;
-  cy.Zp.d = (Fq*)ws_get(ctx, WS_Z, ztot * sizeof(Fq) + 64);
-  if (!cy.Zp.d) return set_err(ctx, SPG_E_NOMEM, "Z table");
+  if (want_z) {
+    cy.Zp.d = (Fq*)ws_get(ctx, WS_Z, ztot * sizeof(Fq) + 64);
+    if (!cy.Zp.d) return set_err(ctx, SPG_E_NOMEM, "Z table");
+  }
   PqxDev& Az = cy.Az;
   Az = pqx_shape(sh.l_proofs, 1, sh.l_cons, npow2(P), max_np, 1, sh.num_cons);
   const size_t atot = Az.total;
@@ -860,11 +931,10 @@ int Prover::setup_tables(ZFill& zf) {
   cy.Cz = (Fq*)ws_get(ctx, WS_CZ, atot * sizeof(Fq) + 64);
   if (!Az.d || !cy.Bz || !cy.Cz) return set_err(ctx, SPG_E_NOMEM, "Az/Bz/Cz");
   // every descriptor of the setup kernels (Z fill, Az/Bz/Cz) goes up in one host-to-device copy
-  SecDesc* dsec = nullptr;
   ZDesc* dz = nullptr;
-  SpDesc* dsd = nullptr;
-  double visits = 0;
-  bool z_tiled = knob::z_tiled(), spmv_tiled = knob::spmv_tiled();
+  bool z_tiled = knob::z_tiled();
+  spmv_tiled_ = knob::spmv_tiled();
+  visits_ = 0;
   int rc = 0;
   {
     std::vector<ZDesc> zd(PLn);
@@ -876,7 +946,7 @@ int Prover::setup_tables(ZFill& zf) {
       zd[p].ni = (uint32_t)sh.l_inputs[p];
       zd[p].lg_ni = (uint32_t)lg2(sh.l_inputs[p]);
       if (sh.l_inputs[p] < 256) z_tiled = false;
-      if (sh.l_cons[p] < 256) spmv_tiled = false;
+      if (sh.l_cons[p] < 256) spmv_tiled_ = false;
       for (size_t w = 0; w < nws; w++) {
         size_t pw = wit.num_proofs[w].size() == 1 ? 0 : p0 + p;
         if (!wit.ptr[w][pw]) return set_err(ctx, SPG_E_ARG, "witness shard does not hold instance");
@@ -901,18 +971,23 @@ int Prover::setup_tables(ZFill& zf) {
       spd[p].lg_rows = (uint32_t)lg2(sh.l_cons[p]);
       spd[p].ni = (uint32_t)sh.l_inputs[p];
       spd[p].lg_ni = (uint32_t)lg2(sh.l_inputs[p]);
-      visits += (double)sh.l_proofs[p] * (inst.nnz[3 * pi] + inst.nnz[3 * pi + 1] + inst.nnz[3 * pi + 2]);
+      visits_ += (double)sh.l_proofs[p] * (inst.nnz[3 * pi] + inst.nnz[3 * pi + 1] + inst.nnz[3 * pi + 2]);
     }
     rc = stage_desc(zd, &dz);
-    if (!rc) rc = stage_desc(sd, &dsec);
+    if (!rc) rc = stage_desc(sd, &dsec_);
     if (!rc) rc = stage_desc(md, &cy.dmd);
-    if (!rc) rc = stage_desc(spd, &dsd);
+    if (!rc) rc = stage_desc(spd, &dsd_);
     if (!rc) rc = flush_desc();
     if (rc) return rc;
   }
-  zf.c = ctx, zf.dz = dz, zf.dsec = dsec, zf.n = (int)PLn, zf.nws = (int)nws;
+  zf.c = ctx, zf.dz = dz, zf.dsec = dsec_, zf.n = (int)PLn, zf.nws = (int)nws;
   zf.Z = cy.Zp.d, zf.total = ztot, zf.tiled = z_tiled, zf.side = knob::z_side();
-  // ---- tau tables (identical on every rank)
+  return 0;
+}
+
+// ---- tau tables (identical on every rank)
+int Prover::setup_tau() {
+  const size_t np = sh.np, nq = sh.nq, nx = sh.nx;
   FqV tau_p = t.challenges("challenge_tau_p", np);
   FqV tau_q = t.challenges("challenge_tau_q", nq);
   FqV tau_x = t.challenges("challenge_tau_x", nx);
@@ -921,13 +996,17 @@ int Prover::setup_tables(ZFill& zf) {
   cy.Aq = (Fq*)ws_get(ctx, WS_TQ, (sizeof(Fq) << nq) + 64);
   cy.Ax = (Fq*)ws_get(ctx, WS_TX, (sizeof(Fq) << nx) + 64);
   if (!cy.Ap || !cy.Aq || !cy.Ax) return set_err(ctx, SPG_E_NOMEM, "eq tables");
-  rc = eq_tables(ctx, {{tau_p, cy.Ap}, {tau_q, cy.Aq}, {tau_x, cy.Ax}});
-  if (rc) return rc;
-  // ---- Az, Bz, Cz: outputs, CSR row pointers, and per visited entry its column, value and z gather
-  KScope ks(ctx, "spmv_block", 96.0 * atot + 12.0 * atot + 68.0 * visits);
-  hipLaunchKernelGGL(spmv_tiled ? k_spmv<true> : k_spmv<false>, dim3(blocks_for(atot)), dim3(256), 0, ctx->stream, dsd,
-                     (int)PLn, cy.dmd, inst.d_rowptr, inst.d_col, inst.d_val, dsec, (int)nws, (uint32_t)Y, Az.d, cy.Bz,
-                     cy.Cz, (uint64_t)atot);
+  return eq_tables(ctx, {{tau_p, cy.Ap}, {tau_q, cy.Aq}, {tau_x, cy.Ax}});
+}
+
+// ---- Az, Bz, Cz: outputs, CSR row pointers, and per visited entry its column, value and z gather
+int Prover::launch_spmv() {
+  const PqxDev& Az = cy.Az;
+  const size_t atot = Az.total, PLn = sh.PLn;
+  KScope ks(ctx, "spmv_block", 96.0 * atot + 12.0 * atot + 68.0 * visits_);
+  hipLaunchKernelGGL(spmv_tiled_ ? k_spmv<true> : k_spmv<false>, dim3(blocks_for(atot)), dim3(256), 0, ctx->stream,
+                     dsd_, (int)PLn, cy.dmd, inst.d_rowptr, inst.d_col, inst.d_val, dsec_, (int)nws, (uint32_t)Y, Az.d,
+                     cy.Bz, cy.Cz, (uint64_t)atot);
   SPG_HIP(ctx, hipGetLastError());
   return 0;
 }
@@ -2133,12 +2212,10 @@ static int check_prove_args(spg_ctx* ctx, const spg_r1cs_inst* inst, size_t num_
   return SPG_OK;
 }
 
-static int r1cs_prove_impl(spg_ctx* ctx, const spg_r1cs_gens* gens, const spg_r1cs_inst* inst,
-                           size_t num_instances, size_t max_num_proofs, const size_t* num_proofs,
-                           size_t max_num_inputs, const size_t* num_inputs, const spg_r1cs_witness* wit,
-                           spg_transcript* transcript, spg_random_tape* tape, uint8_t* proof, size_t proof_cap,
-                           size_t* proof_len, uint64_t* challenges_out, size_t* ch_lens) {
-  Prover pr(ctx, const_cast<spg_r1cs_gens*>(gens)->g, *inst, *wit, transcript->t, tape->t);
+// the argument check on every rank, then the prover's sizes; shared by spg_r1cs_prove and spg_r1cs_sat_check
+static int prover_args(spg_ctx* ctx, Prover& pr, const spg_r1cs_inst* inst, size_t num_instances,
+                       size_t max_num_proofs, const size_t* num_proofs, size_t max_num_inputs,
+                       const size_t* num_inputs, const spg_r1cs_witness* wit) {
   pr.rank = (size_t)ctx->rank;
   pr.nranks = (size_t)ctx->nranks;
   int rc_args = check_prove_args(ctx, inst, num_instances, max_num_proofs, num_proofs, max_num_inputs, num_inputs,
@@ -2161,9 +2238,21 @@ static int r1cs_prove_impl(spg_ctx* ctx, const spg_r1cs_gens* gens, const spg_r1
   pr.nws = wit->nws;
   pr.num_proofs.assign(num_proofs, num_proofs + num_instances);
   pr.num_inputs.assign(num_inputs, num_inputs + num_instances);
+  return SPG_OK;
+}
+
+static int r1cs_prove_impl(spg_ctx* ctx, const spg_r1cs_gens* gens, const spg_r1cs_inst* inst,
+                           size_t num_instances, size_t max_num_proofs, const size_t* num_proofs,
+                           size_t max_num_inputs, const size_t* num_inputs, const spg_r1cs_witness* wit,
+                           spg_transcript* transcript, spg_random_tape* tape, uint8_t* proof, size_t proof_cap,
+                           size_t* proof_len, uint64_t* challenges_out, size_t* ch_lens) {
+  Prover pr(ctx, const_cast<spg_r1cs_gens*>(gens)->g, *inst, *wit, transcript->t, tape->t);
+  int rc = prover_args(ctx, pr, inst, num_instances, max_num_proofs, num_proofs, max_num_inputs, num_inputs, wit);
+  if (rc) return rc;
   timer_start(ctx);
-  int rc = pr.run();
+  rc = pr.run();
   timer_stop(ctx);
+  if (rc == SPG_E_UNSAT) *proof_len = 0;  // check mode: no proof was written
   if (rc) return rc;
   Writer wr;
   pr.pf.ser(wr);
@@ -2192,6 +2281,26 @@ extern "C" int spg_r1cs_prove(spg_ctx* ctx, const spg_r1cs_gens* gens, const spg
   return tr_status(ctx, transcript->t,
                    r1cs_prove_impl(ctx, gens, inst, num_instances, max_num_proofs, num_proofs, max_num_inputs, num_inputs,
                                    wit, transcript, tape, proof, proof_cap, proof_len, challenges_out, ch_lens));
+}
+
+// R1CSInstance::is_sat (src/r1csinstance.rs:322-357) over every execution of every instance: the prover's own
+// descriptor setup and k_spmv, then k_sat_check (satcheck.hip) -- no Z fill, transcript or generators (the Prover's
+// references to them stay unused). A collective under spg_set_comm, as spg_r1cs_prove.
+extern "C" int spg_r1cs_sat_check(spg_ctx* ctx, const spg_r1cs_inst* inst, size_t num_instances, size_t max_num_proofs,
+                                  const size_t* num_proofs, size_t max_num_inputs, const size_t* num_inputs,
+                                  const spg_r1cs_witness* wit, spg_sat_report* out) {
+  if (!ctx || !inst || !num_proofs || !num_inputs || !wit || !out) return SPG_E_ARG;
+  ProverGens none;
+  Tr tr("sat_check");
+  Tape tape("sat_check", fq_zero());
+  Prover pr(ctx, none, *inst, *wit, tr, tape);
+  int rc = prover_args(ctx, pr, inst, num_instances, max_num_proofs, num_proofs, max_num_inputs, num_inputs, wit);
+  if (rc) return rc;
+  pr.init_shape();
+  ZFill zf;
+  rc = pr.setup_desc(zf, false);
+  if (!rc) rc = pr.launch_spmv();
+  return pr.sat_check_tables(rc, out);
 }
 
 // R1CSInstance::multi_evaluate (src/r1csinstance.rs:583-596) / evaluate (:632-641):

@@ -22,6 +22,7 @@
 #include "pe_plan.hpp"
 #include "pe_prove.hpp"
 #include "proto.hpp"
+#include "satcheck.hpp"
 #include "snark_shape.hpp"
 
 using namespace spg;
@@ -762,6 +763,22 @@ struct SnarkProver {
   int queue_input_commits();
   void write_commitments();
   int sat_then_evals(spg_snark_comp* C, const std::vector<size_t>& order, bool as_list);
+  // one of the three R1CSProofs as R1CSProof::prove takes it: the instance, the sizes, the witness sections, and for
+  // every (sorted / merged) instance the component it came from (spg_snark_report.component)
+  struct SatCall {
+    const char* stage;
+    spg_r1cs_inst* inst;
+    size_t P, max_np, max_ni;
+    std::vector<size_t> num_proofs, num_inputs, from;
+    std::vector<WPart> parts;
+  };
+  int block_call(SatCall* c);
+  int pairwise_call(SatCall* c);
+  int perm_root_call(SatCall* c);
+  int sat_stage(const SatCall& c);
+  // the product entry of every w3 polynomial in PERM_PRODUCT's merged order, and the component of each
+  int perm_prod_list(SecInfo* pw3, std::vector<size_t>* im, FqV* prod, std::vector<FqV>* r_list);
+  int check(spg_snark_report* out);
   int prove_block();
   int prove_pairwise();
   int prove_perm_root();
@@ -1002,18 +1019,36 @@ int SnarkProver::sat_then_evals(spg_snark_comp* C, const std::vector<size_t>& or
   return 0;
 }
 
+// R1CSProof::prove of one stage; in check mode (spg_set_check_sat) the prover's message names the stage, and for
+// the blocks the caller's block number
+int SnarkProver::sat_stage(const SatCall& c) {
+  struct Scope {
+    spg_ctx* x;
+    ~Scope() { x->sat_stage = nullptr, x->sat_order = nullptr; }
+  } scope{ctx};
+  ctx->sat_stage = c.stage;
+  ctx->sat_order = c.inst == block->dev_sorted ? c.from.data() : nullptr;
+  return sat_prove(ctx, vars_gens, c.inst, c.P, c.max_np, c.num_proofs, c.max_ni, c.num_inputs, c.parts, &Wt,
+                   transcript, tape_h, &so);
+}
+
 // BLOCK_CORRECTNESS_EXTRACT (lib.rs:2223-2309)
+int SnarkProver::block_call(SatCall* c) {
+  *c = SatCall{"block", block->dev_sorted, sh.P, sh.bmax, a.num_vars, sh.bnp_pad, sh.bnv, sh.order,
+               {wpart(s_bvars), wpart(w0.s), wpart(bw.w2.s), wpart(bw.w3.s), wpart(bw.w3s.s)}};
+  return 0;
+}
 int SnarkProver::prove_block() {
-  int rc = sat_prove(ctx, vars_gens, block->dev_sorted, sh.P, sh.bmax, sh.bnp_pad, a.num_vars, sh.bnv,
-                     {wpart(s_bvars), wpart(w0.s), wpart(bw.w2.s), wpart(bw.w3.s), wpart(bw.w3s.s)}, &Wt, transcript,
-                     tape_h, &so);
+  SatCall c;
+  int rc = block_call(&c);
+  if (!rc) rc = sat_stage(c);
   if (rc) return rc;
   lp.lap("block_sat");
   return sat_then_evals(block, sh.order, true);
 }
 
 // PAIRWISE_CHECK (lib.rs:2311-2424)
-int SnarkProver::prove_pairwise() {
+int SnarkProver::pairwise_call(SatCall* c) {
   SecInfo pw, pws;
   std::vector<size_t> im;
   int rc;
@@ -1024,23 +1059,36 @@ int SnarkProver::prove_pairwise() {
     if (im[i] == 2) comps[i] = &ts.s;
   const SecInfo tsb = concat(comps);
   const size_t n = pw.num_proofs.size();
-  rc = sat_prove(ctx, vars_gens, pairwise->dev_sorted, n, sh.pairwise_size, pw.num_proofs, sh.pw_nv,
-                 std::vector<size_t>(n, sh.pw_nv), {wpart(pw), wpart(pws), wpart(tsb)}, &Wt, transcript, tape_h, &so);
+  *c = SatCall{"pairwise", pairwise->dev_sorted, n, sh.pairwise_size, sh.pw_nv, pw.num_proofs,
+               std::vector<size_t>(n, sh.pw_nv), im, {wpart(pw), wpart(pws), wpart(tsb)}};
+  return 0;
+}
+int SnarkProver::prove_pairwise() {
+  SatCall c;
+  int rc = pairwise_call(&c);
+  if (!rc) rc = sat_stage(c);
   if (rc) return rc;
   return sat_then_evals(pairwise, sh.pw_order, false);
 }
 
 // PERM_ROOT (lib.rs:2426-2532)
-int SnarkProver::prove_perm_root() {
+int SnarkProver::perm_root_call(SatCall* c) {
   SecInfo w1, w2s, w3s, w4;
+  std::vector<size_t> im;
   int rc;
-  if ((rc = merge(ctx, {&s_exec, &iphy.s, &ivir.s, &aphy.s, &avir.s}, &w1))) return rc;
+  if ((rc = merge(ctx, {&s_exec, &iphy.s, &ivir.s, &aphy.s, &avir.s}, &w1, &im))) return rc;
   if ((rc = merge(ctx, {&pe.w2.s, &mem[0].w2.s, &mem[1].w2.s, &mem[2].w2.s, &mem[3].w2.s}, &w2s))) return rc;
   if ((rc = merge(ctx, {&pe.w3.s, &mem[0].w3.s, &mem[1].w3.s, &mem[2].w3.s, &mem[3].w3.s}, &w3s))) return rc;
   if ((rc = merge(ctx, {&pe.w3s.s, &mem[0].w3s.s, &mem[1].w3s.s, &mem[2].w3s.s, &mem[3].w3s.s}, &w4))) return rc;
   const size_t n = w1.num_proofs.size();
-  rc = sat_prove(ctx, vars_gens, perm_root->dev, n, sh.perm_size, w1.num_proofs, num_ios, std::vector<size_t>(n, num_ios),
-                 {wpart(w0.s), wpart(w1), wpart(w2s), wpart(w3s), wpart(w4)}, &Wt, transcript, tape_h, &so);
+  *c = SatCall{"perm_root", perm_root->dev, n, sh.perm_size, num_ios, w1.num_proofs, std::vector<size_t>(n, num_ios), im,
+               {wpart(w0.s), wpart(w1), wpart(w2s), wpart(w3s), wpart(w4)}};
+  return 0;
+}
+int SnarkProver::prove_perm_root() {
+  SatCall c;
+  int rc = perm_root_call(&c);
+  if (!rc) rc = sat_stage(c);
   if (rc) return rc;
   w.out.insert(w.out.end(), so.bytes.begin(), so.bytes.end());
   FqV e;
@@ -1054,7 +1102,8 @@ int SnarkProver::prove_perm_root() {
 
 // PERM_PRODUCT_PROOF (lib.rs:2534-2609): every w3 polynomial's product entry opened in one batched proof; the block
 // w3 polynomials appear once per chain they carry (exec, then physical, then virtual memory)
-int SnarkProver::prove_perm_product() {
+int SnarkProver::perm_prod_list(SecInfo* pw3_out, std::vector<size_t>* im_out, FqV* prod_out,
+                                std::vector<FqV>* r_list_out) {
   std::vector<const SecInfo*> comps = {&pe.w3.s, &mem[0].w3.s, &mem[1].w3.s, &mem[2].w3.s, &mem[3].w3.s, &bw.w3.s};
   if (a.max_block_num_phy_ops > 0) comps.push_back(&bw.w3.s);
   if (a.max_block_num_vir_ops > 0) comps.push_back(&bw.w3.s);
@@ -1078,8 +1127,102 @@ int SnarkProver::prove_perm_product() {
       r_list.push_back({fq_one(), fq_zero()});
     }
   }
+  *pw3_out = std::move(pw3);
+  *im_out = std::move(im);
+  *prod_out = std::move(prod);
+  *r_list_out = std::move(r_list);
+  return 0;
+}
+int SnarkProver::prove_perm_product() {
+  SecInfo pw3;
+  std::vector<size_t> im;
+  FqV prod;
+  std::vector<FqV> r_list;
+  int rc = perm_prod_list(&pw3, &im, &prod, &r_list);
+  if (rc) return rc;
   w.fqs(prod);
   return prove_batched_instances(ctx, g, pw3.poly, r_list, prod, t, tape, w);
+}
+
+// spg_snark_check: SNARK::prove's witness generation (through the input commitments, which fix tau and r as a prove
+// would draw them), then everything a verifier would reject a bad witness for, evaluated without proving: the three
+// R1CS instances' satisfiability (R1CSInstance::is_sat, src/r1csinstance.rs:322-357, on the device), the permutation
+// products SNARK::verify multiplies (verify.hip check_perm_product), and the IO proof's opened points. All checks
+// run; the report's `first` is the earliest failure in the verifier's order.
+int SnarkProver::check(spg_snark_report* out) {
+  memset(out, 0, sizeof(*out));
+  out->io_point = -1;
+  out->first = -1;
+  int rc;
+  t.protocol("Spartan SNARK proof");
+  if ((rc = append_instance())) return rc;
+  if ((rc = launch_early_commits())) return rc;
+  draw_challenges();
+  gen_perm_exec();
+  gen_block();
+  gen_mem(INIT_PHY_MEM_WIDTH, iphy.rows[0], false, &mem[0]);
+  gen_mem(INIT_VIR_MEM_WIDTH, ivir.rows[0], false, &mem[1]);
+  gen_mem(PHY_MEM_WIDTH, aphy.rows[0], false, &mem[2]);
+  gen_mem(VIR_MEM_WIDTH, avir.rows[0], true, &mem[3]);
+  if ((rc = queue_input_commits())) return rc;
+  std::string first_msg;
+  auto failed = [&](int code, const std::string& msg) {
+    if (out->first < 0) out->first = code, first_msg = msg;
+  };
+  int (SnarkProver::*const calls[3])(SatCall*) = {&SnarkProver::block_call, &SnarkProver::pairwise_call,
+                                                  &SnarkProver::perm_root_call};
+  for (int k = 0; k < 3; k++) {
+    SatCall c;
+    if ((rc = (this->*calls[k])(&c))) return rc;
+    if ((rc = witness_from_parts(ctx, c.parts, &Wt))) return rc;
+    spg_sat_report& r = out->sat[k];
+    if ((rc = spg_r1cs_sat_check(ctx, c.inst, c.P, c.max_np, c.num_proofs.data(), c.max_ni, c.num_inputs.data(), Wt, &r)))
+      return rc;
+    if (!r.violations) continue;
+    out->component[k] = r.p < c.from.size() ? c.from[r.p] : 0;
+    failed(k, std::string(c.stage) + ": " + sat_message(r) + (k == 0 ? "; block " + std::to_string(out->component[k]) : ""));
+  }
+  {
+    SecInfo pw3;
+    std::vector<size_t> im;
+    FqV prod;
+    std::vector<FqV> r_list;
+    if ((rc = perm_prod_list(&pw3, &im, &prod, &r_list))) return rc;
+    // the products of check_perm_product (verify.hip): exec against blocks, each memory's ops against its list
+    Fq pe_ = fq_one(), pb = fq_one(), pmb = fq_one(), pma = fq_one(), vmb = fq_one(), vma = fq_one();
+    for (size_t i = 0; i < im.size(); i++) {
+      const Fq& x = prod[i];
+      switch (im[i]) {
+        case 0: pe_ = fq_mul(pe_, x); break;
+        case 1: pmb = fq_mul(pmb, x); break;
+        case 2: vmb = fq_mul(vmb, x); break;
+        case 3: pma = fq_mul(pma, x); break;
+        case 4: vma = fq_mul(vma, x); break;
+        case 5: pb = fq_mul(pb, x); break;
+        case 6:
+          if (a.max_block_num_phy_ops > 0) pmb = fq_mul(pmb, x);
+          else vmb = fq_mul(vmb, x);
+          break;
+        case 7: vmb = fq_mul(vmb, x); break;
+      }
+    }
+    static const char* const what[3] = {"execution / block permutation products", "physical memory permutation products",
+                                        "virtual memory permutation products"};
+    const bool differ[3] = {!fq_eq(pe_, pb), !fq_eq(pmb, pma), !fq_eq(vmb, vma)};
+    for (int k = 0; k < 3; k++) {
+      out->perm_products[k] = differ[k] ? 1 : 0;
+      if (differ[k]) failed(3 + k, what[k]);
+    }
+  }
+  {
+    const IoPoints io = io_points(a, sh.consis, W->liveness.data(), W->liveness.size(), W->input, W->output);
+    const FqV flat = pad_pow2(flatten(W->exec));
+    for (size_t k = 0; k < io.idx.size() && out->io_point < 0; k++)
+      if (io.idx[k] >= flat.size() || !fq_eq(flat[io.idx[k]], io.Zr[k])) out->io_point = (int64_t)k;
+    if (out->io_point >= 0) failed(6, "IO proof: opened point " + std::to_string(out->io_point) + " differs from its public value");
+  }
+  if (out->first >= 0) set_err(ctx, SPG_E_VERIFY, first_msg);
+  return 0;
 }
 
 // SHIFT_PROOFS (lib.rs:2611-2668)
@@ -1169,11 +1312,34 @@ int SnarkProver::finish(uint8_t* proof, size_t proof_cap, size_t* proof_len) {
 
 }  // namespace
 
+static int snark_witness_args(spg_ctx* ctx, spg_snark_comp* block, const spg_snark_wit* W);
+
+extern "C" int spg_snark_check(spg_ctx* ctx, spg_snark_comp* block, spg_snark_comp* pairwise, spg_snark_comp* perm_root,
+                               const spg_snark_wit* W, spg_r1cs_gens* vars_gens, spg_transcript* transcript,
+                               spg_snark_report* out) {
+  if (!ctx || !block || !pairwise || !perm_root || !W || !vars_gens || !transcript || !out) return SPG_E_ARG;
+  if (ctx->nranks > 1) return spg::set_err(ctx, SPG_E_ARG, "spg_snark_check: single-rank, as spg_snark_prove");
+  if (int rc = snark_witness_args(ctx, block, W)) return rc;
+  spg::HostPin pin;
+  spg_random_tape tape("snark_check", spg::fq_zero());  // no blind is drawn before the proofs begin
+  SnarkProver pr(ctx, block, pairwise, perm_root, W, vars_gens, transcript, &tape);
+  return spg::tr_status(ctx, transcript->t, pr.check(out));
+}
+
 static int spg_snark_prove_impl(spg_ctx* ctx, spg_snark_comp* block, spg_snark_comp* pairwise, spg_snark_comp* perm_root,
                                const spg_snark_wit* W, spg_r1cs_gens* vars_gens, spg_transcript* transcript,
                                spg_random_tape* tape_h, uint8_t* proof, size_t proof_cap, size_t* proof_len) {
   if (!ctx || !block || !pairwise || !perm_root || !W || !vars_gens || !transcript || !tape_h || !proof_len)
     return SPG_E_ARG;
+  if (int rc = snark_witness_args(ctx, block, W)) return rc;
+  SnarkProver pr(ctx, block, pairwise, perm_root, W, vars_gens, transcript, tape_h);
+  const int rc = pr.run();
+  if (rc == SPG_E_UNSAT) *proof_len = 0;  // check mode: no proof was written
+  return rc ? rc : pr.finish(proof, proof_cap, proof_len);
+}
+
+// the argument checks of spg_snark_prove and spg_snark_check, before any launch
+static int snark_witness_args(spg_ctx* ctx, spg_snark_comp* block, const spg_snark_wit* W) {
   if (2 * W->a.num_inputs_unpadded > W->a.num_ios) return set_err(ctx, SPG_E_ARG, "num_ios < 2 * num_inputs_unpadded");
   {  // before any launch: a block whose rows or matrices reach beyond its witness width (snark_shape.hpp)
     const size_t Bb = W->a.block_num_instances_bound;
@@ -1189,9 +1355,7 @@ static int spg_snark_prove_impl(spg_ctx* ctx, spg_snark_comp* block, spg_snark_c
                               W->a.num_inputs_unpadded, W->a.num_vars, block->cols_needed.data()) >= 0)
       return set_err(ctx, SPG_E_ARG, "a block names a column beyond its block_num_vars");
   }
-  SnarkProver pr(ctx, block, pairwise, perm_root, W, vars_gens, transcript, tape_h);
-  const int rc = pr.run();
-  return rc ? rc : pr.finish(proof, proof_cap, proof_len);
+  return SPG_OK;
 }
 
 extern "C" int spg_snark_prove(spg_ctx* ctx, spg_snark_comp* block, spg_snark_comp* pairwise, spg_snark_comp* perm_root,

@@ -11,6 +11,7 @@ There is no CPU fallback: constructing a Context without a gfx950 device raises.
 The C signature of every spg_* function is read from include/spg.h when the library is loaded (_signatures, _bind):
 callers pass plain Python ints for size_t / int / long arguments, and a wrong type stops in ctypes.
 """
+import collections
 import ctypes
 import os
 import re
@@ -22,9 +23,10 @@ LIB_PATH = os.environ.get("SPG_LIB") or os.path.join(_HERE, "lib", "libspg.so")
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "spg.h")
 
 SPG_ERRORS = {-1: "SPG_E_ARG", -2: "SPG_E_NOMEM", -3: "SPG_E_HIP", -4: "SPG_E_POINT", -5: "SPG_E_NODEVICE",
-              -6: "SPG_E_VERIFY", -7: "SPG_E_CALLBACK"}
+              -6: "SPG_E_VERIFY", -7: "SPG_E_CALLBACK", -8: "SPG_E_UNSAT"}
 SPG_E_VERIFY = -6
 SPG_E_ARG = -1
+SPG_E_UNSAT = -8
 
 # by-value C types of the header; every parameter with a `*` or `[` is a pointer (c_void_p: handles, byref(), ctypes
 # arrays, None, _p(numpy) and CFUNCTYPE thunks all pass), as are the callback typedefs
@@ -228,6 +230,11 @@ class Context:
         """spg_set_verify_device: this context's verifiers collect their sigma-protocol group equations and check them
         in one spg_eqs_check launch at the end of the call (same verdicts and error texts; off by default)"""
         self.call("spg_set_verify_device", 1 if on else 0)
+
+    def set_check_sat(self, on=True):
+        """spg_set_check_sat: spg_r1cs_prove (and through it spg_snark_prove) checks Az * Bz == Cz on the device right
+        after its multiply_vec_block and refuses an unsatisfying witness with SPG_E_UNSAT, naming the row"""
+        self.call("spg_set_check_sat", 1 if on else 0)
 
     def eqs_last_counts(self):
         """spg_eqs_last_counts: (equations, terms) of this context's most recent spg_eqs_check launch, a deferred
@@ -1072,6 +1079,70 @@ def r1cs_prove(ctx, gens, inst, witness, num_instances, max_num_proofs, num_proo
         out.append(ch[o:o + L].copy())
         o += L
     return buf[: ln.value].tobytes(), out
+
+
+# ---- witness satisfiability (spg_pqx_sat_check, spg_r1cs_sat_check, spg_snark_check, spg_set_check_sat) ----
+class CSatReport(ctypes.Structure):  # spg_sat_report
+    _fields_ = [("rows", ctypes.c_uint64), ("violations", ctypes.c_uint64), ("p", ctypes.c_uint64),
+                ("q", ctypes.c_uint64), ("row", ctypes.c_uint64), ("az", ctypes.c_uint64 * 4),
+                ("bz", ctypes.c_uint64 * 4), ("cz", ctypes.c_uint64 * 4)]
+
+
+class CSnarkReport(ctypes.Structure):  # spg_snark_report
+    _fields_ = [("sat", CSatReport * 3), ("component", ctypes.c_uint64 * 3), ("perm_products", ctypes.c_uint64 * 3),
+                ("io_point", ctypes.c_int64), ("first", ctypes.c_int64)]
+
+
+# spg_snark_report: the stages (indices of sat / component), the values of `first`, and the component numbers
+SAT_BLOCK, SAT_PAIRWISE, SAT_PERM_ROOT = 0, 1, 2
+FIRST_NONE, FIRST_PERM_EXEC, FIRST_PERM_PHY, FIRST_PERM_VIR, FIRST_IO = -1, 3, 4, 5, 6
+PERM_EXEC, PERM_PHY, PERM_VIR = 0, 1, 2  # perm_products
+PAIRWISE_CONSIS, PAIRWISE_PHY, PAIRWISE_VIR = 0, 1, 2
+PERM_ROOT_EXEC, PERM_ROOT_INIT_PHY, PERM_ROOT_INIT_VIR, PERM_ROOT_PHY, PERM_ROOT_VIR = 0, 1, 2, 3, 4
+SAT_STAGES = ("block", "pairwise", "perm_root")
+
+_Q = (1 << 252) + 27742317777372353535851937790883648493
+_RINV = pow(1 << 256, -1, _Q)
+
+SatReport = collections.namedtuple("SatReport", "rows violations p q row az bz cz")
+SnarkReport = collections.namedtuple("SnarkReport", "sat component perm_products io_point first")
+
+
+def _sat_report(c):
+    """spg_sat_report with Python integers; az, bz, cz out of Montgomery form (None when nothing is violated)"""
+    val = lambda limbs: sum(int(limbs[i]) << (64 * i) for i in range(4)) * _RINV % _Q
+    if not c.violations:
+        return SatReport(int(c.rows), 0, None, None, None, None, None, None)
+    return SatReport(int(c.rows), int(c.violations), int(c.p), int(c.q), int(c.row), val(c.az), val(c.bz), val(c.cz))
+
+
+def pqx_sat_check(ctx, Az, Bz, Cz):
+    """spg_pqx_sat_check: Az[i] * Bz[i] == Cz[i] over three tables as r1cs_multiply_vec_block returns them"""
+    rep = CSatReport()
+    ctx.call("spg_pqx_sat_check", Az.handle, Bz.handle, Cz.handle, ctypes.byref(rep))
+    return _sat_report(rep)
+
+
+def r1cs_sat_check(ctx, inst, witness, num_instances, max_num_proofs, num_proofs, max_num_inputs, num_inputs):
+    """spg_r1cs_sat_check (R1CSInstance::is_sat over every execution of every instance): the shape and witness
+    arguments of r1cs_prove; a collective under set_comm"""
+    rep = CSatReport()
+    npf = (ctypes.c_size_t * num_instances)(*num_proofs)
+    nin = (ctypes.c_size_t * num_instances)(*num_inputs)
+    ctx.call("spg_r1cs_sat_check", inst.handle, num_instances, max_num_proofs, npf, max_num_inputs, nin,
+             witness.handle, ctypes.byref(rep))
+    return _sat_report(rep)
+
+
+def snark_check(ctx, block, pairwise, perm_root, witness, vars_gens, transcript):
+    """spg_snark_check: everything a verifier would reject a bad witness for, without proving. `transcript` is a
+    throwaway in the state a prove would start from. -> (SnarkReport, spg_last_error's text for the first failure)"""
+    rep = CSnarkReport()
+    ctx.call("spg_snark_check", block.handle, pairwise.handle, perm_root.handle, witness.handle, vars_gens.handle,
+             transcript.handle, ctypes.byref(rep))
+    out = SnarkReport(tuple(_sat_report(r) for r in rep.sat), tuple(int(x) for x in rep.component),
+                      tuple(int(x) for x in rep.perm_products), int(rep.io_point), int(rep.first))
+    return out, (lib().spg_last_error(ctx.handle).decode() if out.first >= 0 else "")
 
 
 class CWitnessComm(ctypes.Structure):
