@@ -41,6 +41,64 @@ struct Ser {
   void pts(const std::vector<CPt>& v) { u64(v.size()); for (auto& p : v) pt(p); }
 };
 
+// ---- bincode reader ----
+// Every read and every Vec length is checked against the bytes that remain before anything is allocated; a short
+// buffer, an over-long length or (end()) trailing bytes throw Malformed. Points stay as their 32 bytes (the verifier
+// decompresses them where the reference does) and scalar limbs are taken as they are (Scalar([u64; 4]) has no range
+// check, src/scalar/ristretto255.rs:198).
+struct Malformed {};
+struct De {
+  const uint8_t* p;
+  size_t n, o = 0;
+  De(const uint8_t* p_, size_t n_) : p(p_), n(n_) {}
+  void need(size_t k) const { if (k > n - o) throw Malformed(); }
+  uint64_t u64() {
+    need(8);
+    uint64_t x = 0;
+    for (int i = 0; i < 8; i++) x |= (uint64_t)p[o + i] << (8 * i);
+    o += 8;
+    return x;
+  }
+  // a Vec's length; every item takes at least `item_min` (> 0) bytes
+  size_t len(size_t item_min) {
+    uint64_t k = u64();
+    if (k > (n - o) / item_min) throw Malformed();
+    return (size_t)k;
+  }
+  Fq sc() { Fq s; for (int i = 0; i < 4; i++) s.v[i] = u64(); return s; }
+  CPt pt() {
+    need(32);
+    CPt c;
+    memcpy(c.v, p + o, 32);
+    o += 32;
+    return c;
+  }
+  FqVec scs() {
+    size_t k = len(32);
+    FqVec v;
+    v.reserve(k);
+    for (size_t i = 0; i < k; i++) v.push_back(sc());
+    return v;
+  }
+  std::vector<CPt> pts() {
+    size_t k = len(32);
+    std::vector<CPt> v;
+    v.reserve(k);
+    for (size_t i = 0; i < k; i++) v.push_back(pt());
+    return v;
+  }
+  // Vec<T> of structs with a static T::de(De&) and T::MIN_BYTES
+  template <class T>
+  std::vector<T> vec() {
+    size_t k = len(T::MIN_BYTES);
+    std::vector<T> v;
+    v.reserve(k);
+    for (size_t i = 0; i < k; i++) v.push_back(T::de(*this));
+    return v;
+  }
+  void end() const { if (o != n) throw Malformed(); }
+};
+
 // ---- commitments (src/commitments.rs:69-92) ----
 static inline Ge msm_pts(const FqVec& s, const std::vector<Ge>& P) { return vartime_msm(s.data(), P.data(), s.size()); }
 // Scalar::commit : gens.n must be 1
@@ -90,6 +148,7 @@ struct KnowledgeProof {
   CPt alpha;
   Fq z1, z2;
   void ser(Ser& s) const { s.pt(alpha); s.sc(z1); s.sc(z2); }
+  static KnowledgeProof de(De& d) { KnowledgeProof p; p.alpha = d.pt(); p.z1 = d.sc(); p.z2 = d.sc(); return p; }
   static KnowledgeProof prove(const Gens& g, Transcript& t, RandomTape& tape, const Fq& x, const Fq& r, CPt* C) {
     t.append_protocol_name("knowledge proof");
     Fq t1 = tape.random_scalar("t1"), t2 = tape.random_scalar("t2");
@@ -121,6 +180,7 @@ struct EqualityProof {
   CPt alpha;
   Fq z;
   void ser(Ser& s) const { s.pt(alpha); s.sc(z); }
+  static EqualityProof de(De& d) { EqualityProof p; p.alpha = d.pt(); p.z = d.sc(); return p; }
   static EqualityProof prove(const Gens& g, Transcript& t, RandomTape& tape, const Fq& v1, const Fq& s1, const Fq& v2,
                              const Fq& s2, CPt* C1, CPt* C2) {
     t.append_protocol_name("equality proof");
@@ -161,6 +221,12 @@ struct ProductProof {
   void ser(Ser& s) const {
     s.pt(alpha); s.pt(beta); s.pt(delta);
     for (int i = 0; i < 5; i++) s.sc(z[i]);
+  }
+  static ProductProof de(De& d) {
+    ProductProof p;
+    p.alpha = d.pt(); p.beta = d.pt(); p.delta = d.pt();
+    for (int i = 0; i < 5; i++) p.z[i] = d.sc();
+    return p;
   }
   static ProductProof prove(const Gens& g, Transcript& t, RandomTape& tape, const Fq& x, const Fq& rX, const Fq& y,
                             const Fq& rY, const Fq& zz, const Fq& rZ, CPt* X, CPt* Y, CPt* Z) {
@@ -212,6 +278,12 @@ struct DotProductProof {
   FqVec z;
   Fq z_delta, z_beta;
   void ser(Ser& s) const { s.pt(delta); s.pt(beta); s.scs(z); s.sc(z_delta); s.sc(z_beta); }
+  static const size_t MIN_BYTES = 32 + 32 + 8 + 32 + 32;
+  static DotProductProof de(De& d) {
+    DotProductProof p;
+    p.delta = d.pt(); p.beta = d.pt(); p.z = d.scs(); p.z_delta = d.sc(); p.z_beta = d.sc();
+    return p;
+  }
   static DotProductProof prove(const Gens& g1, const Gens& gn, Transcript& t, RandomTape& tape, const FqVec& x,
                                const Fq& blind_x, const FqVec& a, const Fq& y, const Fq& blind_y, CPt* Cx, CPt* Cy) {
     t.append_protocol_name("dot product proof");
@@ -251,6 +323,7 @@ struct DotProductProof {
 struct BulletProof {
   std::vector<CPt> L_vec, R_vec;
   void ser(Ser& s) const { s.pts(L_vec); s.pts(R_vec); }
+  static BulletProof de(De& d) { BulletProof p; p.L_vec = d.pts(); p.R_vec = d.pts(); return p; }
   static BulletProof prove(Transcript& t, const Ge& Q, std::vector<Ge> G, const Ge& H, FqVec a, FqVec b,
                            const Fq& blind, const std::vector<std::pair<Fq, Fq>>& blinds, Ge* Gamma_hat, Fq* a0,
                            Fq* b0, Ge* g0, Fq* blind_fin_out) {
@@ -343,6 +416,13 @@ struct DotProductProofLog {
   CPt delta, beta;
   Fq z1, z2;
   void ser(Ser& s) const { bullet.ser(s); s.pt(delta); s.pt(beta); s.sc(z1); s.sc(z2); }
+  static const size_t MIN_BYTES = 8 + 8 + 4 * 32;
+  static DotProductProofLog de(De& d) {
+    DotProductProofLog p;
+    p.bullet = BulletProof::de(d);
+    p.delta = d.pt(); p.beta = d.pt(); p.z1 = d.sc(); p.z2 = d.sc();
+    return p;
+  }
   static DotProductProofLog prove(const DotGens& g, Transcript& t, RandomTape& tape, const FqVec& x,
                                   const Fq& blind_x, const FqVec& a, const Fq& y, const Fq& blind_y, CPt* Cx, CPt* Cy) {
     t.append_protocol_name("dot product proof (log)");

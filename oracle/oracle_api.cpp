@@ -692,6 +692,84 @@ int orc_snark_prove(const spg_snark_inputs* in_c, const spg_snark_instance* bloc
     return -2;
   }
 }
+// SNARK::verify of caller-supplied bytes: bincode(SNARK) read by De, then snark_verify on a fresh Transcript(label)
+// with the instances encoded and the generators derived as in orc_snark_prove. 0 = accepted, 1..16 = the failing
+// stage, ORC_MALFORMED for bytes De refuses (truncated, trailing, an over-long length) and ORC_DECOMPRESSION when a
+// point of the proof does not decompress where the verifier needs it. Touches no global but the thread_local timers:
+// callable from several threads at once.
+enum { ORC_MALFORMED = -3, ORC_DECOMPRESSION = -4 };
+namespace {
+struct SnarkVerifier {  // what SNARK::verify holds besides the proof; read-only once built
+  SnarkIn in;
+  SnarkInst block, pairwise, perm_root;
+  R1CSGens vg;
+  std::string label;
+  int verify(const uint8_t* proof, size_t len) const {
+    try {
+      De d(proof, len);
+      SNARKProof pf = SNARKProof::de(d);
+      Transcript tv(label.c_str());
+      return snark_verify(pf, in, block, pairwise, perm_root, vg, tv);
+    } catch (const Malformed&) {
+      return ORC_MALFORMED;
+    } catch (const std::string& e) {
+      return e == "DecompressionError" ? ORC_DECOMPRESSION : -2;
+    }
+  }
+};
+SnarkVerifier* snark_verifier_new(const spg_snark_inputs* in_c, const spg_snark_instance* block_c,
+                                  const spg_snark_instance* pairwise_c, const spg_snark_instance* perm_root_c,
+                                  const char* gens_label, size_t gens_num_vars, const char* label) {
+  SnarkVerifier* v = new SnarkVerifier();
+  v->in = snark_in_from_c(in_c);
+  v->block = snark_inst_from_c(block_c, true);
+  v->pairwise = snark_inst_from_c(pairwise_c, false);
+  v->perm_root = snark_inst_from_c(perm_root_c, false);
+  v->vg = R1CSGens::create(gens_label, gens_num_vars);
+  v->label = label;
+  return v;
+}
+}  // namespace
+// the same in two steps, for many verdicts on one program: the handle is never written after it is built, so any
+// number of threads may call orc_snark_verifier_verify on it at once
+void* orc_snark_verifier_new(const spg_snark_inputs* in_c, const spg_snark_instance* block_c,
+                             const spg_snark_instance* pairwise_c, const spg_snark_instance* perm_root_c,
+                             const char* gens_label, size_t gens_num_vars, const char* label) {
+  try {
+    return snark_verifier_new(in_c, block_c, pairwise_c, perm_root_c, gens_label, gens_num_vars, label);
+  } catch (const std::string& e) {
+    return nullptr;
+  }
+}
+int orc_snark_verifier_verify(const void* h, const uint8_t* proof, size_t len) {
+  return ((const SnarkVerifier*)h)->verify(proof, len);
+}
+void orc_snark_verifier_free(void* h) { delete (SnarkVerifier*)h; }
+int orc_snark_verify_bytes(const spg_snark_inputs* in_c, const spg_snark_instance* block_c,
+                           const spg_snark_instance* pairwise_c, const spg_snark_instance* perm_root_c,
+                           const char* gens_label, size_t gens_num_vars, const char* label, const uint8_t* proof,
+                           size_t len) {
+  void* h = orc_snark_verifier_new(in_c, block_c, pairwise_c, perm_root_c, gens_label, gens_num_vars, label);
+  if (!h) return -2;
+  const int rc = orc_snark_verifier_verify(h, proof, len);
+  orc_snark_verifier_free(h);
+  return rc;
+}
+// De then Ser of bincode(SNARK): 0 and the bytes, -1 when they exceed cap, ORC_MALFORMED
+int orc_snark_proof_reserialize(const uint8_t* proof, size_t len, uint8_t* out, size_t cap, size_t* out_len) {
+  try {
+    De d(proof, len);
+    SNARKProof pf = SNARKProof::de(d);
+    Ser s;
+    pf.ser(s);
+    *out_len = s.b.size();
+    if (s.b.size() > cap) return -1;
+    memcpy(out, s.b.data(), s.b.size());
+    return 0;
+  } catch (const Malformed&) {
+    return ORC_MALFORMED;
+  }
+}
 double orc_snark_last_prove_us() { return g_snark_prove_us; }
 // the last snark_prove's phases: up to `max` (name[32], microseconds) pairs, returns their count
 int orc_snark_last_phases(char* names, double* us, int max) {

@@ -36,6 +36,8 @@ static inline PolyCommitment poly_commit(const DensePoly& poly, const DotGens& g
 struct PolyEvalProof {
   DotProductProofLog proof;
   void ser(Ser& s) const { proof.ser(s); }
+  static const size_t MIN_BYTES = DotProductProofLog::MIN_BYTES;
+  static PolyEvalProof de(De& d) { PolyEvalProof p; p.proof = DotProductProofLog::de(d); return p; }
 
   // dense_mlpoly.rs:437-490 (blinds = None, blind_Zr = None)
   static PolyEvalProof prove(const DensePoly& poly, const FqVec& r, const Fq& Zr, const DotGens& g, Transcript& t,
@@ -457,5 +459,6 @@ static inline void ser_proofs(Ser& s, const std::vector<PolyEvalProof>& v) {
   s.u64(v.size());
   for (auto& p : v) p.ser(s);
 }
+static inline std::vector<PolyEvalProof> de_proofs(De& d) { return d.vec<PolyEvalProof>(); }
 
 }  // namespace orc

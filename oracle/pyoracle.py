@@ -504,3 +504,62 @@ def snark_last_verify_us():
     f = lib().orc_snark_last_verify_us
     f.restype = ctypes.c_double
     return f()
+
+
+MALFORMED, DECOMPRESSION = -3, -4  # orc_snark_verify_bytes: bytes De refuses / a point that does not decompress
+
+
+def snark_verify_bytes(wl, proof, gens_label=b"gens_r1cs_sat", gens_num_vars=1 << 24, label=b"snark_test"):
+    """the oracle's SNARK::verify on caller-supplied bincode(SNARK) bytes: 0 = accepted, 1..16 = the failing stage,
+    MALFORMED, DECOMPRESSION. `wl` is a workload.SnarkWorkload or its SnarkViews (build the views once to call this
+    from several threads: the call releases the GIL and the oracle side shares nothing between calls)."""
+    import workload
+
+    v = wl if isinstance(wl, workload.SnarkViews) else workload.SnarkViews(wl)
+    f = lib().orc_snark_verify_bytes
+    f.restype = ctypes.c_int
+    rc = f(ctypes.byref(v.inputs), ctypes.byref(v.block), ctypes.byref(v.pairwise), ctypes.byref(v.perm_root),
+           ctypes.c_char_p(gens_label), ctypes.c_size_t(gens_num_vars), ctypes.c_char_p(label),
+           ctypes.c_char_p(bytes(proof)), ctypes.c_size_t(len(proof)))
+    assert rc >= 0 or rc in (MALFORMED, DECOMPRESSION), rc
+    return rc
+
+
+class SnarkVerifier:
+    """the oracle's verifier of one program, set up once (instances encoded, generators derived): verify(proof) is
+    snark_verify_bytes without the setup, and may run on several threads at once"""
+
+    def __init__(self, wl, gens_label=b"gens_r1cs_sat", gens_num_vars=1 << 24, label=b"snark_test"):
+        import workload
+
+        v = wl if isinstance(wl, workload.SnarkViews) else workload.SnarkViews(wl)
+        f = lib().orc_snark_verifier_new
+        f.restype = ctypes.c_void_p
+        self.h = f(ctypes.byref(v.inputs), ctypes.byref(v.block), ctypes.byref(v.pairwise), ctypes.byref(v.perm_root),
+                   ctypes.c_char_p(gens_label), ctypes.c_size_t(gens_num_vars), ctypes.c_char_p(label))
+        assert self.h
+
+    def verify(self, proof):
+        f = lib().orc_snark_verifier_verify
+        rc = f(ctypes.c_void_p(self.h), ctypes.c_char_p(bytes(proof)), ctypes.c_size_t(len(proof)))
+        assert rc >= 0 or rc in (MALFORMED, DECOMPRESSION), rc
+        return rc
+
+    def __del__(self):
+        if getattr(self, "h", None):
+            lib().orc_snark_verifier_free(ctypes.c_void_p(self.h))
+            self.h = None
+
+
+def snark_proof_reserialize(proof):
+    """bincode(SNARK) read by the oracle's De and written again by Ser; None for malformed bytes"""
+    out = np.zeros(len(proof) + 64, dtype=np.uint8)
+    ln = ctypes.c_size_t(0)
+    f = lib().orc_snark_proof_reserialize
+    f.restype = ctypes.c_int
+    rc = f(ctypes.c_char_p(bytes(proof)), ctypes.c_size_t(len(proof)), _p(out), ctypes.c_size_t(out.size),
+           ctypes.byref(ln))
+    if rc == MALFORMED:
+        return None
+    assert rc == 0, rc
+    return out[: ln.value].tobytes()

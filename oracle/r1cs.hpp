@@ -230,6 +230,22 @@ struct R1CSProof {
     ser_proofs(s, proof_eval_vars_at_ry_list);
     eq2.ser(s);
   }
+  static R1CSProof de(De& d) {
+    R1CSProof p;
+    p.sc1 = ZKSumcheckProof::de(d);
+    for (int i = 0; i < 4; i++) p.claims_phase2[i] = d.pt();
+    p.pok_Cz = KnowledgeProof::de(d);
+    p.proof_prod = ProductProof::de(d);
+    p.eq1 = EqualityProof::de(d);
+    p.sc2 = ZKSumcheckProof::de(d);
+    size_t k = d.len(8);
+    p.comm_vars_at_ry_list.reserve(k);
+    for (size_t i = 0; i < k; i++) p.comm_vars_at_ry_list.push_back(d.pts());
+    p.comm_vars_at_ry = d.pt();
+    p.proof_eval_vars_at_ry_list = de_proofs(d);
+    p.eq2 = EqualityProof::de(d);
+    return p;
+  }
 
   static FqVec prefix_list(size_t nws, const FqVec& rw) {
     Fq one = fq_one();

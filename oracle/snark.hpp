@@ -118,6 +118,7 @@ static inline R1CSComm r1cs_commit(const R1CSInstance& inst, const R1CSCommGens&
 struct IOProofs {
   std::vector<PolyEvalProof> proofs;
   void ser(Ser& s) const { ser_proofs(s, proofs); }
+  static IOProofs de(De& d) { IOProofs p; p.proofs = de_proofs(d); return p; }
 };
 struct ShiftProofs {
   PolyEvalProof proof;
@@ -129,6 +130,16 @@ struct ShiftProofs {
     s.pts(C_shifted_evals);
     s.u64(openings.size());
     for (auto& o : openings) s.pts(o);
+  }
+  static ShiftProofs de(De& d) {
+    ShiftProofs p;
+    p.proof = PolyEvalProof::de(d);
+    p.C_orig_evals = d.pts();
+    p.C_shifted_evals = d.pts();
+    size_t k = d.len(8);
+    p.openings.reserve(k);
+    for (size_t i = 0; i < k; i++) p.openings.push_back(d.pts());
+    return p;
   }
 };
 
@@ -307,6 +318,46 @@ struct SNARKProof {  // lib.rs:701-756
     ser_proofs(s, proof_eval_perm_poly_prod_list);
     shift_proof.ser(s);
     io_proof.ser(s);
+  }
+  // the whole of `d` is one bincode(SNARK): trailing bytes are Malformed as well
+  static SNARKProof de(De& d) {
+    SNARKProof p;
+    auto comms = [&](std::vector<PolyCommitment>& v) {
+      size_t k = d.len(8);
+      v.reserve(k);
+      for (size_t i = 0; i < k; i++) v.push_back(d.pts());
+    };
+    comms(p.block_comm_vars_list);
+    comms(p.exec_comm_inputs);
+    for (auto* c : {&p.addr_comm_phy_mems, &p.addr_comm_phy_mems_shifted, &p.addr_comm_vir_mems,
+                    &p.addr_comm_vir_mems_shifted, &p.addr_comm_ts_bits, &p.perm_exec_comm_w2_list,
+                    &p.perm_exec_comm_w3_list, &p.perm_exec_comm_w3_shifted})
+      *c = d.pts();
+    comms(p.block_comm_w2_list);
+    comms(p.block_comm_w3_list);
+    comms(p.block_comm_w3_list_shifted);
+    for (auto* c : {&p.init_phy_mem_comm_w2, &p.init_phy_mem_comm_w3, &p.init_phy_mem_comm_w3_shifted,
+                    &p.init_vir_mem_comm_w2, &p.init_vir_mem_comm_w3, &p.init_vir_mem_comm_w3_shifted,
+                    &p.phy_mem_addr_comm_w2, &p.phy_mem_addr_comm_w3, &p.phy_mem_addr_comm_w3_shifted,
+                    &p.vir_mem_addr_comm_w2, &p.vir_mem_addr_comm_w3, &p.vir_mem_addr_comm_w3_shifted})
+      *c = d.pts();
+    p.block_r1cs_sat_proof = R1CSProof::de(d);
+    for (int i = 0; i < 3; i++) p.block_inst_evals_bound_rp[i] = d.sc();
+    p.block_inst_evals_list = d.scs();
+    p.block_r1cs_eval_proof_list = d.vec<SparkEvalProof>();
+    p.pairwise_check_r1cs_sat_proof = R1CSProof::de(d);
+    for (int i = 0; i < 3; i++) p.pairwise_check_inst_evals_bound_rp[i] = d.sc();
+    p.pairwise_check_inst_evals_list = d.scs();
+    p.pairwise_check_r1cs_eval_proof = SparkEvalProof::de(d);
+    p.perm_root_r1cs_sat_proof = R1CSProof::de(d);
+    for (int i = 0; i < 3; i++) p.perm_root_inst_evals[i] = d.sc();
+    p.perm_root_r1cs_eval_proof = SparkEvalProof::de(d);
+    p.perm_poly_poly_list = d.scs();
+    p.proof_eval_perm_poly_prod_list = de_proofs(d);
+    p.shift_proof = ShiftProofs::de(d);
+    p.io_proof = IOProofs::de(d);
+    d.end();
+    return p;
   }
 };
 
@@ -1106,6 +1157,8 @@ static inline int snark_verify(const SNARKProof& pf, const SnarkIn& in, const Sn
   append_polycomm(t, "poly_commitment", pf.perm_exec_comm_w3_shifted);
   if (pf.block_comm_w2_list.size() != P || pf.block_comm_w3_list.size() != P || pf.block_comm_vars_list.size() != P)
     return 1;
+  // (a proof read from bytes may hold any list lengths; the reference indexes these and panics)
+  if (pf.block_comm_w3_list_shifted.size() != P || pf.exec_comm_inputs.empty()) return 1;
   for (auto& c : pf.block_comm_w2_list) append_polycomm(t, "poly_commitment", c);
   for (size_t p = 0; p < P; p++) {
     append_polycomm(t, "poly_commitment", pf.block_comm_w3_list[p]);

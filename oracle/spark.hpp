@@ -67,6 +67,14 @@ struct LayerProofBatched {
     s.scs(claims_prod_left);
     s.scs(claims_prod_right);
   }
+  static const size_t MIN_BYTES = 3 * 8;
+  static LayerProofBatched de(De& d) {
+    LayerProofBatched p;
+    p.proof = SumcheckProof::de(d);
+    p.claims_prod_left = d.scs();
+    p.claims_prod_right = d.scs();
+    return p;
+  }
 };
 
 struct ProductCircuitEvalProofBatched {
@@ -76,6 +84,12 @@ struct ProductCircuitEvalProofBatched {
     s.u64(proof.size());
     for (auto& p : proof) p.ser(s);
     for (int i = 0; i < 3; i++) s.scs(claims_dotp[i]);
+  }
+  static ProductCircuitEvalProofBatched de(De& d) {
+    ProductCircuitEvalProofBatched p;
+    p.proof = d.vec<LayerProofBatched>();
+    for (int i = 0; i < 3; i++) p.claims_dotp[i] = d.scs();
+    return p;
   }
 
   // product_tree.rs:271-396
@@ -363,6 +377,17 @@ struct HashLayerProof {
     proof_mem.ser(s);
     proof_derefs.ser(s);  // DerefsEvalProof { proof_derefs: PolyEvalProof }
   }
+  static HashLayerProof de(De& d) {
+    HashLayerProof p;
+    p.eval_row_addr = d.scs(); p.eval_row_read_ts = d.scs(); p.eval_row_audit_ts = d.sc();
+    p.eval_col_addr = d.scs(); p.eval_col_read_ts = d.scs(); p.eval_col_audit_ts = d.sc();
+    p.eval_val = d.scs();
+    p.eval_row_ops_val = d.scs(); p.eval_col_ops_val = d.scs();
+    p.proof_ops = PolyEvalProof::de(d);
+    p.proof_mem = PolyEvalProof::de(d);
+    p.proof_derefs = PolyEvalProof::de(d);
+    return p;
+  }
 };
 
 struct ProductLayerProof {
@@ -376,6 +401,15 @@ struct ProductLayerProof {
     proof_mem.ser(s);
     proof_ops.ser(s);
   }
+  static ProductLayerProof de(De& d) {
+    ProductLayerProof p;
+    p.row_init = d.sc(); p.row_read = d.scs(); p.row_write = d.scs(); p.row_audit = d.sc();
+    p.col_init = d.sc(); p.col_read = d.scs(); p.col_write = d.scs(); p.col_audit = d.sc();
+    p.dotp_left = d.scs(); p.dotp_right = d.scs();
+    p.proof_mem = ProductCircuitEvalProofBatched::de(d);
+    p.proof_ops = ProductCircuitEvalProofBatched::de(d);
+    return p;
+  }
 };
 
 struct SparkEvalProof {  // SparseMatPolyEvalProof
@@ -386,6 +420,15 @@ struct SparkEvalProof {  // SparseMatPolyEvalProof
     s.pts(comm_derefs);
     prod.ser(s);
     hash.ser(s);
+  }
+  // the smallest encoding: every Vec empty, the fixed scalars and the three PolyEvalProofs
+  static const size_t MIN_BYTES = 8 + (4 * 32 + 6 * 8 + 2 * (8 + 3 * 8)) + (7 * 8 + 2 * 32 + 3 * PolyEvalProof::MIN_BYTES);
+  static SparkEvalProof de(De& d) {
+    SparkEvalProof p;
+    p.comm_derefs = d.pts();
+    p.prod = ProductLayerProof::de(d);
+    p.hash = HashLayerProof::de(d);
+    return p;
   }
 };
 

@@ -19,6 +19,13 @@ struct SumcheckProof {  // SumcheckInstanceProof { compressed_polys: Vec<Compres
     s.u64(polys.size());
     for (auto& p : polys) s.scs(p);
   }
+  static SumcheckProof de(De& d) {
+    SumcheckProof p;
+    size_t k = d.len(8);
+    p.polys.reserve(k);
+    for (size_t i = 0; i < k; i++) p.polys.push_back(d.scs());
+    return p;
+  }
   // sumcheck.rs:37-71
   bool verify(Fq claim, size_t num_rounds, size_t degree_bound, Transcript& t, Fq* e_out, FqVec* r_out) const {
     Fq e = claim;
@@ -46,10 +53,18 @@ struct ZKSumcheckProof {
     s.u64(proofs.size());
     for (auto& p : proofs) p.ser(s);
   }
+  static ZKSumcheckProof de(De& d) {
+    ZKSumcheckProof p;
+    p.comm_polys = d.pts();
+    p.comm_evals = d.pts();
+    p.proofs = d.vec<DotProductProof>();
+    return p;
+  }
   // sumcheck.rs:94-189
   bool verify(const CPt& comm_claim, size_t num_rounds, size_t degree_bound, const Gens& g1, const Gens& gn,
               Transcript& t, CPt* final_comm, FqVec* r) const {
     if (comm_polys.size() != num_rounds || comm_evals.size() != num_rounds) return false;
+    if (proofs.size() != num_rounds) return false;  // (the reference indexes proofs[i] and panics)
     for (size_t i = 0; i < comm_polys.size(); i++) {
       t.append_point("comm_poly", comm_polys[i].v);
       Fq r_i = t.challenge_scalar("challenge_nextround");

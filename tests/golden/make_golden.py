@@ -230,6 +230,22 @@ def hetero_snark_fixture():
     return out
 
 
+def snark_mutations_fixture():
+    """{case: {proof_sha256, stages: {"<field>|<mutation>": stage}}}: the oracle verifier's stage (0 = accepted,
+    1..16 = the failing stage) on every well-formed alteration of the proof (tests/proof_mutations.py)"""
+    sys.path.insert(0, os.path.join(ROOT, "spartan-parallel_amd"))
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import proof_mutations as pm
+    from test_oracle_snark_mutations import oracle_sweep
+
+    out = {}
+    for case in sorted(pm.SWEEP):
+        proof, stages = oracle_sweep(O, case)
+        assert all(st >= 0 for st in stages.values()), case
+        out[case] = {"proof_sha256": hashlib.sha256(proof).hexdigest(), "stages": stages}
+    return out
+
+
 def structured_spark_fixture():
     """spark_proofs.json entries of the structured matrices (tests/sparse_cases.py), keyed structured_<case>"""
     sys.path.insert(0, os.path.join(ROOT, "spartan-parallel_amd"))
@@ -273,6 +289,9 @@ def main():
         json.dump(dict(snark_fixture(), **hetero_snark_fixture()), open(os.path.join(HERE, "snark_proofs.json"), "w"),
                   indent=1)
         return
+    if sys.argv[1:] == ["mutations"]:
+        json.dump(snark_mutations_fixture(), open(os.path.join(HERE, "snark_mutations.json"), "w"), indent=0)
+        return
     if sys.argv[1:] == ["r1cs"]:
         json.dump(dict(r1cs_fixture(), **structured_r1cs_fixture()), open(os.path.join(HERE, "r1cs_proofs.json"), "w"),
                   indent=1)
@@ -293,6 +312,7 @@ def main():
     w("r1cs_proofs.json", dict(r1cs_fixture(), **structured_r1cs_fixture()))
     w("spark_proofs.json", dict(spark_fixture(), **structured_spark_fixture()))
     w("snark_proofs.json", dict(snark_fixture(), **hetero_snark_fixture()))
+    json.dump(snark_mutations_fixture(), open(os.path.join(HERE, "snark_mutations.json"), "w"), indent=0)
     print("golden fixtures written to", HERE)
 
 
