@@ -1,6 +1,6 @@
 // Microbenchmark: the planned device bound of the dense polynomial commitment seam (csrc/pe_bound.hpp, k_pe_part +
 // k_pe_sum) against back-to-back passes of the single-polynomial pair every other prover path uses (k_bound_rows +
-// k_bound_sum of csrc/spark.hip, restated here with poly_eval_prove's launch shape).
+// k_bound_sum of csrc/hyrax.hip, restated here with poly_eval_prove's launch shape).
 //   points    num_vars = 24, D = 4 distinct left halves over one Z: one tiled pass (kt = 4), D passes with kt = 1 of the
 //             same kernels, D passes of the old pair
 //   instances 40 polynomials of num_vars = 16, 8 groups: one launch pair against 40 passes of the old pair
@@ -41,7 +41,7 @@ __global__ void k_fill(Fq* v, size_t n, uint32_t salt) {
   v[i] = a;
 }
 
-// csrc/spark.hip's pair
+// csrc/hyrax.hip's pair
 __global__ void __launch_bounds__(256) k_bound_rows(const Fq* __restrict__ Z, const Fq* __restrict__ L, size_t Ls,
                                                     size_t Rs, size_t chunk, Fq* __restrict__ part) {
   size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;

@@ -22,7 +22,7 @@ NAMES = {
     "k_phase2_fold2x": "sc_fold", "k_pqx_bound_q": "sc_fold_q_all",
     "k_bullet_comb": "msm_bullet_round", "k_comb_msm_parts": "msm_comb_parts", "k_comb_accum": "msm_comb",
     "k_phase1_eval": "sc_phase1_eval", "k_phase2_eval": "sc_phase2_eval", "k_pqx_fold": "sc_fold",
-    "k_spmv": "spmv_block", "k_z_fill": "z_fill", "k_abc": "eval_table_abc", "k_bound_part": "poly_bound",
+    "k_spmv": "spmv_block", "k_z_fill": "z_fill", "k_abc": "eval_table_abc", "k_bound_part_multi": "poly_bound",
     "k_fold_top": "fold_dense", "k_eq_table": "eq_table", "k_cubic_eval": "sc_cubic_eval",
     "k_final": "msm_final", "k_segments": "msm_segments", "k_items": "msm_bucket_items",
     "k_seg_dot": "spark_evaluate",

@@ -259,17 +259,15 @@ void* mapped_get(spg_ctx* c, size_t bytes, void** dev) {
   return c->mapped;
 }
 
-void* ws_get(spg_ctx* c, size_t slot, size_t bytes) {
-  std::vector<spg_ctx::Slot>& space = c->stream2 && c->stream == c->stream2 ? c->ws2 : c->ws;
-  if (space.size() <= slot) space.resize(slot + 1);
-  spg_ctx::Slot& s = space[slot];
+void* ws_get(spg_ctx* c, Ws slot, size_t bytes) {
+  spg_ctx::Slot& s = (c->stream2 && c->stream == c->stream2 ? c->ws2 : c->ws)[(size_t)slot];
 #ifdef SPG_CHECKED
   // two streams of one context must never share a slot while the previous owner may still read or write it (the
   // commit queue's side stream once did: the bench's repeated proves saw different bytes)
   if (s.p && s.owner && s.owner != c->stream && hipStreamQuery(s.owner) == hipErrorNotReady) {
-    char m[160];
-    snprintf(m, sizeof m, "workspace slot %zu taken by stream %p while stream %p still has work queued on it", slot,
-             (void*)c->stream, (void*)s.owner);
+    char m[200];
+    snprintf(m, sizeof m, "workspace slot %zu (%s) taken by stream %p while stream %p still has work queued on it",
+             (size_t)slot, ws_name(slot), (void*)c->stream, (void*)s.owner);
     fprintf(stderr, "[spg checked] %s\n", m);
     if (c->ws_violation.empty()) c->ws_violation = m;
     return nullptr;

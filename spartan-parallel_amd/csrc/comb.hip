@@ -380,7 +380,7 @@ int msm_comb(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const Fq* d_sca
   if (S > 1) {
     // the commit queue's second stream runs row commits while the main stream's block-witness commit is in flight:
     // ws_get gives each stream its own slot space
-    part = (Ext*)ws_get(ctx, 25, B * S * sizeof(Ext) + 64);
+    part = (Ext*)ws_get(ctx, Ws::CombPart, B * S * sizeof(Ext) + 64);
     if (!part) return set_err(ctx, SPG_E_NOMEM, "comb parts");
   }
   {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <array>
 #include <initializer_list>
 #include <map>
 #include <mutex>
@@ -12,6 +13,7 @@
 #include "../../include/spg.h"
 #include "curve.hpp"
 #include "msm_plan.hpp"
+#include "ws_slots.hpp"
 
 namespace spg {
 struct Uploader;  // api.hip
@@ -81,8 +83,8 @@ struct spg_ctx {
   spg_r1cs_witness* wt_cache = nullptr;
   double last_us = 0.0;
   std::string err;
-  // workspace slots: grown on demand, reused across calls (no allocation in steady state). Each stream has its own
-  // slot space (ws for `stream`, ws2 for `stream2`), so work queued on the two streams at once can never share a
+  // workspace slots (ws_slots.hpp): allocated on first use, reused across calls (no allocation in steady state). Each
+  // stream has its own slot space (ws for `stream`, ws2 for `stream2`), so work queued on the two streams at once can never share a
   // buffer by slot number. `owner` records the stream that took the slot; the checked build (make checked,
   // -DSPG_CHECKED) refuses a slot that another stream still has work queued on.
   struct Slot {
@@ -90,7 +92,7 @@ struct spg_ctx {
     size_t bytes = 0;
     hipStream_t owner = nullptr;
   };
-  std::vector<Slot> ws, ws2;
+  std::array<Slot, (size_t)spg::Ws::kCount> ws, ws2;
   std::string ws_violation;  // checked build: the first cross-stream slot conflict (prefixed to the error text)
   // the transcript of the prove in progress when it forwards to caller callbacks (TrCallbacks::failed): every
   // cross-rank exchange carries its failure as this rank's status, so all ranks fail together
@@ -171,8 +173,11 @@ bool failpoint(const spg_ctx* c, const char* site);
     if (!(cond)) return spg::set_err(ctx, SPG_E_ARG, msg); \
   } while (0)
 
+// workgroups of 256 threads over n elements
+inline unsigned nblk(size_t n) { return (unsigned)((n + 255) / 256); }
+
 // returns a device buffer of at least `bytes` for workspace slot `slot` (contents undefined)
-void* ws_get(spg_ctx* c, size_t slot, size_t bytes);
+void* ws_get(spg_ctx* c, Ws slot, size_t bytes);
 
 // page-locked host staging of at least `bytes` (contents undefined; valid until the next larger request,
 // which synchronises the stream before freeing the old buffer)

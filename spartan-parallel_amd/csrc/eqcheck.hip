@@ -194,9 +194,9 @@ int eqs_check_run(spg_ctx* ctx, const EqsView& v, const Niels* base, uint8_t* su
                o_r = o_f + al(4 * (E + 1)), o_k = o_r + al(4 * T), in_bytes = o_k + al(T);
   // results: status, the lowest rejected term, the encodings
   const size_t r_bad = al(E), r_sums = r_bad + 32, out_bytes = r_sums + (sums ? 32 * E : 0);
-  uint8_t* d_in = (uint8_t*)ws_get(ctx, 130, in_bytes + 64);
-  Ext* d_prod = (Ext*)ws_get(ctx, 131, T * sizeof(Ext) + al(T) + 64);
-  uint8_t* d_out = (uint8_t*)ws_get(ctx, 132, out_bytes + 64);
+  uint8_t* d_in = (uint8_t*)ws_get(ctx, Ws::EqsIn, in_bytes + 64);
+  Ext* d_prod = (Ext*)ws_get(ctx, Ws::EqsProd, T * sizeof(Ext) + al(T) + 64);
+  uint8_t* d_out = (uint8_t*)ws_get(ctx, Ws::EqsOut, out_bytes + 64);
   uint8_t* hp = (uint8_t*)pinned_get(ctx, in_bytes + out_bytes);
   if (!d_in || !d_prod || !d_out || !hp) return set_err(ctx, SPG_E_NOMEM, "spg_eqs_check workspace");
   uint8_t* h_out = hp + in_bytes;

@@ -1,6 +1,7 @@
 // spg — host build of the product's field / curve / transcript code (the same headers the HIP kernels
 // compile), exported for the CPU test suite so the arithmetic can be checked against the oracle
 // without a GPU. Not part of the proving path.
+#include <stdio.h>
 #include <string.h>
 
 #include <vector>
@@ -22,7 +23,9 @@
 #include "pe_plan.hpp"
 #include "satcheck.hpp"
 #include "snark_shape.hpp"
+#include "spark_shape.hpp"
 #include "vmsm.hpp"
+#include "ws_slots.hpp"
 
 using namespace spg;
 
@@ -596,6 +599,74 @@ size_t spgh_knob_table(char* buf, size_t cap) {
   if (cap) memcpy(buf, s.data(), std::min(cap, s.size()));
   return s.size();
 }
+// The workspace slot table (ws_slots.hpp) as text, one row per enumerator below kCount in order: ws_name, owner file,
+// what it holds, tab separated. Writes at most cap bytes and returns the length of the whole text.
+size_t spgh_ws_table(char* buf, size_t cap) {
+  std::string s;
+  for (size_t i = 0; i < (size_t)Ws::kCount; i++)
+    s += std::string(ws_name((Ws)i)) + "\t" + ws_table()[i].owner + "\t" + ws_table()[i].what + "\n";
+  if (cap) memcpy(buf, s.data(), std::min(cap, s.size()));
+  return s.size();
+}
+
+// ---- spark_shape.hpp
+// out[11] = (N, cells, nv_ops, nv_mem, nv_der, ops_len, mem_len, der_len, gens_n, ops_rows, mem_rows) of a batch of B
+// matrices of 2^nvx x 2^nvy with at most max_nnz entries each
+void spgh_spark_shape(size_t B, size_t max_nnz, size_t nvx, size_t nvy, size_t gens_nvx, size_t gens_nvy,
+                      size_t gens_nnz, size_t gens_batch, size_t* out) {
+  const size_t N = spark_num_ops(max_nnz), cells = spark_num_cells(nvx, nvy);
+  const SparkShape sp(B, N, cells, gens_nvx, gens_nvy, gens_nnz, gens_batch);
+  const size_t v[11] = {N,          cells,      sp.nv_ops,   sp.nv_mem,     sp.nv_der,    sp.ops_len,
+                        sp.mem_len, sp.der_len, sp.gens_n(), sp.ops_rows(), sp.mem_rows()};
+  memcpy(out, v, sizeof v);
+}
+// the refusals' messages ("" when accepted) into msg[cap]; return 1 when refused
+static int refusal(const char* why, char* msg, size_t cap) {
+  snprintf(msg, cap, "%s", why ? why : "");
+  return why != nullptr;
+}
+int spgh_spark_commit_refusal(size_t B, size_t N, size_t cells, size_t nvx, size_t nvy, size_t gens_nvx,
+                              size_t gens_nvy, size_t gens_nnz, size_t gens_batch, char* msg, size_t cap) {
+  return refusal(spark_commit_refusal(B, N, cells, nvx, nvy, gens_nvx, gens_nvy, gens_nnz, gens_batch), msg, cap);
+}
+int spgh_spark_comm_refusal(size_t B, size_t N, size_t cells, size_t ops_rows, size_t mem_rows, size_t gens_nvx,
+                            size_t gens_nvy, size_t gens_nnz, size_t gens_batch, char* msg, size_t cap) {
+  return refusal(spark_comm_refusal(B, N, cells, ops_rows, mem_rows, gens_nvx, gens_nvy, gens_nnz, gens_batch), msg, cap);
+}
+// v[2W]: the W gathered entries first; filled with the levels above them. prod: the circuit's evaluate()
+void spgh_tree_tops(uint64_t* v, size_t W, uint64_t* prod) {
+  std::vector<Fq> t(2 * W, fq_zero());
+  for (size_t i = 0; i < W; i++) t[i] = ldq(v + 4 * i);
+  stq(prod, tree_tops_host(t.data(), W));
+  for (size_t i = 0; i < 2 * W; i++) stq(v + 4 * i, t[i]);
+}
+
+// ---- the multi-round decoders of hostmath.hpp. ev: a pair's 15 or a triple's 64 posted values; r: r_j (and r_j+1);
+// out: (e0, e2, e3) of round j, then of round j + 1 (then of round j + 2)
+void spgh_pair_rounds(const uint64_t* ev, const uint64_t* r, uint64_t* out) {
+  Fq e[15], o[6];
+  for (int i = 0; i < 15; i++) e[i] = ldq(ev + 4 * i);
+  pair_round_j(e, o);
+  pair_round_j1(e, ldq(r), o + 3);
+  for (int i = 0; i < 6; i++) stq(out + 4 * i, o[i]);
+}
+void spgh_triple_rounds(const uint64_t* ev, const uint64_t* r, uint64_t* out) {
+  Fq e[64], o[9], L[4], M[4];
+  for (int i = 0; i < 64; i++) e[i] = ldq(ev + 4 * i);
+  lagrange4(ldq(r), L);
+  lagrange4(ldq(r + 4), M);
+  triple_round_j(e, o);
+  triple_round_j1(e, L, o + 3);
+  triple_round_j2(e, L, M, o + 6);
+  for (int i = 0; i < 9; i++) stq(out + 4 * i, o[i]);
+}
+// dims = 2: w[4] folded at r[2]; dims = 3: w[8] at r[3]
+void spgh_fold_corners(int dims, const uint64_t* w, const uint64_t* r, uint64_t* out) {
+  Fq c[8];
+  for (int i = 0; i < (1 << dims); i++) c[i] = ldq(w + 4 * i);
+  stq(out, dims == 2 ? fold_corners2(c, ldq(r), ldq(r + 4)) : fold_corners3(c, ldq(r), ldq(r + 4), ldq(r + 8)));
+}
+
 // The parse rule of one kind (knobs.hpp) on text (NULL: unset), with no environment involved. dflt[3], out[3]: the
 // COSTS triple, else entry 0 alone (bools as 0 / 1, GB in bytes, STR: 1 when the text itself came back). Returns 0, or
 // -1 for a kind the table does not know

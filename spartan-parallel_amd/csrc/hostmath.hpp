@@ -71,4 +71,78 @@ inline Fq uni_eval(const FqV& c, const Fq& r) {
 
 inline bool is_pow2(size_t x) { return x && !(x & (x - 1)); }
 
+// ---- several cubic sumcheck rounds from the grid one launch posts (k_phase1_pair / k_phase2_pair, k_layer_pair,
+// k_layer_triple): the round polynomials' (e0, e2, e3), each once the challenge before it is drawn, and the final
+// claims from a vector's posted corners.
+
+// the cubic Lagrange basis on the nodes 0..3 at r
+inline void lagrange4(const Fq& r, Fq L[4]) {
+  static const Fq inv2 = fq_inv(fq_from_u64(2)), inv6 = fq_inv(fq_from_u64(6));
+  const Fq a0 = r, a1 = fq_sub(r, fq_one()), a2 = fq_sub(a1, fq_one()), a3 = fq_sub(a2, fq_one());
+  const Fq a01 = fq_mul(a0, a1), a23 = fq_mul(a2, a3);
+  L[0] = fq_neg(fq_mul(fq_mul(a1, a23), inv6));
+  L[1] = fq_mul(fq_mul(a0, a23), inv2);
+  L[2] = fq_neg(fq_mul(fq_mul(a01, a3), inv2));
+  L[3] = fq_mul(fq_mul(a01, a2), inv6);
+}
+// A pair's 15 values of F(t, s), the round-j summand in its own and the next round's variable: ev[4 y + t] = F(t, Y)
+// for t = 0..3 on the lines Y = 0, 2, 3 (y = 0, 1, 2), then ev[12 + x] = F(X, 1) at X = 0, 2, 3.
+// Round j: F(X, 0) + F(X, 1) at X = 0, 2, 3
+inline void pair_round_j(const Fq ev[15], Fq ej[3]) {
+  ej[0] = fq_add(ev[0], ev[12]);
+  ej[1] = fq_add(ev[2], ev[13]);
+  ej[2] = fq_add(ev[3], ev[14]);
+}
+// round j + 1: the cubics t -> F(t, Y) at t = r_j
+inline void pair_round_j1(const Fq ev[15], const Fq& r_j, Fq ej1[3]) {
+  Fq L[4];
+  lagrange4(r_j, L);
+  for (int y = 0; y < 3; y++) {
+    Fq acc = fq_zero();
+    for (int k = 0; k < 4; k++) acc = fq_add(acc, fq_mul(L[k], ev[4 * y + k]));
+    ej1[y] = acc;
+  }
+}
+// A triple's 64 values F(t, s, u) = ev[t + 4 s + 16 u] on {0..3}^3. Round j: F(X, s, u) over s, u in {0, 1}
+inline void triple_round_j(const Fq ev[64], Fq ej[3]) {
+  for (int xi = 0; xi < 3; xi++) {
+    const int X = xi == 0 ? 0 : xi + 1;
+    ej[xi] = fq_add(fq_add(ev[X], ev[X + 4]), fq_add(ev[X + 16], ev[X + 20]));
+  }
+}
+// round j + 1: t -> F(t, Y, 0) + F(t, Y, 1) at t = r_j, Y = 0, 2, 3 (L = lagrange4(r_j))
+inline void triple_round_j1(const Fq ev[64], const Fq L[4], Fq ej1[3]) {
+  for (int yi = 0; yi < 3; yi++) {
+    const int Y = yi == 0 ? 0 : yi + 1;
+    Fq acc = fq_zero();
+    for (int a = 0; a < 4; a++) acc = fq_add(acc, fq_mul(L[a], fq_add(ev[a + 4 * Y], ev[a + 4 * Y + 16])));
+    ej1[yi] = acc;
+  }
+}
+// round j + 2: (t, s) -> F(t, s, Z) at (r_j, r_j+1), Z = 0, 2, 3 (L = lagrange4(r_j), M = lagrange4(r_j+1))
+inline void triple_round_j2(const Fq ev[64], const Fq L[4], const Fq M[4], Fq ej2[3]) {
+  for (int zi = 0; zi < 3; zi++) {
+    const int Z = zi == 0 ? 0 : zi + 1;
+    Fq acc = fq_zero();
+    for (int b = 0; b < 4; b++) {
+      Fq row = fq_zero();
+      for (int a = 0; a < 4; a++) row = fq_add(row, fq_mul(L[a], ev[a + 4 * b + 16 * Z]));
+      acc = fq_add(acc, fq_mul(M[b], row));
+    }
+    ej2[zi] = acc;
+  }
+}
+// a vector's 2 x 2 corners w[2 t + s] (p00, p01, p10, p11) folded at (r_j, r_j+1): bound_poly_var_top twice
+inline Fq fold_corners2(const Fq w[4], const Fq& rj, const Fq& rj1) {
+  const Fq q0 = fq_add(w[0], fq_mul(rj, fq_sub(w[2], w[0]))), q1 = fq_add(w[1], fq_mul(rj, fq_sub(w[3], w[1])));
+  return fq_add(q0, fq_mul(rj1, fq_sub(q1, q0)));
+}
+// its 2 x 2 x 2 corners w[4 t + 2 s + u] folded at (r_j, r_j+1, r_j+2)
+inline Fq fold_corners3(const Fq w[8], const Fq& rj, const Fq& rj1, const Fq& rj2) {
+  Fq q[4];
+  for (int j = 0; j < 4; j++) q[j] = fq_add(w[j], fq_mul(rj, fq_sub(w[j + 4], w[j])));
+  const Fq y0 = fq_add(q[0], fq_mul(rj1, fq_sub(q[2], q[0]))), y1 = fq_add(q[1], fq_mul(rj1, fq_sub(q[3], q[1])));
+  return fq_add(y0, fq_mul(rj2, fq_sub(y1, y0)));
+}
+
 }  // namespace spg

@@ -1,4 +1,4 @@
-// spg — small host-side helpers shared by the prover drivers (r1cs.hip, spark.hip): sizes, eq tables,
+// spg — small host-side helpers shared by the prover drivers (r1cs.hip, spark.hip, layers.hip, hyrax.hip): sizes, eq tables,
 // round polynomials, scalar (de)serialisation at the C-ABI.
 #pragma once
 #include <initializer_list>

@@ -23,7 +23,7 @@
 //     level (every >= 2 and >= 3 test) is fixed at library load, not at first use; whether it is set, at first use.
 //   * SPG_VEC_MIN=0 switches the 8-lane host sums off everywhere (host.hpp, proto.hip, comb.hip).
 //   * negative LONG values reach their sites as huge size_t counts (the sites cast, as they always did); the limits
-//     derived at the sites are taken there: SPG_PAIR_MAX by SPG_PAIR_BS (spark.hip), SPG_TRIPLE_MAX at 384,
+//     derived at the sites are taken there: SPG_PAIR_MAX by SPG_PAIR_BS (layers.hip), SPG_TRIPLE_MAX at 384,
 //     SPG_P1_PAIR_MAX / SPG_P2_PAIR_MAX at kP1PairMax (r1cs.hip), SPG_VMSM_C to 4..14 when non-zero (vmsm.hpp),
 //     SPG_H2D_CHUNK_KB at the upload chunk, SPG_SMSM_C outside 4..9 ignored (msm.hip).
 //   * SPG_COMB_C, SPG_POOL_THREADS, SPG_TRACE: unset (kUnset) differs from every value, 0 included: the sites ask

@@ -1,45 +1,17 @@
 // spg — SPARK layer-sumcheck kernels (ProductCircuitEvalProofBatched rounds, product_tree.rs:271-396);
-// spark.hip launches them, scripts/micro/layer_phases.hip times their phases.
+// layers.hip launches them, scripts/micro/layer_phases.hip times their phases.
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include "ctx.hpp"
 #include "lds.hpp"
 #include "qsum.hpp"
+#include "segsum.hpp"
 #include "cube.hpp"
 #include "prodc.hpp"
 
 namespace spg {
 
-__device__ __forceinline__ void block_sum3_sp(Fq& v0, Fq& v1, Fq& v2) {
-  __shared__ uint32_t sh[3][soa_words<Fq, 256>()];  // component-major: no bank conflicts
-  int t = threadIdx.x;
-  for (int d = 128; d >= 1; d >>= 1) {
-    if (t >= d && t < 2 * d) {
-      soa_put<256>(sh[0], t - d, v0);
-      soa_put<256>(sh[1], t - d, v1);
-      soa_put<256>(sh[2], t - d, v2);
-    }
-    __syncthreads();
-    if (t < d) {
-      v0 = fq_add(v0, soa_get<256, Fq>(sh[0], t));
-      v1 = fq_add(v1, soa_get<256, Fq>(sh[1], t));
-      v2 = fq_add(v2, soa_get<256, Fq>(sh[2], t));
-    }
-    __syncthreads();
-  }
-  // broadcast thread 0's sums
-  if (t == 0) {
-    soa_put<256>(sh[0], 0, v0);
-    soa_put<256>(sh[1], 0, v1);
-    soa_put<256>(sh[2], 0, v2);
-  }
-  __syncthreads();
-  v0 = soa_get<256, Fq>(sh[0], 0);
-  v1 = soa_get<256, Fq>(sh[1], 0);
-  v2 = soa_get<256, Fq>(sh[2], 0);
-  __syncthreads();
-}
 // block-wide sums of three Fq values over BS threads; the result is valid in thread 0
 template <int BS>
 __device__ __forceinline__ void block_sum3_t0(Fq& v0, Fq& v1, Fq& v2) {

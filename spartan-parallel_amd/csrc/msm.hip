@@ -846,7 +846,7 @@ int msm_small_device(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const F
   const int c = pick_small_window(per);
   const int NB = 1 << (c - 1);
   SPG_CHECK(ctx, B <= 65535, "msm batch too large for the latency path");
-  Ext* bk = (Ext*)ws_get(ctx, 13, B * (size_t)NB * sizeof(Ext) + 64);
+  Ext* bk = (Ext*)ws_get(ctx, Ws::MsmLatBuckets, B * (size_t)NB * sizeof(Ext) + 64);
   if (!bk) return set_err(ctx, SPG_E_NOMEM, "small msm workspace");
   const int n1 = (int)(g->n + 1), off = (int)gen_offset, h = h_index < 0 ? (int)g->n : (int)h_index;
   switch (c) {
@@ -879,7 +879,7 @@ int compress_ext_device(spg_ctx* ctx, const Ext* d_ext, size_t n, uint8_t* d_out
 // B MSMs of n scalars (rows of a Hyrax commitment) through the latency path, compressed on the device
 int msm_small_compressed(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const Fq* d_scalars, size_t n, size_t B,
                          uint8_t* d_out) {
-  Ext* d_ext = (Ext*)ws_get(ctx, 15, B * sizeof(Ext) + 64);
+  Ext* d_ext = (Ext*)ws_get(ctx, Ws::MsmLatExt, B * sizeof(Ext) + 64);
   if (!d_ext) return set_err(ctx, SPG_E_NOMEM, "small msm output");
   const bool trace3 = knob::trace() >= 3;
   hipEvent_t e[3];
@@ -958,7 +958,7 @@ int msm_batch_device(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const F
   // time in its digit sort and bucket reduction as in its additions
   const size_t tot = B * (n + (d_blinds ? 1 : 0));
   if (msm_comb_rule(d_idx != nullptr, B, n, tot)) {
-    Ext* ext = d_ext ? d_ext : (Ext*)ws_get(ctx, 17, B * sizeof(Ext) + 64);
+    Ext* ext = d_ext ? d_ext : (Ext*)ws_get(ctx, Ws::MsmRowExt, B * sizeof(Ext) + 64);
     if (!ext) return set_err(ctx, SPG_E_NOMEM, "msm comb points");
     const int hi = !d_blinds ? -1 : (h_index < 0 ? (int)g->n : (int)h_index);
     const int rc = msm_comb(ctx, g, gen_offset, d_scalars, n, B, d_blinds, d_out, hi, ext);
@@ -977,17 +977,17 @@ int msm_batch_device(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const F
   SPG_CHECK(ctx, max_entries < 0x7fffffffULL, "msm batch too large");
   SPG_CHECK(ctx, (size_t)kTableRows * (g->n + 1) < 0x7fffffffULL, "generator table too large");
 
-  uint32_t* hist = (uint32_t*)ws_get(ctx, 1, (nkeys + 1) * 4);
-  uint32_t* off = (uint32_t*)ws_get(ctx, 2, (nkeys + 1) * 4);
-  uint32_t* cursor = (uint32_t*)ws_get(ctx, 3, (nkeys + 1) * 4);
-  uint32_t* items = (uint32_t*)ws_get(ctx, 4, (nkeys + 1) * 4);
-  uint32_t* item_off = (uint32_t*)ws_get(ctx, 5, (nkeys + 1) * 4);
-  uint32_t* entries = (uint32_t*)ws_get(ctx, 6, max_entries * 4 + 4);
-  uint32_t* item_key = (uint32_t*)ws_get(ctx, 7, max_items * 4);
-  Ext* partial = (Ext*)ws_get(ctx, 8, max_items * sizeof(Ext));
+  uint32_t* hist = (uint32_t*)ws_get(ctx, Ws::MsmHist, (nkeys + 1) * 4);
+  uint32_t* off = (uint32_t*)ws_get(ctx, Ws::MsmOff, (nkeys + 1) * 4);
+  uint32_t* cursor = (uint32_t*)ws_get(ctx, Ws::MsmCursor, (nkeys + 1) * 4);
+  uint32_t* items = (uint32_t*)ws_get(ctx, Ws::MsmItems, (nkeys + 1) * 4);
+  uint32_t* item_off = (uint32_t*)ws_get(ctx, Ws::MsmItemOff, (nkeys + 1) * 4);
+  uint32_t* entries = (uint32_t*)ws_get(ctx, Ws::MsmEntries, max_entries * 4 + 4);
+  uint32_t* item_key = (uint32_t*)ws_get(ctx, Ws::MsmItemKey, max_items * 4);
+  Ext* partial = (Ext*)ws_get(ctx, Ws::MsmPartial, max_items * sizeof(Ext));
   const int m = rt.m, S = rt.S, log2m = rt.log2m;  // buckets per segment, segments per MSM
-  Ext* segT = (Ext*)ws_get(ctx, 9, B * (size_t)S * sizeof(Ext));
-  Ext* segS = (Ext*)ws_get(ctx, 10, B * (size_t)S * sizeof(Ext));
+  Ext* segT = (Ext*)ws_get(ctx, Ws::MsmSegT, B * (size_t)S * sizeof(Ext));
+  Ext* segS = (Ext*)ws_get(ctx, Ws::MsmSegS, B * (size_t)S * sizeof(Ext));
   if (!hist || !off || !cursor || !items || !item_off || !entries || !item_key || !partial || !segT || !segS)
     return set_err(ctx, SPG_E_NOMEM, "msm workspace allocation failed");
 
@@ -1018,7 +1018,7 @@ int msm_batch_device(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const F
 
   size_t tmp_bytes = 0;
   hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_bytes, hist, off, (int)(nkeys + 1), s);
-  void* tmp = ws_get(ctx, 11, tmp_bytes + 16);
+  void* tmp = ws_get(ctx, Ws::MsmScanTmp, tmp_bytes + 16);
   if (!tmp) return set_err(ctx, SPG_E_NOMEM, "scan workspace");
   if (rows) {
     KScope ks(ctx, "msm_digits_rows");
@@ -1063,13 +1063,13 @@ int msm_batch_device(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const F
       // encodings one lane per MSM (k_compress_ext) instead of on one lane of each k_final block: the
       // ~250 dependent squarings of an encoding would otherwise serialise behind every block's tree
       Ext* ext = d_ext;
-      if (!ext && d_out) ext = (Ext*)ws_get(ctx, 17, B * sizeof(Ext) + 64);
+      if (!ext && d_out) ext = (Ext*)ws_get(ctx, Ws::MsmRowExt, B * sizeof(Ext) + 64);
       if (!ext) return set_err(ctx, SPG_E_NOMEM, "msm final points");
       const Ext *fT = segT, *fS = segS;
       const int fSn = rt.final_S, flog2m = rt.final_log2m;  // what the final scan sees
       if (rt.regroup) {  // few MSMs with many segments: regroup 8 segments per group first
         const int lg = 3, G = rt.final_S;
-        Ext* rT = (Ext*)ws_get(ctx, 18, 2 * B * (size_t)G * sizeof(Ext) + 64);
+        Ext* rT = (Ext*)ws_get(ctx, Ws::MsmRunT, 2 * B * (size_t)G * sizeof(Ext) + 64);
         if (!rT) return set_err(ctx, SPG_E_NOMEM, "msm regroup");
         Ext* rS = rT + B * (size_t)G;
         hipLaunchKernelGGL(k_regroup_q, dim3((unsigned)((4 * B * (size_t)G + 255) / 256)), dim3(256), 0, s, segT,
@@ -1238,7 +1238,7 @@ static int msm_host(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const ui
   if (gen_offset + n > g->n) return set_err(ctx, SPG_E_ARG, "MSM longer than the generator set");
   hipStream_t s = ctx->stream;
   size_t sb = B * n * sizeof(Fq);
-  Fq* d_s = (Fq*)ws_get(ctx, 0, sb + B * sizeof(Fq) + B * 32 + 64);
+  Fq* d_s = (Fq*)ws_get(ctx, Ws::MsmScalars, sb + B * sizeof(Fq) + B * 32 + 64);
   if (!d_s) return set_err(ctx, SPG_E_NOMEM, "scalar upload");
   Fq* d_bl = blinds ? d_s + B * n : nullptr;
   uint8_t* d_out = (uint8_t*)(d_s + B * n + B);
@@ -1257,7 +1257,7 @@ static int msm_host(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, const ui
     ctx->last_us = ms * 1000.0;
     return SPG_OK;
   }
-  Ext* d_ext = small ? (Ext*)ws_get(ctx, 14, B * sizeof(Ext) + 64) : nullptr;
+  Ext* d_ext = small ? (Ext*)ws_get(ctx, Ws::MsmSmallExt, B * sizeof(Ext) + 64) : nullptr;
   if (small && !d_ext) return set_err(ctx, SPG_E_NOMEM, "msm output");
   timer_start(ctx);
   int rc = small ? msm_small_device(ctx, g, gen_offset, d_s, n, B, d_bl, d_ext, nullptr, -1)
@@ -1299,7 +1299,7 @@ static int msm_partial_dev(spg_ctx* ctx, const spg_gens* g, size_t gen_offset, c
     h::fe_to_bytes(r.Z, out_ext + 64);
     h::fe_to_bytes(r.T, out_ext + 96);
   } else {
-    Ext* d_ext = (Ext*)ws_get(ctx, 19, sizeof(Ext) + 64);
+    Ext* d_ext = (Ext*)ws_get(ctx, Ws::MsmOneExt, sizeof(Ext) + 64);
     if (!d_ext) return set_err(ctx, SPG_E_NOMEM, "msm output");
     timer_start(ctx);
     int rc = n <= kSmallMaxN ? msm_small_device(ctx, g, gen_offset, d_s, n, 1, nullptr, d_ext, nullptr, -1)
@@ -1329,7 +1329,7 @@ extern "C" int spg_msm_partial(spg_ctx* ctx, const spg_gens* g, size_t gen_offse
     memcpy(out_ext, &id, sizeof(Ext));
     return SPG_OK;
   }
-  Fq* d_s = (Fq*)ws_get(ctx, 0, n * sizeof(Fq) + 64);
+  Fq* d_s = (Fq*)ws_get(ctx, Ws::MsmScalars, n * sizeof(Fq) + 64);
   if (!d_s) return set_err(ctx, SPG_E_NOMEM, "scalar upload");
   SPG_HIP(ctx, hipMemcpyAsync(d_s, scalars_mont, n * sizeof(Fq), hipMemcpyHostToDevice, ctx->stream));
   return msm_partial_dev(ctx, g, gen_offset, d_s, n, out_ext);
@@ -1388,8 +1388,8 @@ int spg::msm_rows_host_enc(spg_ctx* ctx, const spg_gens* g, const Fq* d_scalars,
   hipStream_t s = ctx->stream;
   const size_t tot = B * (n + (d_blinds ? 1 : 0));
   const bool comb = msm_comb_rule(false, B, n, tot);
-  if (halve && comb && B >= 384) {  // (fewer rows: spark.hip kHalvedMin)
-    Ext* ext = (Ext*)ws_get(ctx, 17, B * sizeof(Ext) + 64);
+  if (halve && comb && B >= 384) {  // (fewer rows: proto.hpp kHalvedMin)
+    Ext* ext = (Ext*)ws_get(ctx, Ws::MsmRowExt, B * sizeof(Ext) + 64);
     if (!ext) return set_err(ctx, SPG_E_NOMEM, "msm comb points");
     const int hi = !d_blinds ? -1 : (h_index < 0 ? (int)g->n : (int)h_index);
     const int rc = msm_comb(ctx, g, 0, d_scalars, n, B, d_blinds, nullptr, hi, ext, true);
@@ -1404,7 +1404,7 @@ int spg::msm_rows_host_enc(spg_ctx* ctx, const spg_gens* g, const Fq* d_scalars,
     }
     if (rc != kCombSkip) return rc;
   }
-  uint8_t* d_out = (uint8_t*)ws_get(ctx, 12, 32 * B + 64);
+  uint8_t* d_out = (uint8_t*)ws_get(ctx, Ws::MsmOut, 32 * B + 64);
   if (!d_out) return set_err(ctx, SPG_E_NOMEM, "commit rows out");
   const int rc = msm_batch_device(ctx, g, 0, d_scalars, n, B, d_blinds, d_out, nullptr, h_index);
   if (rc) return rc;

@@ -142,7 +142,7 @@ inline bool bullet_comb_launch(int shape_P, int P, int c, int eg, int ebs, int e
   return *wgs * *R <= kBulletPartsMax;
 }
 
-// ---------------------------------------------------------------- SPARK layers (spark.hip)
+// ---------------------------------------------------------------- SPARK layers (layers.hip)
 // workgroups and block size of a fused layer round over W = nt * len elements: one workgroup up to one_wg
 // (SPG_LAYER_ONEWG) elements (no ticket), else about ept (SPG_LAYER_EPT) elements per thread over 256-thread workgroups
 inline void layer_grid(size_t W, size_t one_wg, size_t ept, unsigned* K, int* BS) {

@@ -36,7 +36,6 @@ namespace spg {
 
 namespace {
 
-// workspace slots 110..122 (msm_big.hip 100..108)
 constexpr int kVBS = 256;     // threads per workgroup (64 quads)
 constexpr int kVQuads = kVBS / 4;
 constexpr int kVKeys = 8192;  // LDS histogram / cursor words per pass (one window at c = 14)
@@ -307,24 +306,24 @@ int vmsm_device(spg_ctx* ctx, const spg_points* P, const size_t* offs, const siz
   a.wpp = std::max(1, kVKeys / NB);
   a.M = (uint32_t)M;
   const size_t desc_bytes = B * sizeof(VMsm), blk_bytes = blk.size() * sizeof(VBlk);
-  uint8_t* desc = (uint8_t*)ws_get(ctx, 122, desc_bytes + blk_bytes + 64);
-  a.digits = (int16_t*)ws_get(ctx, 111, E * sizeof(int16_t) + 64);
-  a.bh = (uint32_t*)ws_get(ctx, 112, (M + 1) * 4 + 64);
-  a.off = (uint32_t*)ws_get(ctx, 113, (M + 1) * 4 + 64);
-  a.entries = (uint32_t*)ws_get(ctx, 114, E * 4 + 64);
-  VChunk* chunks = (VChunk*)ws_get(ctx, 115, max_chunks * sizeof(VChunk));
-  uint32_t* nch = (uint32_t*)ws_get(ctx, 116, (K + 1) * 4 + 64);
-  uint32_t* first = (uint32_t*)ws_get(ctx, 117, (K + GS + 1) * 4 + 64);
-  Ext* sums = (Ext*)ws_get(ctx, 118, max_chunks * sizeof(Ext));
-  unsigned* gcnt = (unsigned*)ws_get(ctx, 119, NG * 4 + 64);
-  Ext* groups = (Ext*)ws_get(ctx, 121, 2 * NG * sizeof(Ext));
+  uint8_t* desc = (uint8_t*)ws_get(ctx, Ws::VmsmDesc, desc_bytes + blk_bytes + 64);
+  a.digits = (int16_t*)ws_get(ctx, Ws::VmsmDigits, E * sizeof(int16_t) + 64);
+  a.bh = (uint32_t*)ws_get(ctx, Ws::VmsmHist, (M + 1) * 4 + 64);
+  a.off = (uint32_t*)ws_get(ctx, Ws::VmsmOff, (M + 1) * 4 + 64);
+  a.entries = (uint32_t*)ws_get(ctx, Ws::VmsmEntries, E * 4 + 64);
+  VChunk* chunks = (VChunk*)ws_get(ctx, Ws::VmsmChunks, max_chunks * sizeof(VChunk));
+  uint32_t* nch = (uint32_t*)ws_get(ctx, Ws::VmsmNumChunks, (K + 1) * 4 + 64);
+  uint32_t* first = (uint32_t*)ws_get(ctx, Ws::VmsmFirst, (K + GS + 1) * 4 + 64);
+  Ext* sums = (Ext*)ws_get(ctx, Ws::VmsmSums, max_chunks * sizeof(Ext));
+  unsigned* gcnt = (unsigned*)ws_get(ctx, Ws::VmsmGroupCnt, NG * 4 + 64);
+  Ext* groups = (Ext*)ws_get(ctx, Ws::VmsmGroups, 2 * NG * sizeof(Ext));
   if (!desc || !a.digits || !a.bh || !a.off || !a.entries || !chunks || !nch || !first || !sums || !gcnt || !groups)
     return set_err(ctx, SPG_E_NOMEM, "variable-base MSM workspace");
   size_t tmp1 = 0, tmp2 = 0;
   hipcub::DeviceScan::ExclusiveSum(nullptr, tmp1, a.bh, a.off, (int)(M + 1), s);
   hipcub::DeviceScan::ExclusiveSum(nullptr, tmp2, nch, first, (int)(K + 1), s);
   size_t tmp_bytes = std::max(tmp1, tmp2);
-  void* tmp = ws_get(ctx, 120, tmp_bytes + 16);
+  void* tmp = ws_get(ctx, Ws::VmsmScanTmp, tmp_bytes + 16);
   if (!tmp) return set_err(ctx, SPG_E_NOMEM, "variable-base MSM scan workspace");
   Ext* h_groups = (Ext*)pinned_get(ctx, 2 * NG * sizeof(Ext));
   if (!h_groups) return set_err(ctx, SPG_E_NOMEM, "variable-base MSM staging");
@@ -407,7 +406,7 @@ int vmsm_run(spg_ctx* ctx, const spg_points* P, const size_t* offs, const size_t
     return SPG_OK;
   }
   if (!d_s) {
-    Fq* up = (Fq*)ws_get(ctx, 110, N * sizeof(Fq) + 64);
+    Fq* up = (Fq*)ws_get(ctx, Ws::VmsmScalars, N * sizeof(Fq) + 64);
     if (!up) return set_err(ctx, SPG_E_NOMEM, "scalar upload");
     SPG_HIP(ctx, hipMemcpyAsync(up, h_s, N * sizeof(Fq), hipMemcpyHostToDevice, s));
     d_s = up;

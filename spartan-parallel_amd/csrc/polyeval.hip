@@ -42,8 +42,6 @@ struct spg_poly_gens {  // PolyCommitmentGens: gens_n = G_0 .. G_{n-1} with h, g
 
 namespace spg {
 
-constexpr size_t kWsPeJobs = 124, kWsPeSums = 125, kWsPeL = 126, kWsPePart = 127, kWsPeOut = 128, kWsPeBlinds = 129;
-constexpr size_t kWsPeRagTerms = 130;
 
 // Every L.Z vector of a plan in one launch pair and one download. Z: the polynomial of every term (points form: of
 // term 0, shared by all). Lp: the scaled eq table of every bound term, in term order. out: plan.out_len scalars, group g
@@ -101,11 +99,11 @@ static int pe_bound(spg_ctx* ctx, const PePlan& plan, bool points, const std::ve
     c0 += (uint32_t)((g.Rs + kPeSumCols - 1) / kPeSumCols);
   }
   if (b0 != plan.xblocks) return set_err(ctx, SPG_E_ARG, "poly eval: plan and jobs disagree");
-  PeJob* dj = (PeJob*)ws_get(ctx, kWsPeJobs, jobs.size() * sizeof(PeJob) + 64);
-  PeSum* ds = (PeSum*)ws_get(ctx, kWsPeSums, sums.size() * sizeof(PeSum) + 64);
-  Fq* dL = (Fq*)ws_get(ctx, kWsPeL, Lall.size() * sizeof(Fq) + 64);
-  Fq* dpart = (Fq*)ws_get(ctx, kWsPePart, plan.part_len * sizeof(Fq) + 64);
-  Fq* dout = (Fq*)ws_get(ctx, kWsPeOut, plan.out_len * sizeof(Fq) + 64);
+  PeJob* dj = (PeJob*)ws_get(ctx, Ws::PeJobs, jobs.size() * sizeof(PeJob) + 64);
+  PeSum* ds = (PeSum*)ws_get(ctx, Ws::PeSums, sums.size() * sizeof(PeSum) + 64);
+  Fq* dL = (Fq*)ws_get(ctx, Ws::PeL, Lall.size() * sizeof(Fq) + 64);
+  Fq* dpart = (Fq*)ws_get(ctx, Ws::PePart, plan.part_len * sizeof(Fq) + 64);
+  Fq* dout = (Fq*)ws_get(ctx, Ws::PeOut, plan.out_len * sizeof(Fq) + 64);
   if (!dj || !ds || !dL || !dpart || !dout) return set_err(ctx, SPG_E_NOMEM, "poly eval: bound workspace");
   hipStream_t s = ctx->stream;
   SPG_HIP(ctx, hipMemcpyAsync(dj, jobs.data(), jobs.size() * sizeof(PeJob), hipMemcpyHostToDevice, s));
@@ -158,12 +156,12 @@ static int pe_bound_ragged(spg_ctx* ctx, const PeUniPlan& plan, const std::vecto
   else
     add_group(0, plan.R_size, 0, n);
   if (b0 != plan.xblocks) return set_err(ctx, SPG_E_ARG, "poly eval: plan and jobs disagree");
-  PeJob* dj = (PeJob*)ws_get(ctx, kWsPeJobs, jobs.size() * sizeof(PeJob) + 64);
-  PeRagSum* ds = (PeRagSum*)ws_get(ctx, kWsPeSums, sums.size() * sizeof(PeRagSum) + 64);
-  PeRagTerm* dt = (PeRagTerm*)ws_get(ctx, kWsPeRagTerms, terms.size() * sizeof(PeRagTerm) + 64);
-  Fq* dL = (Fq*)ws_get(ctx, kWsPeL, Lall.size() * sizeof(Fq) + 64);
-  Fq* dpart = (Fq*)ws_get(ctx, kWsPePart, plan.part_len * sizeof(Fq) + 64);
-  Fq* dout = (Fq*)ws_get(ctx, kWsPeOut, plan.out_len * sizeof(Fq) + 64);
+  PeJob* dj = (PeJob*)ws_get(ctx, Ws::PeJobs, jobs.size() * sizeof(PeJob) + 64);
+  PeRagSum* ds = (PeRagSum*)ws_get(ctx, Ws::PeSums, sums.size() * sizeof(PeRagSum) + 64);
+  PeRagTerm* dt = (PeRagTerm*)ws_get(ctx, Ws::PeRagTerms, terms.size() * sizeof(PeRagTerm) + 64);
+  Fq* dL = (Fq*)ws_get(ctx, Ws::PeL, Lall.size() * sizeof(Fq) + 64);
+  Fq* dpart = (Fq*)ws_get(ctx, Ws::PePart, plan.part_len * sizeof(Fq) + 64);
+  Fq* dout = (Fq*)ws_get(ctx, Ws::PeOut, plan.out_len * sizeof(Fq) + 64);
   if (!dj || !ds || !dt || !dL || !dpart || !dout) return set_err(ctx, SPG_E_NOMEM, "poly eval: bound workspace");
   hipStream_t s = ctx->stream;
   SPG_HIP(ctx, hipMemcpyAsync(dj, jobs.data(), jobs.size() * sizeof(PeJob), hipMemcpyHostToDevice, s));
@@ -206,7 +204,7 @@ static int commit_impl(spg_ctx* ctx, const spg_poly_gens* pg, const spg_buf* Z, 
   SPG_HIP(ctx, hipSetDevice(ctx->device));
   ProverGens& g = const_cast<ProverGens&>(pg->g);
   if (!blinds) return commit_rows(ctx, g, Z->d + offset, R, L, reinterpret_cast<Pt*>(comm));
-  Fq* db = (Fq*)ws_get(ctx, kWsPeBlinds, L * sizeof(Fq) + 64);
+  Fq* db = (Fq*)ws_get(ctx, Ws::PeBlinds, L * sizeof(Fq) + 64);
   if (!db) return set_err(ctx, SPG_E_NOMEM, "poly commit: blinds");
   const FqV hb = lds(blinds, L);
   SPG_HIP(ctx, hipMemcpyAsync(db, hb.data(), L * sizeof(Fq), hipMemcpyHostToDevice, ctx->stream));

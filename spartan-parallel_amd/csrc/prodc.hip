@@ -4,7 +4,7 @@
 //   spg_prodc_new / evaluate  ProductCircuit::new / evaluate              src/product_tree.rs:18-108
 //   spg_prove_cubic_batched   SumcheckInstanceProof::prove_cubic_batched  src/sumcheck.rs:264-434
 //   spg_prodc_prove_batched   ProductCircuitEvalProofBatched::prove       src/product_tree.rs:260-396
-// The trees, the layer rounds and their launch forms are the SPARK prover's (spark.hip through prodc.hpp); this file
+// The trees, the layer rounds and their launch forms are the SPARK prover's (layers.hip through prodc.hpp); this file
 // hashes field-element operands, arranges caller vectors into the prover's tree layout and moves results back.
 #include <hip/hip_runtime.h>
 #include <string.h>
@@ -26,8 +26,6 @@ struct spg_prodc {
 
 namespace spg {
 namespace {
-
-constexpr size_t kWsProdcDesc = 114, kWsProdcTmp = 115, kWsProdcTops = 116;
 
 // a scalar as two 16-byte accesses (spg_buf data is hipMalloc'd: 32 i bytes in is 16-byte aligned)
 __device__ __forceinline__ Fq ld_wide(const Fq* p) {
@@ -87,10 +85,8 @@ __global__ void __launch_bounds__(256) k_put_prefix(Fq* const* __restrict__ dst,
   dst[u / s][u % s] = vals[u];
 }
 
-unsigned nblk(size_t n) { return (unsigned)((n + 255) / 256); }
-
 // host bytes into workspace slot `slot` (synchronous: `h` may be a temporary)
-void* upload_desc(spg_ctx* ctx, size_t slot, const void* h, size_t bytes) {
+void* upload_desc(spg_ctx* ctx, Ws slot, const void* h, size_t bytes) {
   void* d = ws_get(ctx, slot, bytes + 64);
   if (!d) return nullptr;
   if (hipMemcpyAsync(d, h, bytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
@@ -101,7 +97,7 @@ void* upload_desc(spg_ctx* ctx, size_t slot, const void* h, size_t bytes) {
 
 // n gathers of `per * s` scalars each (k_gather_vecs) in launches of at most 65535 vectors
 int gather_vecs(spg_ctx* ctx, const std::vector<const Fq*>& src, Fq* dst, size_t dst_stride, size_t per, size_t s) {
-  const Fq* const* d = (const Fq* const*)upload_desc(ctx, kWsProdcDesc, src.data(), src.size() * sizeof(Fq*));
+  const Fq* const* d = (const Fq* const*)upload_desc(ctx, Ws::ProdcDesc, src.data(), src.size() * sizeof(Fq*));
   if (!d) return set_err(ctx, SPG_E_NOMEM, "vector descriptors");
   for (size_t b0 = 0; b0 < src.size(); b0 += 65535) {
     const size_t nb = std::min<size_t>(65535, src.size() - b0);
@@ -118,7 +114,7 @@ int put_prefix(spg_ctx* ctx, const std::vector<Fq*>& dst, const FqV& vals, size_
   std::vector<uint8_t> h(pb + vals.size() * sizeof(Fq));
   memcpy(h.data(), dst.data(), nb * sizeof(Fq*));
   memcpy(h.data() + pb, vals.data(), vals.size() * sizeof(Fq));
-  uint8_t* d = (uint8_t*)upload_desc(ctx, kWsProdcDesc, h.data(), h.size());
+  uint8_t* d = (uint8_t*)upload_desc(ctx, Ws::ProdcDesc, h.data(), h.size());
   if (!d) return set_err(ctx, SPG_E_NOMEM, "bound values upload");
   hipLaunchKernelGGL(k_put_prefix, dim3(nblk(nb * s)), dim3(256), 0, ctx->stream, (Fq* const*)d, (const Fq*)(d + pb), s,
                      nb);
@@ -179,7 +175,7 @@ extern "C" int spg_hash_layer(spg_ctx* ctx, const spg_buf* eval_table, const spg
   std::vector<spg::HashOps> h(n);
   for (size_t k = 0; k < n; k++)
     h[k] = {addrs[k]->d, derefs[k]->d, read_ts[k]->d, made[2 + k]->d, made[2 + n + k]->d};
-  const spg::HashOps* dops = (const spg::HashOps*)spg::upload_desc(ctx, spg::kWsProdcDesc, h.data(), n * sizeof(spg::HashOps));
+  const spg::HashOps* dops = (const spg::HashOps*)spg::upload_desc(ctx, spg::Ws::ProdcDesc, h.data(), n * sizeof(spg::HashOps));
   if (!dops) return fail(SPG_E_NOMEM, "spg_hash_layer: descriptors");
   {
     // algorithmic bytes: 2 scalars read and 2 written per cell, 3 read and 2 written per op
@@ -219,7 +215,7 @@ extern "C" int spg_prodc_new(spg_ctx* ctx, const spg_buf* const* polys, size_t n
     return spg::set_err(ctx, code, msg);
   };
   if (hipMalloc(&P->tree, nc * 2 * M * sizeof(Fq) + 64) != hipSuccess) return fail(SPG_E_NOMEM, "spg_prodc_new: trees");
-  Fq* dtops = (Fq*)spg::ws_get(ctx, spg::kWsProdcTops, nc * sizeof(Fq) + 64);
+  Fq* dtops = (Fq*)spg::ws_get(ctx, spg::Ws::ProdcTops, nc * sizeof(Fq) + 64);
   if (!dtops) return fail(SPG_E_NOMEM, "spg_prodc_new: tops");
   std::vector<const Fq*> src(nc);
   for (size_t c = 0; c < nc; c++) src[c] = polys[c]->d;
@@ -270,7 +266,7 @@ extern "C" int spg_prodc_layer(spg_ctx* ctx, const spg_prodc* P, size_t c, size_
   return SPG_OK;
 }
 
-// One layer of the prover (spark.hip cubic_layer: its descriptors, launch plan and kernels) over the caller's vectors.
+// One layer of the prover (layers.hip cubic_layer: its descriptors, launch plan and kernels) over the caller's vectors.
 // With num_rounds = k the triples point at the caller's buffers. With num_rounds < k the s = 2^(k - num_rounds) entries
 // that stay are the low index bits, which no round binds: the sumcheck is that of the s interleaved sub-vectors
 // x[i s + j] (i < 2^num_rounds) of every vector side by side, each with its triple's coefficient, so the vectors are
@@ -311,7 +307,7 @@ static int prove_cubic_batched_impl(spg_ctx* ctx, const uint64_t* claim_mont, si
     for (size_t i = 0; i < n_seq; i++) tr[n_par + i] = {A_seq[i]->d, B_seq[i]->d, C_seq[i]->d};
   } else {
     // scratch vector 3 i + v = vector v (A, B, C) of triple i as its s sub-vectors back to back
-    Fq* tmp = (Fq*)spg::ws_get(ctx, spg::kWsProdcTmp, 3 * (n_par + n_seq) * len * sizeof(Fq) + 64);
+    Fq* tmp = (Fq*)spg::ws_get(ctx, spg::Ws::ProdcTmp, 3 * (n_par + n_seq) * len * sizeof(Fq) + 64);
     if (!tmp) return spg::set_err(ctx, SPG_E_NOMEM, "spg_prove_cubic_batched: scratch");
     std::vector<const Fq*> src;
     for (size_t i = 0; i < n_par; i++) src.insert(src.end(), {A_par[i]->d, B_par[i]->d, C_par->d});

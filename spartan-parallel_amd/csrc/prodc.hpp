@@ -1,5 +1,5 @@
-// spg — what the product-circuit seams (prodc.hip) share with the SPARK prover (spark.hip): the tree layout, the
-// batched layer prover and its proof objects. The kernels and launch forms live in spark.hip / layer.hpp; prodc.hip
+// spg — what the product-circuit seams (prodc.hip) share with the SPARK prover (spark.hip), both through layers.hip: the tree layout, the
+// batched layer prover and its proof objects. The kernels and launch forms live in layers.hip / layer.hpp; prodc.hip
 // only arranges caller vectors into the prover's layout and calls these.
 #pragma once
 #include <vector>
@@ -34,7 +34,7 @@ struct BatchedProofP {  // ProductCircuitEvalProofBatched
 };
 
 // A set of nc product circuits (M leaves each), possibly sharded over the W ranks of a proof (see "sharded
-// proof" at spark_prove_core): rank r holds leaves i = W i' + r as a local tree of m = M / W leaves (levels of
+// proof" at SparkProver, spark.hip): rank r holds leaves i = W i' + r as a local tree of m = M / W leaves (levels of
 // >= 2 entries at loc + c 2m, the usual back-to-back layout), and every rank holds the global levels of <= W
 // entries as a replicated "top" tree (circuit c at top + c 2W, W entries first). W == 1: loc is the whole tree.
 struct TreeSh {
@@ -49,7 +49,7 @@ struct TreeSh {
 int tree_build(spg_ctx* ctx, Fq* tree, size_t nc, size_t M, Fq* tops);
 // DotProductCircuit::evaluate of every triple (n entries per vector) into out (host)
 int dotp_evaluate(spg_ctx* ctx, const std::vector<Triple>& dotp, size_t n, Fq* out);
-// ProductCircuitEvalProofBatched::prove (product_tree.rs:271-396), see spark.hip
+// ProductCircuitEvalProofBatched::prove (product_tree.rs:271-396), see layers.hip
 int batched_prove(spg_ctx* ctx, const TreeSh& ts, size_t nc, size_t M, FqV claims, const std::vector<Triple>& dotp,
                   const FqV& dotp_claims, Tr& t, BatchedProofP* out, FqV* rand_out, const Shard& sh);
 // One layer's sumcheck (SumcheckInstanceProof::prove_cubic_batched, sumcheck.rs:264-434) over caller vectors of

@@ -298,8 +298,8 @@ static int device_msm_flat(spg_ctx* ctx, ProverGens& g, const std::vector<Fq>& h
   g_msm_laps.lap("bullet_host");
   const size_t sc_bytes = hs.size() * sizeof(Fq), ix_bytes = h_idx ? h_idx->size() * 4 : 0;
   const size_t in_bytes = sc_bytes + ix_bytes, bk_bytes = sizeof(Ext) * B * 256;
-  Fq* d_s = (Fq*)ws_get(ctx, 20, in_bytes + 64);
-  Ext* d_bk = (Ext*)ws_get(ctx, 23, bk_bytes + 64);
+  Fq* d_s = (Fq*)ws_get(ctx, Ws::ProtoScalars, in_bytes + 64);
+  Ext* d_bk = (Ext*)ws_get(ctx, Ws::ProtoBuckets, bk_bytes + 64);
   uint8_t* stage = (uint8_t*)pinned_get(ctx, in_bytes + bk_bytes + 256);
   if (!d_s || !d_bk || !stage) return set_err(ctx, SPG_E_NOMEM, "device_msm");
   // scalars (and indices) up through page-locked staging (a pageable source costs a staging copy + blit per call)
@@ -339,7 +339,7 @@ int device_msm_idx(spg_ctx* ctx, ProverGens& g, const std::vector<FqV>& scalars,
       hi[b * n + i] = idx[b][i];
     }
   }
-  uint32_t* d_i = (uint32_t*)ws_get(ctx, 21, hi.size() * 4 + 64);
+  uint32_t* d_i = (uint32_t*)ws_get(ctx, Ws::ProtoIdx, hi.size() * 4 + 64);
   if (!d_i) return set_err(ctx, SPG_E_NOMEM, "device_msm_idx");
   SPG_HIP(ctx, hipMemcpyAsync(d_i, hi.data(), hi.size() * 4, hipMemcpyHostToDevice, ctx->stream));
   return device_msm_flat(ctx, g, hs, n, B, d_i, out);
@@ -407,7 +407,7 @@ static int bullet_round_launch(spg_ctx* ctx, ProverGens& g, const Fq* aa_in, con
 
 static int bullet_round0_launch(spg_ctx* ctx, ProverGens& g, size_t n, const Fq* d_x, const uint32_t* d_idx,
                                 size_t gmax, Ext* d_bk, uint32_t* seq, int* per) {
-  Fq* st = (Fq*)ws_get(ctx, 24, 4 * n * sizeof(Fq) + 64);  // aa[2], cw[2]
+  Fq* st = (Fq*)ws_get(ctx, Ws::ProtoBulletState, 4 * n * sizeof(Fq) + 64);  // aa[2], cw[2]
   if (!st) return set_err(ctx, SPG_E_NOMEM, "bullet state");
   // round 0 reads a = x where the Cx MSM's scalars already are, and writes the state round 1 reads (aa[1], cw[1]);
   // no later round reads aa[0] before writing it
@@ -428,7 +428,7 @@ static int bullet_rounds_device(spg_ctx* ctx, ProverGens& g, Tr& t, const FqV& x
                                 uint32_t seq0 = 0, int per0 = 0, DevFinal* fin = nullptr) {
   const size_t n = x.size();
   const size_t G1 = g.gens_1.G[0], H = g.gens_n.h;
-  Fq* st = (Fq*)ws_get(ctx, 24, 4 * n * sizeof(Fq) + 64);  // aa[2], cw[2]
+  Fq* st = (Fq*)ws_get(ctx, Ws::ProtoBulletState, 4 * n * sizeof(Fq) + 64);  // aa[2], cw[2]
   if (!st) return set_err(ctx, SPG_E_NOMEM, "bullet state");
   Fq* d_aa[2] = {st, st + n};
   Fq* d_cw[2] = {st + 2 * n, st + 3 * n};
@@ -531,7 +531,7 @@ int dotproduct_log_prove(spg_ctx* ctx, ProverGens& g, Tr& t, Tape& tape, const F
       idx2[b * n2 + n + 1] = H;
     }
     if (!(dev_path && ahead)) {  // (the ahead path uploads them with the Cx scalars)
-      d_idx = (uint32_t*)ws_get(ctx, 21, idx2.size() * 4 + 64);
+      d_idx = (uint32_t*)ws_get(ctx, Ws::ProtoIdx, idx2.size() * 4 + 64);
       if (!d_idx) return set_err(ctx, SPG_E_NOMEM, "bullet indices");
       SPG_HIP(ctx, hipMemcpyAsync(d_idx, idx2.data(), idx2.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     }
@@ -565,7 +565,7 @@ int dotproduct_log_prove(spg_ctx* ctx, ProverGens& g, Tr& t, Tape& tape, const F
     // for Cx: one device round trip fewer per proof
     // one page-locked copy: the Cx scalars (x, 0, blind_x), then the generator indices of every round
     const size_t sb = n2 * sizeof(Fq), ib = idx2.size() * 4;
-    Fq* d_s = (Fq*)ws_get(ctx, 20, sb + ib + 64);
+    Fq* d_s = (Fq*)ws_get(ctx, Ws::ProtoScalars, sb + ib + 64);
     uint8_t* stage = (uint8_t*)pinned_get(ctx, sb + ib + 64);
     if (!d_s || !stage || idx2.empty()) return set_err(ctx, SPG_E_NOMEM, "Cx");
     memcpy(stage, x.data(), n * sizeof(Fq));
@@ -745,8 +745,8 @@ int dotproduct_log_prove(spg_ctx* ctx, ProverGens& g, Tr& t, Tape& tape, const F
     // device rounds: d g_hat from the comb table as partial points (as Cx), r_delta h and beta on the host meanwhile;
     // the bucket form (device_msm_flat) where the comb does not apply
     int cper = 0, rc = 1;
-    if (mbk && delta_comb) {  // (the mapped region's Cx part and slot 26 are free again: Cx is done, the rounds are over)
-      Fq* d_s = (Fq*)ws_get(ctx, 26, n * sizeof(Fq) + 64);
+    if (mbk && delta_comb) {  // (the mapped region's Cx part and the ProtoDotScalars slot are free again: Cx is done, the rounds are over)
+      Fq* d_s = (Fq*)ws_get(ctx, Ws::ProtoDotScalars, n * sizeof(Fq) + 64);
       if (!d_s) return set_err(ctx, SPG_E_NOMEM, "delta scalars");
       if (use_dfin) {
         rc = bullet_delta_scalars(ctx, dfin.cw, (int)n, d, dfin.u, dfin.uinv, d_s);

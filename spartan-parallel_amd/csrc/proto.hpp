@@ -161,7 +161,7 @@ void bucket_finals(const Ext* bk, size_t B, int NB, Pt* out, const h::HExt* extr
 int device_msm_idx(spg_ctx* ctx, ProverGens& g, const std::vector<FqV>& scalars, const std::vector<std::vector<uint32_t>>& idx,
                    std::vector<Pt>* out);
 
-// ---- Hyrax commitments / PolyEvalProof on device polynomials (spark.hip) ----
+// ---- Hyrax commitments / PolyEvalProof on device polynomials (hyrax.hip) ----
 // PolyCommitmentGens::new(nv, label) as a view of a derived generator stream
 ProverGens gens_view(spg_gens* dev, size_t nv);
 // DensePolynomial::commit (no blinds) of 2^nv device scalars; rows of 2^(nv - nv/2) <= g.n_pc scalars. With
@@ -217,7 +217,7 @@ int spark_from_comm(spg_ctx* ctx, size_t B, size_t N, size_t cells, const std::v
                     size_t gens_nvy, size_t gens_nnz, size_t gens_batch, spg_spark** out);
 void spark_comm_append(const spg_spark* S, Tr& t);
 // sh.n > 1: one proof as an SPMD collective over the ranks of sh (every rank holds the whole dense representation
-// and returns the same bytes); see spark.hip "sharded proof"
+// and returns the same bytes); see spark.hip "Sharded proof"
 int spark_prove_core(spg_ctx* ctx, spg_spark* S, FqV ex, FqV ey, const FqV& evals, Tr& t, Tape& tape, Writer& w,
                      const Shard& sh = Shard());
 
@@ -266,7 +266,7 @@ struct spg_spark {
   spg::Fq* d_val = nullptr;     // [B][N]
   spg::Fq* d_comb_ops = nullptr;
   spg::Fq* d_comb_mem = nullptr;
-  size_t comb_ops_len = 0, comb_mem_len = 0;
+  size_t comb_ops_len = 0, comb_mem_len = 0, der_len = 0;  // (spark_shape.hpp; der_len: the derefs a prove commits to)
   spg_gens* dev = nullptr;
   spg::ProverGens g_ops, g_mem, g_der;
   std::vector<spg::Pt> comm_ops, comm_mem;  // SparseMatPolyCommitment

@@ -258,24 +258,6 @@ __global__ void __launch_bounds__(256) k_abc(const AbcDesc* __restrict__ ad, int
   ABC[d.out_off + (size_t)w * d.ni + brev(i, d.lg_ni)] = r;
 }
 
-// DensePolynomial::bound: out[i] = sum_j L[j] * Z[j * Rs + i], split over gridDim.y chunks of j
-__global__ void __launch_bounds__(256) k_bound_part(const Fq* __restrict__ Z, const Fq* __restrict__ L, uint32_t Ls,
-                                                    uint32_t Rs, uint32_t chunk, Fq* __restrict__ part) {
-  uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= Rs) return;
-  uint32_t j0 = blockIdx.y * chunk, j1 = min(Ls, j0 + chunk);
-  Fq acc = fq_zero();
-  for (uint32_t j = j0; j < j1; j++) acc = fq_add(acc, fq_mul(L[j], Z[(size_t)j * Rs + i]));
-  part[(size_t)blockIdx.y * Rs + i] = acc;
-}
-__global__ void k_sum_cols(const Fq* __restrict__ part, uint32_t S, uint32_t Rs, Fq* __restrict__ out) {
-  uint32_t i = blockIdx.x * 256 + threadIdx.x;
-  if (i >= Rs) return;
-  Fq acc = fq_zero();
-  for (uint32_t y = 0; y < S; y++) acc = fq_add(acc, part[(size_t)y * Rs + i]);
-  out[i] = acc;
-}
-
 // every witness polynomial's L.Z bound of one proof in two launches (instead of two per polynomial): job k's
 // partial rows are blocks [b0, b0 + nbx * S) of the first launch, its column sums blocks
 // [c0, c0 + ceil(Rs / kSumCols)) of the second
@@ -378,37 +360,7 @@ static size_t p2_pair_max() { return std::min<size_t>(kP1PairMax, (size_t)knob::
 
 // (ZKRounds, the ZK sumcheck round bookkeeping shared by phase 1 and phase 2: zk_rounds.hpp)
 
-// workspace slots used here (msm.hip uses 0..12, proto.hip 20..22)
-enum {
-  WS_AZ = 30, WS_BZ, WS_CZ, WS_Z, WS_ABC, WS_TP, WS_TQ, WS_TX, WS_EQRX, WS_EQP, WS_PART, WS_OUT3, WS_DESC,
-  WS_L, WS_BPART, WS_BOUT, WS_EV_RX, WS_EV_RY, WS_EV_PART, WS_EV_OUT, WS_EV_DESC, WS_C1, WS_C2, WS_TQ2, WS_TX2, WS_ABC2,
-  WS_EQQ  // (56; spark.hip starts at 60)
-};
-// the cubic Lagrange basis on the nodes 0..3 at r (a pair's round j + 1 from its grid at t = r_j)
-static void lagrange4(const Fq& r, Fq L[4]) {
-  static const Fq inv2 = fq_inv(fq_from_u64(2)), inv6 = fq_inv(fq_from_u64(6));
-  const Fq a0 = r, a1 = fq_sub(r, fq_one()), a2 = fq_sub(a1, fq_one()), a3 = fq_sub(a2, fq_one());
-  const Fq a01 = fq_mul(a0, a1), a23 = fq_mul(a2, a3);
-  L[0] = fq_neg(fq_mul(fq_mul(a1, a23), inv6));
-  L[1] = fq_mul(fq_mul(a0, a23), inv2);
-  L[2] = fq_neg(fq_mul(fq_mul(a01, a3), inv2));
-  L[3] = fq_mul(fq_mul(a01, a2), inv6);
-}
-// a pair's posted grid (k_phase1_pair / k_phase2_pair) -> round j's (e0, e2, e3) and, once r_j is drawn, round j + 1's
-static void pair_round_j(const Fq ev[15], Fq ej[3]) {
-  ej[0] = fq_add(ev[0], ev[12]);
-  ej[1] = fq_add(ev[2], ev[13]);
-  ej[2] = fq_add(ev[3], ev[14]);
-}
-static void pair_round_j1(const Fq ev[15], const Fq& r_j, Fq ej1[3]) {
-  Fq L[4];
-  lagrange4(r_j, L);
-  for (int y = 0; y < 3; y++) {
-    Fq acc = fq_zero();
-    for (int k = 0; k < 4; k++) acc = fq_add(acc, fq_mul(L[k], ev[4 * y + k]));
-    ej1[y] = acc;
-  }
-}
+// (a pair's posted grid -> round j's and round j + 1's (e0, e2, e3): pair_round_j, pair_round_j1 of hostmath.hpp)
 
 // ------------------------------------------------------------------------------------ the R1CS prover
 // R1CSProof::prove (r1csproof.rs). Prover::run_stages calls the stages in protocol order: setup_tables (Z, Az, Bz, Cz
@@ -585,7 +537,7 @@ struct Prover {
   uint8_t* desc_dev = nullptr;
   template <class D>
   int stage_desc(const std::vector<D>& v, D** dptr) {
-    if (!desc_dev && !(desc_dev = (uint8_t*)ws_get(ctx, WS_DESC, 1 << 20)))
+    if (!desc_dev && !(desc_dev = (uint8_t*)ws_get(ctx, Ws::R1csDesc, 1 << 20)))
       return set_err(ctx, SPG_E_NOMEM, "descriptor buffer");
     const size_t bytes = v.size() * sizeof(D), off = (desc_cur + 255) & ~(size_t)255;
     if (off + bytes > (1 << 20)) return set_err(ctx, SPG_E_ARG, "too many descriptors");
@@ -834,7 +786,7 @@ int Prover::run_stages() {
   if (!rc && !knob::z_side()) rc = zf.queue();
   if (rc) return rc;
   lp.lap("setup");
-  cy.partials = (Fq*)ws_get(ctx, WS_PART, std::max(3 * (size_t)kScGridMax, kP1PairMax) * sizeof(Fq) + 64);
+  cy.partials = (Fq*)ws_get(ctx, Ws::R1csPart, std::max(3 * (size_t)kScGridMax, kP1PairMax) * sizeof(Fq) + 64);
   if (!cy.partials) return set_err(ctx, SPG_E_NOMEM, "partials");
   FqV r1;  // phase 1's challenges in round order: x, q, p
   if ((rc = run_phase1(zf, r1))) return rc;
@@ -845,7 +797,7 @@ int Prover::run_stages() {
   cy.rx.assign(rx_rev.rbegin(), rx_rev.rend());
   cy.rq.assign(cy.rq_rev.rbegin(), cy.rq_rev.rend());
   // eq(rx) of phase 2 depends on phase 1's challenges alone: on the device while the host runs the sigma protocols
-  cy.eq_rx = (Fq*)ws_get(ctx, WS_EQRX, (sizeof(Fq) << sh.nx) + 64);
+  cy.eq_rx = (Fq*)ws_get(ctx, Ws::R1csEqRx, (sizeof(Fq) << sh.nx) + 64);
   if (!cy.eq_rx) return set_err(ctx, SPG_E_NOMEM, "eq(rx)");
   if ((rc = eq_table(ctx, cy.rx, cy.eq_rx))) return rc;
   sigma1();
@@ -920,15 +872,15 @@ int Prover::setup_desc(ZFill& zf, bool want_z) {
   cy.Zp = pqx_shape(sh.l_proofs, nws, sh.l_inputs, npow2(P), max_np, npow2(nws), Y);
   const size_t ztot = cy.Zp.total;
   if (want_z) {
-    cy.Zp.d = (Fq*)ws_get(ctx, WS_Z, ztot * sizeof(Fq) + 64);
+    cy.Zp.d = (Fq*)ws_get(ctx, Ws::R1csZ, ztot * sizeof(Fq) + 64);
     if (!cy.Zp.d) return set_err(ctx, SPG_E_NOMEM, "Z table");
   }
   PqxDev& Az = cy.Az;
   Az = pqx_shape(sh.l_proofs, 1, sh.l_cons, npow2(P), max_np, 1, sh.num_cons);
   const size_t atot = Az.total;
-  Az.d = (Fq*)ws_get(ctx, WS_AZ, atot * sizeof(Fq) + 64);
-  cy.Bz = (Fq*)ws_get(ctx, WS_BZ, atot * sizeof(Fq) + 64);
-  cy.Cz = (Fq*)ws_get(ctx, WS_CZ, atot * sizeof(Fq) + 64);
+  Az.d = (Fq*)ws_get(ctx, Ws::R1csAz, atot * sizeof(Fq) + 64);
+  cy.Bz = (Fq*)ws_get(ctx, Ws::R1csBz, atot * sizeof(Fq) + 64);
+  cy.Cz = (Fq*)ws_get(ctx, Ws::R1csCz, atot * sizeof(Fq) + 64);
   if (!Az.d || !cy.Bz || !cy.Cz) return set_err(ctx, SPG_E_NOMEM, "Az/Bz/Cz");
   // every descriptor of the setup kernels (Z fill, Az/Bz/Cz) goes up in one host-to-device copy
   ZDesc* dz = nullptr;
@@ -992,9 +944,9 @@ int Prover::setup_tau() {
   FqV tau_q = t.challenges("challenge_tau_q", nq);
   FqV tau_x = t.challenges("challenge_tau_x", nx);
   if (knob::debug_tr()) fprintf(stderr, "[prove] r1cs P=%zu np=%zu nq=%zu nx=%zu tau_x0 %08x\n", (size_t)P, (size_t)np, (size_t)nq, (size_t)nx, tau_x[0].l[0]);
-  cy.Ap = (Fq*)ws_get(ctx, WS_TP, (sizeof(Fq) << np) + 64);
-  cy.Aq = (Fq*)ws_get(ctx, WS_TQ, (sizeof(Fq) << nq) + 64);
-  cy.Ax = (Fq*)ws_get(ctx, WS_TX, (sizeof(Fq) << nx) + 64);
+  cy.Ap = (Fq*)ws_get(ctx, Ws::R1csTp, (sizeof(Fq) << np) + 64);
+  cy.Aq = (Fq*)ws_get(ctx, Ws::R1csTq, (sizeof(Fq) << nq) + 64);
+  cy.Ax = (Fq*)ws_get(ctx, Ws::R1csTx, (sizeof(Fq) << nx) + 64);
   if (!cy.Ap || !cy.Aq || !cy.Ax) return set_err(ctx, SPG_E_NOMEM, "eq tables");
   return eq_tables(ctx, {{tau_p, cy.Ap}, {tau_q, cy.Aq}, {tau_x, cy.Ax}});
 }
@@ -1045,7 +997,7 @@ int Prover::p1_to_compact(Phase1& s) {
   Ct.d = cy.Cz;
   int rc = gather_first({&cy.Az, &Bt, &Ct}, full);
   if (rc) return rc;
-  Fq* buf = (Fq*)ws_get(ctx, WS_C1, 3 * P * sizeof(Fq) + 64);
+  Fq* buf = (Fq*)ws_get(ctx, Ws::R1csC1, 3 * P * sizeof(Fq) + 64);
   if (!buf) return set_err(ctx, SPG_E_NOMEM, "compact tables");
   for (int i = 0; i < 3; i++)
     SPG_HIP(ctx, hipMemcpyAsync(buf + i * P, full[i].data(), P * sizeof(Fq), hipMemcpyHostToDevice, ctx->stream));
@@ -1260,8 +1212,8 @@ int Prover::run_phase1(ZFill& zf, FqV& r_all) {
   s.T = &cy.Az, s.TB = cy.Bz, s.TC = cy.Cz;
   s.Aq = cy.Aq, s.Ax = cy.Ax, s.Ap_l = cy.Ap + p0;
   if (knob::sc_fuse()) {
-    s.Aq2 = (Fq*)ws_get(ctx, WS_TQ2, (sizeof(Fq) << nq) + 64);
-    s.Ax2 = (Fq*)ws_get(ctx, WS_TX2, (sizeof(Fq) << nx) + 64);
+    s.Aq2 = (Fq*)ws_get(ctx, Ws::R1csTq2, (sizeof(Fq) << nq) + 64);
+    s.Ax2 = (Fq*)ws_get(ctx, Ws::R1csTx2, (sizeof(Fq) << nx) + 64);
     if (!s.Aq2 || !s.Ax2) return set_err(ctx, SPG_E_NOMEM, "eq tables");
   }
   int rc = s.rounds && nx + nq == 0 ? p1_to_compact(s) : 0;
@@ -1324,7 +1276,7 @@ int Prover::phase2_prep(ZFill& zf) {
   ABC.num_proofs.assign(P, 1);
   ABC.num_inputs.assign(num_inputs.begin() + Ab0, num_inputs.end());
   const size_t btot = ABC.total;
-  ABC.d = (Fq*)ws_get(ctx, WS_ABC, btot * sizeof(Fq) + 64);
+  ABC.d = (Fq*)ws_get(ctx, Ws::R1csAbc, btot * sizeof(Fq) + 64);
   if (!ABC.d) return set_err(ctx, SPG_E_NOMEM, "ABC");
   int rc = 0;
   {
@@ -1356,7 +1308,7 @@ int Prover::phase2_prep(ZFill& zf) {
   // challenge, each a read-write pass over the live rows
   const FqV& rq_rev = cy.rq_rev;
   if (knob::q_bound_all() && rq_rev.size() >= 2) {
-    Fq* eq_q = (Fq*)ws_get(ctx, WS_EQQ, (sizeof(Fq) << rq_rev.size()) + 64);
+    Fq* eq_q = (Fq*)ws_get(ctx, Ws::R1csEqQ, (sizeof(Fq) << rq_rev.size()) + 64);
     if (!eq_q) return set_err(ctx, SPG_E_NOMEM, "eq(rq)");
     rc = eq_table(ctx, rq_rev, eq_q);
     if (!rc) rc = pqx_bound_q_all(ctx, cy.Zp, eq_q, rq_rev.size());
@@ -1365,7 +1317,7 @@ int Prover::phase2_prep(ZFill& zf) {
     for (size_t k = 0; k < rq_rev.size(); k++)
       if ((rc = pqx_bound(ctx, cy.Zp, nullptr, nullptr, rq_rev[k], MODE_Q))) return rc;
   }
-  cy.eq_p = (Fq*)ws_get(ctx, WS_EQP, (sizeof(Fq) << sh.np) + 64);
+  cy.eq_p = (Fq*)ws_get(ctx, Ws::R1csEqP, (sizeof(Fq) << sh.np) + 64);
   if (!cy.eq_p) return set_err(ctx, SPG_E_NOMEM, "eq(rp)");
   return eq_table(ctx, cy.rp, cy.eq_p);
 }
@@ -1393,7 +1345,7 @@ int Prover::p2_to_compact(Phase2& s) {
   std::vector<std::vector<Fq>> full;
   int rc = single ? gather_first({&cy.Zp}, full) : gather_first({&cy.Zp, &cy.ABC}, full);
   if (rc) return rc;
-  Fq* buf = (Fq*)ws_get(ctx, WS_C2, 2 * P * sizeof(Fq) + 64);
+  Fq* buf = (Fq*)ws_get(ctx, Ws::R1csC2, 2 * P * sizeof(Fq) + 64);
   if (!buf) return set_err(ctx, SPG_E_NOMEM, "compact tables");
   SPG_HIP(ctx, hipMemcpyAsync(buf, full[0].data(), P * sizeof(Fq), hipMemcpyHostToDevice, st));
   if (single) {  // the shared ABC keeps its single (0,0,0,0) element
@@ -1551,7 +1503,7 @@ int Prover::run_phase2() {
   // -- a sharded rank whose first instance is narrower takes the separate fold
   s.fuse2 = knob::sc_fuse() && (!sh.single || num_inputs[p0] == num_inputs[0]);
   if (s.fuse2 && sh.single) {
-    s.ABC2 = (Fq*)ws_get(ctx, WS_ABC2, cy.ABC.total * sizeof(Fq) + 64);
+    s.ABC2 = (Fq*)ws_get(ctx, Ws::R1csAbc2, cy.ABC.total * sizeof(Fq) + 64);
     if (!s.ABC2) return set_err(ctx, SPG_E_NOMEM, "ABC");
   }
   int rc = s.rounds && ny + nw == 0 ? p2_to_compact(s) : 0;
@@ -1634,9 +1586,9 @@ int Prover::lz_bound(std::vector<PolyRef>& polys, size_t lz_total, std::vector<F
     right_tables(polys, rr_of);
     return 0;
   }
-  Fq* dL = (Fq*)ws_get(ctx, WS_L, totL * sizeof(Fq) + 64);
-  Fq* dpart = (Fq*)ws_get(ctx, WS_BPART, totP * sizeof(Fq) + 64);
-  Fq* dout = (Fq*)ws_get(ctx, WS_BOUT, lz_total * sizeof(Fq) + 64);
+  Fq* dL = (Fq*)ws_get(ctx, Ws::R1csL, totL * sizeof(Fq) + 64);
+  Fq* dpart = (Fq*)ws_get(ctx, Ws::R1csBoundPart, totP * sizeof(Fq) + 64);
+  Fq* dout = (Fq*)ws_get(ctx, Ws::R1csBoundOut, lz_total * sizeof(Fq) + 64);
   if (!dL || !dpart || !dout) return set_err(ctx, SPG_E_NOMEM, "bound");
   if (!all_mine) SPG_HIP(ctx, hipMemsetAsync(dout, 0, lz_total * sizeof(Fq), st));  // other ranks' ranges
   // one eq table per distinct rl (polynomials of one shape share it)
@@ -2318,8 +2270,8 @@ extern "C" int spg_r1cs_multi_evaluate(spg_ctx* ctx, const spg_r1cs_inst* inst, 
   FqV vx(rx_len), vy(ry_len);
   for (size_t i = 0; i < rx_len; i++) vx[i] = ld_fq(rx + 4 * i);
   for (size_t i = 0; i < ry_len; i++) vy[i] = ld_fq(ry + 4 * i);
-  Fq* erx = (Fq*)ws_get(ctx, WS_EV_RX, (sizeof(Fq) << rx_len) + 64);
-  Fq* ery = (Fq*)ws_get(ctx, WS_EV_RY, (sizeof(Fq) << ry_len) + 64);
+  Fq* erx = (Fq*)ws_get(ctx, Ws::R1csEvRx, (sizeof(Fq) << rx_len) + 64);
+  Fq* ery = (Fq*)ws_get(ctx, Ws::R1csEvRy, (sizeof(Fq) << ry_len) + 64);
   std::vector<MatDesc> md(Pm);
   std::vector<uint32_t> rr(2 * Pm);
   size_t maxrows = 1;
@@ -2335,9 +2287,9 @@ extern "C" int spg_r1cs_multi_evaluate(spg_ctx* ctx, const spg_r1cs_inst* inst, 
     rows += 3.0 * (rr[2 * p + 1] - rr[2 * p]);
   }
   const unsigned nblk = blocks_for(maxrows);
-  Fq* part = (Fq*)ws_get(ctx, WS_EV_PART, 3 * Pm * nblk * sizeof(Fq) + 64);
-  Fq* dout = (Fq*)ws_get(ctx, WS_EV_OUT, 3 * Pm * sizeof(Fq) + 64);
-  uint8_t* ddesc = (uint8_t*)ws_get(ctx, WS_EV_DESC, Pm * (sizeof(MatDesc) + 8) + 64);
+  Fq* part = (Fq*)ws_get(ctx, Ws::R1csEvPart, 3 * Pm * nblk * sizeof(Fq) + 64);
+  Fq* dout = (Fq*)ws_get(ctx, Ws::R1csEvOut, 3 * Pm * sizeof(Fq) + 64);
+  uint8_t* ddesc = (uint8_t*)ws_get(ctx, Ws::R1csEvDesc, Pm * (sizeof(MatDesc) + 8) + 64);
   if (!erx || !ery || !part || !dout || !ddesc) {
     int rc = set_err(ctx, SPG_E_NOMEM, "multi_evaluate");
     FqV none(3 * Pm);

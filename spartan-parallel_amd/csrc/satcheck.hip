@@ -14,7 +14,6 @@ namespace spg {
 
 namespace {
 
-static const size_t kWsSatRec = 133, kWsSatDesc = 134;
 
 __device__ __forceinline__ Fq sat_ld(const Fq* p) {  // two 16-byte accesses (the tables are 32-byte aligned)
   const uint4 lo = ((const uint4*)p)[0], hi = ((const uint4*)p)[1];
@@ -69,12 +68,12 @@ int sat_check_run(spg_ctx* ctx, const std::vector<SatDesc>& d, uint64_t total, c
   if (d.empty() || d.size() >= 0x7fffffffULL || blocks_needed(total) > 0x7fffffffULL)
     return set_err(ctx, SPG_E_ARG, "sat_check: domain too large");
   hipStream_t s = ctx->stream;
-  unsigned long long* rec = (unsigned long long*)ws_get(ctx, kWsSatRec, 64);
+  unsigned long long* rec = (unsigned long long*)ws_get(ctx, Ws::SatRec, 64);
   if (!rec) return set_err(ctx, SPG_E_NOMEM, "sat_check record");
   SatArgs a{};
   a.P = (int)d.size();
   if (d.size() > (size_t)kSatMaxP) {
-    SatDesc* dd = (SatDesc*)ws_get(ctx, kWsSatDesc, d.size() * sizeof(SatDesc) + 64);
+    SatDesc* dd = (SatDesc*)ws_get(ctx, Ws::SatDesc, d.size() * sizeof(SatDesc) + 64);
     if (!dd) return set_err(ctx, SPG_E_NOMEM, "sat_check descriptors");
     // (d outlives the synchronisation below)
     SPG_HIP(ctx, hipMemcpyAsync(dd, d.data(), d.size() * sizeof(SatDesc), hipMemcpyHostToDevice, s));

@@ -22,8 +22,6 @@
 namespace spg {
 namespace {
 
-constexpr size_t kWsSeamPart = 112, kWsSeamTmp = 113;  // (110, 111: the Pqx descriptors, sumcheck.hip)
-constexpr size_t kWsSeamRev = 131, kWsSeamRevDesc = 132, kWsSeamEq = 133;
 
 // bound_poly_var_bot: out[i] = in[2i] + r (in[2i + 1] - in[2i]); out-of-place (in place, a workgroup's outputs would
 // overwrite entries another workgroup still reads)
@@ -79,7 +77,7 @@ int d2h(spg_ctx* ctx, void* dst, const void* src, size_t bytes) {
 // (e0, e2, e3) of a prove_cubic round over A, B, C of equal even length
 int cubic_round(spg_ctx* ctx, const spg_buf* A, const spg_buf* B, const spg_buf* C, Fq out3[3]) {
   const size_t half = A->n / 2;
-  Fq* partials = (Fq*)ws_get(ctx, kWsSeamPart, 3 * kScGridMax * sizeof(Fq) + 64);
+  Fq* partials = (Fq*)ws_get(ctx, Ws::SeamPart, 3 * kScGridMax * sizeof(Fq) + 64);
   if (!partials) return set_err(ctx, SPG_E_NOMEM, "cubic round partials");
   return cubic_eval(ctx, A->d, B->d, C->d, half, partials, out3);
 }
@@ -102,7 +100,7 @@ extern "C" int spg_buf_bound_bot(spg_ctx* ctx, spg_buf* b, const uint64_t* r_mon
   if (!ctx || !b || !r_mont) return SPG_E_ARG;
   if (b->n < 2 || (b->n & 1)) return spg::set_err(ctx, SPG_E_ARG, "spg_buf_bound_bot: length must be even and >= 2");
   const size_t n = b->n / 2;
-  Fq* tmp = (Fq*)spg::ws_get(ctx, spg::kWsSeamTmp, n * sizeof(Fq) + 64);
+  Fq* tmp = (Fq*)spg::ws_get(ctx, spg::Ws::SeamTmp, n * sizeof(Fq) + 64);
   if (!tmp) return spg::set_err(ctx, SPG_E_NOMEM, "spg_buf_bound_bot");
   hipLaunchKernelGGL(spg::k_fold_bot, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, b->d, tmp, n,
                      spg::ld_fq(r_mont));
@@ -121,7 +119,7 @@ extern "C" int spg_buf_evaluate(spg_ctx* ctx, const spg_buf* b, const uint64_t* 
   if (!ctx || !b || !out_mont || (!r_mont && ell)) return SPG_E_ARG;
   if (ell >= 64 || b->n != ((size_t)1 << ell))
     return spg::set_err(ctx, SPG_E_ARG, "spg_buf_evaluate: the vector must hold 2^ell scalars");
-  Fq* tmp = (Fq*)spg::ws_get(ctx, spg::kWsSeamTmp, b->n * sizeof(Fq) + 64);
+  Fq* tmp = (Fq*)spg::ws_get(ctx, spg::Ws::SeamTmp, b->n * sizeof(Fq) + 64);
   if (!tmp) return spg::set_err(ctx, SPG_E_NOMEM, "spg_buf_evaluate");
   SPG_HIP(ctx, hipMemcpyAsync(tmp, b->d, b->n * sizeof(Fq), hipMemcpyDeviceToDevice, ctx->stream));
   size_t len = b->n;
@@ -269,10 +267,10 @@ int pqx_new_rev_dev(spg_ctx* ctx, const char* what, const Fq* z, bool have_z, si
     while (((size_t)1 << li) < num_inputs[p]) li++;
     rd[p] = spg::RevDesc{(uint32_t)T.off[p], (uint32_t)lq, (uint32_t)li, (uint32_t)num_witness_secs};
   }
-  spg::RevDesc* d_rd = (spg::RevDesc*)spg::ws_get(ctx, spg::kWsSeamRevDesc, rd.size() * sizeof(spg::RevDesc) + 64);
+  spg::RevDesc* d_rd = (spg::RevDesc*)spg::ws_get(ctx, spg::Ws::SeamRevDesc, rd.size() * sizeof(spg::RevDesc) + 64);
   if (!d_rd) fail(SPG_E_NOMEM, "descriptors");
   if (!rc && z_host) {  // the host form: one upload in the caller's order, reordered on the device
-    Fq* up = (Fq*)spg::ws_get(ctx, spg::kWsSeamRev, T.total * sizeof(Fq) + 64);
+    Fq* up = (Fq*)spg::ws_get(ctx, spg::Ws::SeamRev, T.total * sizeof(Fq) + 64);
     if (!up) fail(SPG_E_NOMEM, "upload buffer");
     else if (hipMemcpyAsync(up, z_host, T.total * sizeof(Fq), hipMemcpyHostToDevice, ctx->stream) != hipSuccess)
       fail(SPG_E_HIP, "upload");
@@ -400,7 +398,7 @@ extern "C" int spg_pqx_bound_rq(spg_ctx* ctx, spg_pqx* h, const uint64_t* rq_mon
   int rc = 0;
   spg::timer_start(ctx);
   if (n >= 2) {
-    Fq* E = (Fq*)spg::ws_get(ctx, spg::kWsSeamEq, (sizeof(Fq) << n) + 64);
+    Fq* E = (Fq*)spg::ws_get(ctx, spg::Ws::SeamEq, (sizeof(Fq) << n) + 64);
     if (!E) return spg::set_err(ctx, SPG_E_NOMEM, "spg_pqx_bound_rq");
     std::vector<Fq> r(n);
     for (size_t k = 0; k < n; k++) r[k] = spg::ld_fq(rq_mont + 4 * k);
@@ -423,7 +421,7 @@ extern "C" int spg_pqx_evaluate(spg_ctx* ctx, const spg_pqx* h, const uint64_t* 
                                 uint64_t* out_mont) {
   if (!ctx || !h || !out_mont || (np && !rp) || (nq && !rq) || (nw && !rw) || (nx && !rx)) return SPG_E_ARG;
   spg::PqxDev C = h->T;  // the clone: same descriptors and sizes, its own copy of the entries
-  C.d = (Fq*)spg::ws_get(ctx, spg::kWsSeamTmp, C.total * sizeof(Fq) + 64);
+  C.d = (Fq*)spg::ws_get(ctx, spg::Ws::SeamTmp, C.total * sizeof(Fq) + 64);
   if (!C.d) return spg::set_err(ctx, SPG_E_NOMEM, "spg_pqx_evaluate");
   SPG_HIP(ctx, hipMemcpyAsync(C.d, h->T.d, C.total * sizeof(Fq), hipMemcpyDeviceToDevice, ctx->stream));
   const struct {
@@ -479,7 +477,7 @@ extern "C" int spg_phase1_round_evals(spg_ctx* ctx, const spg_buf* Ap, const spg
     if (proof_len % sc_np[p] || cons_len % sc_nc[p])
       return spg::set_err(ctx, SPG_E_ARG, "phase-1 round: table sizes exceed the eq tables");
   }
-  Fq* partials = (Fq*)spg::ws_get(ctx, spg::kWsSeamPart,
+  Fq* partials = (Fq*)spg::ws_get(ctx, spg::Ws::SeamPart,
                                   std::max(3 * (size_t)spg::kScGridMax, spg::kP1PairMax) * sizeof(Fq) + 64);
   if (!partials) return spg::set_err(ctx, SPG_E_NOMEM, "phase-1 round partials");
   Fq e[3];
@@ -519,7 +517,7 @@ extern "C" int spg_phase2_round_evals(spg_ctx* ctx, const spg_buf* A, const spg_
   std::vector<size_t> sc_ni = TZ.num_inputs;
   for (size_t p = 0; p < sc_ni.size(); p++)
     if (mode == spg::MODE_X && sc_ni[p] > 1) sc_ni[p] /= 2;
-  Fq* partials = (Fq*)spg::ws_get(ctx, spg::kWsSeamPart,
+  Fq* partials = (Fq*)spg::ws_get(ctx, spg::Ws::SeamPart,
                                   std::max(3 * (size_t)spg::kScGridMax, spg::kP1PairMax) * sizeof(Fq) + 64);
   if (!partials) return spg::set_err(ctx, SPG_E_NOMEM, "phase-2 round partials");
   Fq e[3];

@@ -271,8 +271,8 @@ struct CQ {
     }
     // the one-launch batch path of commit_rows only (rows wider than the latency path, one chunk)
     if (its.empty() || R <= 256 || R > g.n_pc || total / R > ((size_t)1 << 24) / R) return 0;
-    Fq* d = (Fq*)ws_get(ctx, 92, total * sizeof(Fq) + 64);
-    uint8_t* out = (uint8_t*)ws_get(ctx, 93, 32 * (total / R) + 64);
+    Fq* d = (Fq*)ws_get(ctx, Ws::SnarkEarlyIn, total * sizeof(Fq) + 64);
+    uint8_t* out = (uint8_t*)ws_get(ctx, Ws::SnarkEarlyOut, 32 * (total / R) + 64);
     if (!d || !out) return set_err(ctx, SPG_E_NOMEM, "early commit staging");
     SPG_HIP(ctx, hipEventRecord(ctx->ev_pre, ctx->stream));  // flush()'s side stream starts from here
     size_t o = 0;
@@ -282,8 +282,7 @@ struct CQ {
     }
     // the comb rows with halved scalars: flush() encodes the points' doubles on the host in one batch (~50 us on the
     // pool for 1024 rows) instead of a k_compress_ext launch (~140 us of dependent squarings per lane)
-    // slot 95 (94 is unused)
-    Ext* ext = knob::halved_enc() && total / R >= kHalvedMin ? (Ext*)ws_get(ctx, 95, sizeof(Ext) * (total / R) + 64) : nullptr;
+    Ext* ext = knob::halved_enc() && total / R >= kHalvedMin ? (Ext*)ws_get(ctx, Ws::SnarkEarlyExt, sizeof(Ext) * (total / R) + 64) : nullptr;
     int rc = ext ? msm_comb(ctx, g.dev, 0, d, R, total / R, nullptr, nullptr, -1, ext, true) : kCombSkip;
     if (rc == kCombSkip) {
       ext = nullptr;
@@ -303,7 +302,7 @@ struct CQ {
     size_t total = 0;
     for (auto& it : items)
       if (!is_early(it)) total += it.len;
-    Fq* d = (Fq*)ws_get(ctx, 91, total * sizeof(Fq) + 64);
+    Fq* d = (Fq*)ws_get(ctx, Ws::SnarkRowsIn, total * sizeof(Fq) + 64);
     if (total && !d) return set_err(ctx, SPG_E_NOMEM, "commit staging");
     rows.assign(widths.size(), {});
     jobs.clear();

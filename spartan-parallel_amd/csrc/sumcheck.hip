@@ -1156,7 +1156,7 @@ int dev_eq_table(spg_ctx* ctx, const Fq* r, int ell, Fq* out, const KBlob* blob,
     launch(a, out, n, blob != nullptr);
   } else {  // eq(r) = eq(r_hi) (x) eq(r_lo): two small tables, then one multiplication per entry
     const int hb = ell / 2, lb = ell - hb;
-    Fq* t = (Fq*)ws_get(ctx, 16, (((size_t)1 << hb) + ((size_t)1 << lb)) * sizeof(Fq) + 64);
+    Fq* t = (Fq*)ws_get(ctx, Ws::ScEqHalves, (((size_t)1 << hb) + ((size_t)1 << lb)) * sizeof(Fq) + 64);
     if (!t) return set_err(ctx, SPG_E_NOMEM, "eq table");
     Fq* hi = t;
     Fq* lo = t + ((size_t)1 << hb);
@@ -1244,8 +1244,7 @@ static void pqx_fill_args(const PqxDev& T, PqxArgs& a, std::vector<PqxInst>& v) 
 }
 // the descriptors into the kernel arguments, or - more than kMaxP instances - into device memory (workspace slot;
 // stream-ordered, so the next launch's copy into the same slot lands after this launch has read it)
-enum : size_t { kWsPqxA = 110, kWsPqxB = 111 };
-static int pqx_pack(spg_ctx* ctx, const std::vector<PqxInst>& v, PqxArgs& a, size_t slot) {
+static int pqx_pack(spg_ctx* ctx, const std::vector<PqxInst>& v, PqxArgs& a, Ws slot) {
   a.ext = nullptr;
   for (size_t p = 0; p < v.size() && p < (size_t)kMaxP; p++) a.in[p] = v[p];
   if (v.size() <= (size_t)kMaxP) return 0;
@@ -1280,7 +1279,7 @@ int phase1_eval(spg_ctx* ctx, const PqxDev& T, int mode, size_t proof_len, size_
     for (size_t p = 0; p < P; p++) v[p].fstride = fold->stride[p];
   }
   if (dom >= 0xffffffffULL) return set_err(ctx, SPG_E_ARG, "phase-1 domain too large");
-  if (int rc = pqx_pack(ctx, v, a, kWsPqxA)) return rc;
+  if (int rc = pqx_pack(ctx, v, a, Ws::PqxA)) return rc;
   const bool quad = dom <= sc_quad_max();
   const int nb = quad ? grid_for((uint32_t)(4 * dom)) : grid_for((uint32_t)dom);
   // x-mode rounds over rows of >= 128 points: the row-factored kernel, J points per lane (SPG_P1_ROWS=0: off)
@@ -1359,7 +1358,7 @@ int phase1_pair(spg_ctx* ctx, const PqxDev& T, const P1Pair& pp, Fq* partials, F
     dom += pp.rows[p] * pp.cols[p];
   }
   if (dom == 0 || dom > kP1PairMax) return set_err(ctx, SPG_E_ARG, "phase-1 pair: domain size");
-  if (int rc = pqx_pack(ctx, v, A.a, kWsPqxA)) return rc;
+  if (int rc = pqx_pack(ctx, v, A.a, Ws::PqxA)) return rc;
   A.mode = pp.mode;
   A.total = (uint32_t)dom;
   A.c = (uint32_t)pp.c;
@@ -1412,7 +1411,7 @@ int phase1_fold2x(spg_ctx* ctx, const PqxDev& T, const P1Pair& pp) {
     dom += pp.rows[p] * pp.cols[p];
   }
   if (dom >= 0xffffffffULL) return set_err(ctx, SPG_E_ARG, "phase-1 fold2x: domain size");
-  if (int rc = pqx_pack(ctx, v, A.a, kWsPqxA)) return rc;
+  if (int rc = pqx_pack(ctx, v, A.a, Ws::PqxA)) return rc;
   A.mode = pp.mode;
   A.total = (uint32_t)dom;
   A.nf = 2;
@@ -1458,8 +1457,8 @@ static int p2_args(spg_ctx* ctx, const PqxDev& AB, const PqxDev& Z, const P2Pair
   }
   if (dom == 0 || dom > (fold ? (size_t)0xffffffffULL : (size_t)kP1PairMax))
     return set_err(ctx, SPG_E_ARG, "phase-2 pair: domain size");
-  if (int rc = pqx_pack(ctx, va, A.ab, kWsPqxA)) return rc;
-  if (int rc = pqx_pack(ctx, vz, A.zz, kWsPqxB)) return rc;
+  if (int rc = pqx_pack(ctx, va, A.ab, Ws::PqxA)) return rc;
+  if (int rc = pqx_pack(ctx, vz, A.zz, Ws::PqxB)) return rc;
   A.total = (uint32_t)dom;
   A.nf = fold ? 2 : pp.nf;
   A.r1 = pp.r1;
@@ -1531,8 +1530,8 @@ int phase2_eval(spg_ctx* ctx, const PqxDev& AB, const PqxDev& Z, int mode, size_
     for (size_t p = 0; p < vab.size(); p++) vab[p].fstride = fold->a.stride[p];
     for (size_t p = 0; p < P; p++) vz[p].fstride = fold->z.stride[p];
   }
-  if (int rc = pqx_pack(ctx, vab, ab, kWsPqxA)) return rc;
-  if (int rc = pqx_pack(ctx, vz, zz, kWsPqxB)) return rc;
+  if (int rc = pqx_pack(ctx, vab, ab, Ws::PqxA)) return rc;
+  if (int rc = pqx_pack(ctx, vz, zz, Ws::PqxB)) return rc;
   const bool quad = dom <= sc_quad_max();
   const int nb = quad ? grid_for((uint32_t)(4 * dom)) : grid_for((uint32_t)dom);
   const Fold2Arg fa = fold ? fold->arg : Fold2Arg{};
@@ -1556,7 +1555,7 @@ int phase2_eval(spg_ctx* ctx, const PqxDev& AB, const PqxDev& Z, int mode, size_
 
 // DensePolynomialPqx::bound_poly(r, mode) applied to up to three tables of identical shape (T[0] owns shape)
 // host bookkeeping of one Pqx fold (the reference's field updates) and the kernel arguments; dom = entries
-static int pqx_prepare(spg_ctx* ctx, PqxDev& T, int mode, PqxArgs& a, size_t& dom, size_t slot) {
+static int pqx_prepare(spg_ctx* ctx, PqxDev& T, int mode, PqxArgs& a, size_t& dom, Ws slot) {
   size_t P = std::min(T.num_instances, T.zlen);
   // host-side size bookkeeping first (mirrors the reference's field updates)
   if (mode == MODE_P) {
@@ -1609,7 +1608,7 @@ static int pqx_prepare(spg_ctx* ctx, PqxDev& T, int mode, PqxArgs& a, size_t& do
 int pqx_bound(spg_ctx* ctx, PqxDev& T, Fq* d1, Fq* d2, const Fq& r, int mode, Fq* side, size_t side_len) {
   PqxArgs a;
   size_t dom = 0;
-  int rc = pqx_prepare(ctx, T, mode, a, dom, kWsPqxA);
+  int rc = pqx_prepare(ctx, T, mode, a, dom, Ws::PqxA);
   if (rc) return rc;
   const size_t side_half = side ? side_len / 2 : 0;
   if (dom || side_half) {
@@ -1659,8 +1658,8 @@ int pqx_fold_plan(spg_ctx* ctx, PqxDev& T, int mode, FoldPlan* fp) {
 int pqx_bound2(spg_ctx* ctx, PqxDev& TA, PqxDev& TB, const Fq& r, int mode) {
   PqxArgs a, b;
   size_t da = 0, db = 0;
-  int rc = pqx_prepare(ctx, TA, mode, a, da, kWsPqxA);
-  if (!rc) rc = pqx_prepare(ctx, TB, mode, b, db, kWsPqxB);
+  int rc = pqx_prepare(ctx, TA, mode, a, da, Ws::PqxA);
+  if (!rc) rc = pqx_prepare(ctx, TB, mode, b, db, Ws::PqxB);
   if (rc) return rc;
   if (da + db) {
     KScope ks(ctx, "sc_fold", 96.0 * (double)(da + db));
@@ -1701,7 +1700,7 @@ int pqx_bound_q_all(spg_ctx* ctx, PqxDev& T, const Fq* E, size_t nq) {
   // the bookkeeping of nq pqx_prepare(MODE_Q) calls: every local instance ends with one row
   for (size_t j = 0; j < nq; j++) T.max_num_proofs /= 2;
   for (size_t p = 0; p < P; p++) T.num_proofs[p] = 1;
-  int rc = pqx_pack(ctx, v, a, kWsPqxA);
+  int rc = pqx_pack(ctx, v, a, Ws::PqxA);
   if (rc) return rc;
   if (dom) {
     KScope ks(ctx, "sc_fold_q_all", 32.0 * (double)(reads + dom));
@@ -1740,7 +1739,7 @@ int pqx_bound_q_prefix(spg_ctx* ctx, PqxDev& T, const Fq* E, size_t nq) {
   if (dom >= ((size_t)1 << 32)) return set_err(ctx, SPG_E_ARG, "q bound: domain");
   T.max_num_proofs >>= nq;  // the bookkeeping of nq pqx_prepare(MODE_Q) calls
   T.num_proofs = after;
-  int rc = pqx_pack(ctx, v, a, kWsPqxA);
+  int rc = pqx_pack(ctx, v, a, Ws::PqxA);
   if (rc) return rc;
   if (dom) {
     KScope ks(ctx, "sc_fold_q_prefix", 32.0 * (double)(reads + dom));

@@ -1169,7 +1169,7 @@ struct SnarkVerifier : V {
 // DensePolynomial::commit (no blinds) of a host vector, through the device Hyrax path
 PolyComm commit_vec(spg_ctx* ctx, ProverGens& g, FqV Z) {
   Z.resize(npow2(std::max<size_t>(Z.size(), 1)), fq_zero());
-  Fq* d = (Fq*)ws_get(ctx, 96, Z.size() * sizeof(Fq) + 64);
+  Fq* d = (Fq*)ws_get(ctx, Ws::VerifyZ, Z.size() * sizeof(Fq) + 64);
   if (!d) throw Fail{"workspace"};
   if (hipMemcpy(d, Z.data(), Z.size() * sizeof(Fq), hipMemcpyHostToDevice) != hipSuccess) throw Fail{"upload"};
   std::vector<Pt> out;

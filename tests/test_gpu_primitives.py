@@ -17,7 +17,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "spartan-parallel_amd")
 # (C, G) of bullet_round_comb / comb_msm_parts in csrc/msm.hip (window width, window groups: SPG_BCOMB_G) and the workgroup sizes
-# quad_block_sum / row_block_sum are launched with (k_layer_round_q, k_layer_pair, k_layer_triple in csrc/spark.hip,
+# quad_block_sum / row_block_sum are launched with (k_layer_round_q, k_layer_pair, k_layer_triple in csrc/layers.hip,
 # quad_grid_post<256>, k_phase1_pair<256>, k_phase2_pair<256> in csrc/sumcheck.hip): extend with the launch tables
 RECODE_SHAPES = [(13, 4), (13, 10), (12, 4), (12, 8), (12, 11)]
 BLOCK_SIZES = [64, 256]

@@ -85,7 +85,7 @@ def test_hash_layer_r_hash_zero(ctx, oracle):
 
 # ------------------------------------------------------------------------------------------------ trees
 # 2048 / 4096: the largest M whose levels all come from k_tree_top, and the smallest with a k_tree_level launch
-# (spark.hip tree_build: levels of more than kTopHalf = 1024 products per circuit take one grid-wide launch each)
+# (layers.hip tree_build: levels of more than kTopHalf = 1024 products per circuit take one grid-wide launch each)
 @pytest.mark.parametrize("nc", [1, 4, 8])
 @pytest.mark.parametrize("M", [2, 4, 64, 1024, 2048, 4096, 1 << 14])
 def test_prodc_new(ctx, oracle, M, nc):
@@ -287,7 +287,7 @@ def test_prodc_prove_batched_launch_forms(ctx, oracle):
         assert res.stdout.strip().splitlines()[-1] == want, env
 
 
-# the lane form's grid (spark.hip layer_grid; only rounds that are neither wide nor in the quad form take it, and only
+# the lane form's grid (layers.hip layer_grid; only rounds that are neither wide nor in the quad form take it, and only
 # single rounds): every round ticketed over several workgroups, one workgroup looping over everything, and 1 or 8
 # elements per thread of the wider grids
 LANE = {"SPG_LAYER_QUAD": "0", "SPG_WIDE_MIN": "1000000000000", "SPG_LAYER_PAIR": "0", "SPG_LAYER_TRIPLE": "0"}

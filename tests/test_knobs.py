@@ -56,7 +56,7 @@ PINNED = [
     ("SPG_COMB_GMIN", "LONG", "1", 0),
     ("SPG_BIG_COMB_G", "LONG", "2", 0),
     # msm.hip
-    ("SPG_HALVED_ENC", "ON", "on", 0),  # (also spark.hip; snark.hip read it per prove)
+    ("SPG_HALVED_ENC", "ON", "on", 0),  # (also hyrax.hip; snark.hip read it per prove)
     ("SPG_MSM_BIG", "ON", "on", 0),
     ("SPG_SMSM_QUAD", "ON", "on", 0),
     ("SPG_SMSM_C", "INT", "0", 1),
@@ -113,7 +113,7 @@ PINNED = [
     ("SPG_CQ_SIDE", "ON", "on", 1),
     ("SPG_VERIFY_VMSM", "OFF", "off", 0),
     ("SPG_RCCL_TIMEOUT_S", "LONG", "600", 0),
-    # spark.hip
+    # hyrax.hip, layers.hip
     ("SPG_HOST_ENC_MAX", "LONG", "384", 0),
     ("SPG_HOST_COMMIT_MAX", "LONG", "0", 0),
     ("SPG_TREE_TOP", "LONG", "1024", 0),
@@ -143,7 +143,7 @@ PINNED_CLAMPS = {
     "SPG_ITEM_K": ("1", "-"),  # msm.hip
     "SPG_SEG_M": ("1", "-"),
     "SPG_FINALS_K": ("1", "-"),  # proto.hip
-    "SPG_LAYER_EPT": ("1", "-"),  # spark.hip
+    "SPG_LAYER_EPT": ("1", "-"),  # layers.hip
     "SPG_RCCL_TIMEOUT_S": ("1", "-"),  # rccl.hip
 }
 
