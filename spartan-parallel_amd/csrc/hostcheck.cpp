@@ -21,6 +21,7 @@
 #include "knobs.hpp"
 #include "msm_plan.hpp"
 #include "pe_plan.hpp"
+#include "r1cs_desc.hpp"
 #include "satcheck.hpp"
 #include "snark_shape.hpp"
 #include "spark_shape.hpp"
@@ -639,6 +640,48 @@ void spgh_tree_tops(uint64_t* v, size_t W, uint64_t* prod) {
   for (size_t i = 0; i < W; i++) t[i] = ldq(v + 4 * i);
   stq(prod, tree_tops_host(t.data(), W));
   for (size_t i = 0; i < 2 * W; i++) stq(v + 4 * i, t[i]);
+}
+
+// ---- r1cs_desc.hpp: the descriptor builders of the R1CS table kernels (tests/test_r1cs_tables_host.py)
+// pqx_shape(rows, secs, cols): off[n] and the total
+void spgh_pqx_shape(size_t n, const size_t* rows, size_t secs, const size_t* cols, size_t* off, size_t* total) {
+  const PqxDev T = pqx_shape({rows, rows + n}, secs, {cols, cols + n}, npow2(n), 1, 1, 1);
+  std::copy(T.off.begin(), T.off.end(), off);
+  *total = T.total;
+}
+// k_spmv's list as the callers build it, over the instances [p0, p1) of P: the (proofs, 1, cons) table of those
+// instances gives the offsets, then sp_descs. single: one matrix triple; log_ni = 1: the prover's form, 0: the
+// multiply_vec_block seam's. out[8 p ..] = (dom_off, out_off, pi, lg_q, nrows, lg_rows, ni, lg_ni); returns p1 - p0
+size_t spgh_r1cs_sp_descs(const size_t* proofs, const size_t* cons, const size_t* inputs, size_t p0, size_t p1, int single,
+                          int log_ni, uint64_t* out) {
+  const std::vector<size_t> lp(proofs + p0, proofs + p1), lc(cons + p0, cons + p1), li(inputs + p0, inputs + p1);
+  const PqxDev Az = pqx_shape(lp, 1, lc, 1, 1, 1, 1);
+  const std::vector<SpDesc> d = sp_descs(lp, lc, li, Az.off, p0, single != 0, log_ni != 0);
+  for (size_t p = 0; p < d.size(); p++) {
+    const uint64_t row[8] = {d[p].dom_off, d[p].out_off, d[p].pi, d[p].lg_q, d[p].nrows, d[p].lg_rows, d[p].ni, d[p].lg_ni};
+    memcpy(out + 8 * p, row, sizeof(row));
+  }
+  return d.size();
+}
+// k_abc's list over the n matrices pi0, pi0 + 1, .. whose widths are inputs[pi0 ..]: the (1, secs, inputs) table gives
+// the offsets, then abc_descs. out[6 p ..] = (dom_off, out_off, pi, ni, lg_ni, pad)
+void spgh_r1cs_abc_descs(const size_t* inputs, size_t pi0, size_t n, size_t secs, uint64_t* out) {
+  const std::vector<size_t> li(inputs + pi0, inputs + pi0 + n);
+  const PqxDev ABC = pqx_shape(std::vector<size_t>(n, 1), secs, li, 1, 1, 1, 1);
+  const std::vector<AbcDesc> d = abc_descs(ABC.ani, ABC.off, pi0);
+  for (size_t p = 0; p < n; p++) {
+    const uint64_t row[6] = {d[p].dom_off, d[p].out_off, d[p].pi, d[p].ni, d[p].lg_ni, d[p].pad};
+    memcpy(out + 6 * p, row, sizeof(row));
+  }
+}
+// mat_descs of a handle with Pm matrices: out[4 p ..] = (rp[0], rp[1], rp[2], cp)
+void spgh_r1cs_mat_descs(size_t Pm, const uint64_t* rp_off, const uint64_t* cp_off, uint64_t* out) {
+  spg_r1cs_inst I;
+  I.num_instances = Pm;
+  I.rp_off.assign(rp_off, rp_off + 3 * Pm);
+  I.cp_off.assign(cp_off, cp_off + Pm);
+  const std::vector<MatDesc> md = mat_descs(I);
+  memcpy(out, md.data(), Pm * sizeof(MatDesc));
 }
 
 // ---- the multi-round decoders of hostmath.hpp. ev: a pair's 15 or a triple's 64 posted values; r: r_j (and r_j+1);

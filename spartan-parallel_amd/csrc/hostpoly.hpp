@@ -1,5 +1,5 @@
-// spg — small host-side helpers shared by the prover drivers (r1cs.hip, spark.hip, layers.hip, hyrax.hip): sizes, eq tables,
-// round polynomials, scalar (de)serialisation at the C-ABI.
+// spg — small host-side helpers shared by the prover drivers (r1cs.hip, r1cs_tables.hip, r1cs_seams.hip, spark.hip,
+// layers.hip, hyrax.hip): sizes, eq tables, round polynomials, scalar (de)serialisation at the C-ABI.
 #pragma once
 #include <initializer_list>
 #include <chrono>

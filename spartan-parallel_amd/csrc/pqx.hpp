@@ -10,6 +10,12 @@
 
 #include "field.hpp"
 
+#if defined(__HIPCC__)
+#define SPG_PQX_HD __host__ __device__ inline
+#else
+#define SPG_PQX_HD inline  // (r1cs_desc.hpp brings PqxDev into hostcheck.cpp)
+#endif
+
 namespace spg {
 
 static const int kMaxP = 32;  // instances whose descriptors ride in the kernel arguments (two PqxArgs stay under
@@ -35,9 +41,9 @@ struct PqxArgs {
   PqxInst in[kMaxP];
 };
 // descriptor of instance p (kernel argument or device copy)
-__host__ __device__ inline const PqxInst& pinst(const PqxArgs& a, int p) { return a.ext ? a.ext[p] : a.in[p]; }
+SPG_PQX_HD const PqxInst& pinst(const PqxArgs& a, int p) { return a.ext ? a.ext[p] : a.in[p]; }
 
-__host__ __device__ inline size_t pqx_off(const PqxInst& d) { return ((size_t)d.off_hi << 32) | d.off_lo; }
+SPG_PQX_HD size_t pqx_off(const PqxInst& d) { return ((size_t)d.off_hi << 32) | d.off_lo; }
 
 struct PqxDev {
   Fq* d = nullptr;
@@ -53,7 +59,7 @@ struct PqxDev {
 
 }  // namespace spg
 
-// the C-ABI handle of a resident DensePolynomialPqx (seams.hip; spg_r1cs_multiply_vec_block in r1cs.hip makes them too)
+// the C-ABI handle of a resident DensePolynomialPqx (seams.hip; the seams of r1cs_seams.hip make them too)
 struct spg_pqx {
   spg::PqxDev T;
 };

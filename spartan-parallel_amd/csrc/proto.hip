@@ -816,3 +816,61 @@ int dotproduct_log_prove(spg_ctx* ctx, ProverGens& g, Tr& t, Tape& tape, const F
 }
 
 }  // namespace spg
+
+using namespace spg;
+
+// ------------------------------------------------------------------------------------ C-ABI: transcript, random tape
+extern "C" int spg_transcript_new(const char* label, spg_transcript** out) {
+  if (!label || !out) return SPG_E_ARG;
+  *out = new spg_transcript(label);
+  return SPG_OK;
+}
+extern "C" int spg_transcript_new_callbacks(spg_transcript_append_fn append, spg_transcript_challenge_fn challenge,
+                                            void* user, spg_transcript** out) {
+  if (!append || !challenge || !out) return SPG_E_ARG;
+  spg_transcript* t = new spg_transcript("");  // its own merlin state is never used
+  t->t.cb = std::make_shared<TrCallbacks>();
+  t->t.cb->append = append;
+  t->t.cb->challenge = challenge;
+  t->t.cb->user = user;
+  *out = t;
+  return SPG_OK;
+}
+extern "C" int spg_transcript_append_message(spg_transcript* t, const char* label, const uint8_t* msg, size_t len) {
+  if (!t || !label || (!msg && len)) return SPG_E_ARG;
+  t->t.message(label, msg, len);
+  return t->t.failed() ? SPG_E_CALLBACK : SPG_OK;
+}
+extern "C" int spg_transcript_append_scalar(spg_transcript* t, const char* label, const uint64_t* scalar_mont) {
+  if (!t || !label || !scalar_mont) return SPG_E_ARG;
+  t->t.scalar(label, ld_fq(scalar_mont));
+  return t->t.failed() ? SPG_E_CALLBACK : SPG_OK;
+}
+extern "C" int spg_transcript_challenge_scalar(spg_transcript* t, const char* label, uint64_t* out_mont) {
+  if (!t || !label || !out_mont) return SPG_E_ARG;
+  st_fq(out_mont, t->t.challenge(label));
+  return t->t.failed() ? SPG_E_CALLBACK : SPG_OK;
+}
+extern "C" int spg_transcript_challenge_bytes(spg_transcript* t, const char* label, uint8_t* out, size_t len) {
+  if (!t || !label || (!out && len)) return SPG_E_ARG;
+  t->t.challenge_bytes(label, out, len);
+  return t->t.failed() ? SPG_E_CALLBACK : SPG_OK;
+}
+extern "C" int spg_transcript_free(spg_transcript* t) {
+  delete t;
+  return SPG_OK;
+}
+extern "C" int spg_random_tape_new(const char* name, const uint64_t* init_mont, spg_random_tape** out) {
+  if (!name || !init_mont || !out) return SPG_E_ARG;
+  *out = new spg_random_tape(name, ld_fq(init_mont));
+  return SPG_OK;
+}
+extern "C" int spg_random_tape_scalar(spg_random_tape* tp, const char* label, uint64_t* out_mont) {
+  if (!tp || !label || !out_mont) return SPG_E_ARG;
+  st_fq(out_mont, tp->t.scalar(label));
+  return SPG_OK;
+}
+extern "C" int spg_random_tape_free(spg_random_tape* tp) {
+  delete tp;
+  return SPG_OK;
+}

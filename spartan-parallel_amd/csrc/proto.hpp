@@ -221,7 +221,7 @@ void spark_comm_append(const spg_spark* S, Tr& t);
 int spark_prove_core(spg_ctx* ctx, spg_spark* S, FqV ex, FqV ey, const FqV& evals, Tr& t, Tape& tape, Writer& w,
                      const Shard& sh = Shard());
 
-// ---- R1CS witness from parts (r1cs.hip) ----
+// ---- R1CS witness from parts (r1cs_objects.hip) ----
 struct WPart {  // one ProverWitnessSecInfo: per instance (num_proofs x num_inputs) scalars at src (host or device)
   std::vector<size_t> num_proofs, num_inputs;
   std::vector<const Fq*> src;

@@ -1,6 +1,6 @@
 // spg — k_sat_check: Az[i] Bz[i] == Cz[i] over the flat domain of three (p, q_rev, 0, x_rev) tables, the check of the
 // reference's R1CSInstance::is_sat (src/r1csinstance.rs:322-357) as one streaming pass over what k_spmv wrote
-// (r1cs.hip). A lane takes one stored position: three 32-byte loads, one product, a comparison of canonical residues.
+// (r1cs_tables.hip). A lane takes one stored position: three 32-byte loads, one product, a comparison of canonical residues.
 // Only a violating lane looks its descriptor up, to turn the stored position back into the natural key (q and row
 // bit-reversed back); a wavefront that found one adds its count and min-reduces its key into the 16-byte record with
 // two 64-bit atomics. A satisfying table performs none. Modelled traffic: 96 bytes per row.

@@ -7,7 +7,7 @@
 //     instance commitments -> transcript, block / pairwise sort and padding             (host, O(#instances))
 //     permutation / memory witnesses w2, w3, w3_shifted    lib.rs:1299-1955, 831-968    (host, O(Q * 8))
 //     Hyrax commitments of every witness polynomial        lib.rs:1957-2221             commit_dev (device MSMs)
-//     three R1CSProof::prove + multi_evaluate + R1CSEvalProof                             r1cs.hip / spark.hip
+//     three R1CSProof::prove + multi_evaluate + R1CSEvalProof                             r1cs.hip, r1cs_seams.hip / spark.hip
 //     perm product, shift and IO PolyEvalProofs            lib.rs:2534-2693, 187-446    polyeval.hip (pe_prove.hpp)
 // The host side is the transcript, the small witness recurrences and the bincode writer; every O(N) table
 // (block_vars, Az/Bz/Cz, SPARK dense representations) lives in HBM. SnarkProver::run calls one stage per section

@@ -63,10 +63,10 @@ namespace spg {
   X(PqxA, "sumcheck.hip", "Pqx instance descriptors, first operand") \
   X(PqxB, "sumcheck.hip", "Pqx instance descriptors, second operand") \
   /* R1CSProof::prove */ \
-  X(R1csAz, "r1cs.hip", "Az") \
-  X(R1csBz, "r1cs.hip", "Bz") \
-  X(R1csCz, "r1cs.hip", "Cz") \
-  X(R1csZ, "r1cs.hip", "the Z table") \
+  X(R1csAz, "r1cs_tables.hip", "Az") \
+  X(R1csBz, "r1cs_tables.hip", "Bz") \
+  X(R1csCz, "r1cs_tables.hip", "Cz") \
+  X(R1csZ, "r1cs_tables.hip", "the Z table") \
   X(R1csAbc, "r1cs.hip", "the bound ABC table of phase 2") \
   X(R1csTp, "r1cs.hip", "eq table over p") \
   X(R1csTq, "r1cs.hip", "eq table over q") \
@@ -75,15 +75,15 @@ namespace spg {
   X(R1csEqP, "r1cs.hip", "eq(rp)") \
   X(R1csPart, "r1cs.hip", "per-workgroup round partials") \
   X(R1csOut3, "r1cs.hip", "a round's three evaluations") \
-  X(R1csDesc, "r1cs.hip", "instance descriptors") \
+  X(R1csDesc, "r1cs_tables.hip", "instance descriptors") \
   X(R1csL, "r1cs.hip", "L vectors of the witness openings") \
   X(R1csBoundPart, "r1cs.hip", "partial bound rows") \
   X(R1csBoundOut, "r1cs.hip", "bound rows (LZ)") \
-  X(R1csEvRx, "r1cs.hip", "eq(rx) of the matrix evaluations") \
-  X(R1csEvRy, "r1cs.hip", "eq(ry) of the matrix evaluations") \
-  X(R1csEvPart, "r1cs.hip", "partial matrix evaluations") \
-  X(R1csEvOut, "r1cs.hip", "matrix evaluations") \
-  X(R1csEvDesc, "r1cs.hip", "matrix descriptors") \
+  X(R1csEvRx, "r1cs_seams.hip", "eq(rx) of the matrix evaluations") \
+  X(R1csEvRy, "r1cs_seams.hip", "eq(ry) of the matrix evaluations") \
+  X(R1csEvPart, "r1cs_seams.hip", "partial matrix evaluations") \
+  X(R1csEvOut, "r1cs_seams.hip", "matrix evaluations") \
+  X(R1csEvDesc, "r1cs_seams.hip", "matrix descriptors") \
   X(R1csC1, "r1cs.hip", "phase 1 claim vectors") \
   X(R1csC2, "r1cs.hip", "phase 2 claim vectors") \
   X(R1csTq2, "r1cs.hip", "second eq table over q") \

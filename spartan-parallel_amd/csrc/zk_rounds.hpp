@@ -1,4 +1,4 @@
-// spg — the round bookkeeping of the two ZK sumchecks of R1CSProof::prove (r1cs.hip) and of their seams (seams.hip).
+// spg — the round bookkeeping of the two ZK sumchecks of R1CSProof::prove (the Prover of r1cs.hip) and of their seams (seams.hip).
 #pragma once
 #include "hostpoly.hpp"
 #include "knobs.hpp"

@@ -93,7 +93,7 @@ PINNED = [
     ("SPG_EQ_LDS", "ON", "on", 0),
     ("SPG_EQ_MULTI", "ON", "on", 0),
     ("SPG_P1_ROWS", "ON", "on", 0),
-    # r1cs.hip
+    # r1cs.hip, r1cs_tables.hip (the Z fill and k_spmv forms), r1cs_objects.hip (SPG_WIT_IN_PLACE)
     ("SPG_TAPE_AHEAD", "ON", "on", 0),
     ("SPG_SC_FUSE", "ON", "on", 0),
     ("SPG_Z_TILED", "ON", "on", 0),
